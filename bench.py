@@ -5,8 +5,13 @@ a 32768 x 32768 fp64 grid (ghost-frame convention, T=2 inside, Dirichlet T=1
 frame, fortran/hip/heat.F90:274-282), slab-decomposed over N GPUs (strong
 scaling: the grid is fixed), RCCL halo exchange over xGMI.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run does what the headline figure needs: it sets up, warms up, times
+the K steps and prints the result line. --full adds the checks beside it
+(--verify, --field-check: the timed field against an independent engine);
+--dump-outputs DIR writes the field the timed steps left to DIR/field.npy.
 
 W untimed warm-up steps, then exactly K FTCS time steps, bracketed by a
 barrier + device synchronisation on both sides; the time is the MAX over
@@ -31,7 +36,7 @@ this benchmark's IC (T = 2 inside, 1 on the frame) every value stays in
 [1, 2], so sum - 4c is exact (Sterbenz) and the field is bitwise identical to
 --arith exact (GPU-checked: tests/test_jacobi.py::
 test_hip_jacobi_equals_exact_on_reference_ic). --arith auto (fma, also bitwise
-identical here) and exact remain available. The timed field is checked
+identical here) and exact remain available. With --full the timed field is checked
 bitwise against the run-time compiled r * sum form and against the reference
 rounding: bitwise on this IC, within the stated bound on data where sum - 4c
 rounds (--ic hotspot, the zero + hot-spot data BASELINE.json names).
@@ -66,6 +71,49 @@ def arith_name(r, arith):
     if arith == "auto":
         return "fma" if r > 0 and math.frexp(r)[0] == 0.5 else "exact"
     return arith
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: the most it writes
+
+
+def sample_rows(total, row_bytes, budget=DUMP_BYTES):
+    """Rows of a `total`-row field that --dump-outputs writes, ascending: all of
+    them when they fit the budget, else the first and last quarter of the rows
+    that fit (the Dirichlet frame's neighbourhood) and seeded random rows of
+    the middle — a function of the arguments alone, the same on every run."""
+    import numpy as np
+    fit = max(4, int(budget // row_bytes))
+    if total <= fit:
+        return np.arange(total, dtype=np.int64)
+    edge = fit // 4
+    mid = np.random.default_rng(20240229).choice(total - 2 * edge, size=fit - 2 * edge, replace=False) + edge
+    return np.concatenate([np.arange(edge), np.sort(mid), np.arange(total - edge, total)]).astype(np.int64)
+
+
+def slab_rows(s, local_rows, device):
+    """Owned columns of the solver's current field at its local rows `local_rows`
+    (ascending) as a host array. On the GPU only these rows leave the device:
+    each run of consecutive rows is packed into one device buffer."""
+    import ctypes as C
+    import numpy as np
+    from heat2d.ops import _native as N
+    s.synchronize()
+    if device is None or len(local_rows) == s.nrows:
+        return s.download()[local_rows]
+    import torch
+    assert len(local_rows) and 0 <= local_rows[0] and local_rows[-1] < s.nrows, (local_rows[0], local_rows[-1])
+    info = s.info()
+    buf = torch.empty(len(local_rows) * s.ncols, dtype=torch.float64 if s.dtype == N.F64 else torch.float32,
+                      device=f"cuda:{device}")
+    torch.cuda.synchronize()
+    starts = np.flatnonzero(np.diff(local_rows, prepend=local_rows[0] - 2) != 1)
+    for a, b in zip(starts, list(starts[1:]) + [len(local_rows)]):
+        N.call("heat2d_pack_rows", s.dtype, C.c_void_p(info["field"]), C.byref(s.layout), int(local_rows[a]),
+               int(b - a), C.c_void_p(buf.data_ptr() + int(a) * s.ncols * buf.element_size()),
+               C.c_void_p(info["stream"]))
+    s.synchronize()
+    torch.cuda.synchronize()
+    return buf.cpu().numpy().reshape(len(local_rows), s.ncols)
 
 
 def _free_port():
@@ -201,13 +249,23 @@ def main():
                     help="every rank on GPU 0: the exact multi-process path on a 1-GPU box (RCCL refuses two ranks "
                          "on one GPU, so auto falls back to ipc); a correctness / overhead rehearsal, not a node "
                          "throughput")
-    ap.add_argument("--verify", default="on", choices=["on", "off"],
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks beside the headline figure after the timed run: --verify on and "
+                         "--field-check auto unless given. A plain run sets up, warms up, times the steps and "
+                         "prints the result line ('verified' and 'timed_field_check' null)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the field they left as DIR/field.npy (the run's dtype; rank "
+                         "0 writes the whole grid's rows). A field over 48 MiB is sampled in whole rows, the same "
+                         "rows on every run: the first and last ones and seeded random ones between (sample_rows)")
+    ap.add_argument("--verify", default=None, choices=["on", "off"],
                     help="after the timed run: a small uneven rough-data problem on the same transport kind and "
-                         "rank layout, gathered and compared bitwise with the NumPy golden (JSON 'verified')")
-    ap.add_argument("--field-check", default="auto", choices=["auto", "full", "windows", "off"],
+                         "rank layout, gathered and compared bitwise with the NumPy golden (JSON 'verified'); "
+                         "default: on with --full, else off")
+    ap.add_argument("--field-check", default=None, choices=["auto", "full", "windows", "off"],
                     help="after the timed run (untimed): its field checked against the run-time compiled one-step "
                          "kernel in the reference arithmetic from the same IC (JSON 'timed_field_check'); auto: the "
-                         "whole slab when a second copy fits, else row windows at the slab boundaries and middle")
+                         "whole slab when a second copy fits, else row windows at the slab boundaries and middle; "
+                         "default: auto with --full, else off")
     ap.add_argument("--window-rows", type=int, default=64, help="rows per checked window (--field-check windows)")
     ap.add_argument("--measure-hbm", action="store_true",
                     help="1 rank: after the run, re-run the timed region twice under rocprofv3 --pmc (FETCH_SIZE, "
@@ -221,6 +279,10 @@ def main():
     args = ap.parse_args()
     import faulthandler
     faulthandler.enable()  # Python stacks on a fatal signal (the native library adds its backtrace)
+    if args.verify is None:
+        args.verify = "on" if args.full else "off"
+    if args.field_check is None:
+        args.field_check = "auto" if args.full else "off"
     if args.transport == "peer":
         args.transport = "ipc"
     if args.graph == "on":  # replay every measured schedule, long cycles too
@@ -679,6 +741,22 @@ def main():
         tr.close()
         return
     elapsed = timed(s)
+    if args.dump_outputs:
+        # the field the timed steps left, before anything else touches the solver:
+        # every rank's share of the sampled rows of the whole grid, written by rank 0
+        import numpy as np
+        es_d = 8 if args.dtype == "fp64" else 4
+        total, base = (s.nrows, 0) if world == 1 else (prob.n_owned, s.row0)
+        want = sample_rows(total, s.ncols * es_d)
+        mine = want[(want >= base) & (want < base + s.nrows)] - base
+        part = slab_rows(s, mine, device if hip else None) if len(mine) else np.empty((0, s.ncols), s.np_dtype)
+        if world > 1:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(part, parts, dst=0)
+            part = np.concatenate(parts, axis=0) if rank == 0 else None
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "field.npy"), part)
 
     pts = float(prob.n_owned) * float(rows or prob.n_owned)
     gpts = pts * args.steps / elapsed / 1e9

@@ -30,7 +30,7 @@ def run_bench(nproc, *args, port):
 
 @pytest.mark.parametrize("nproc,dtype", [(2, "fp64"), (3, "fp32")])
 def test_bench_json_line_multi_rank(nproc, dtype):
-    d = run_bench(nproc, "--grid", "100", "--steps", "24", "--warmup", "4", "--dtype", dtype, "--tb", "4",
+    d = run_bench(nproc, "--full", "--grid", "100", "--steps", "24", "--warmup", "4", "--dtype", dtype, "--tb", "4",
                   port=29560 + nproc)
     assert KEYS <= set(d)
     assert d["n_gpus"] == nproc and d["steps"] == 24 and d["warmup"] == 4 and d["dtype"] == dtype
@@ -162,7 +162,7 @@ def test_bench_auto_transport_falls_back_to_ipc_share_gpu():
     refuses four ranks on one GPU, every rank skips it alike and the run
     proceeds on the IPC transport (the fallback a node whose RCCL cannot
     initialise takes), then verifies the decomposition bitwise."""
-    common = ["--grid", "8192", "--steps", "20", "--warmup", "5", "--check"]
+    common = ["--full", "--grid", "8192", "--steps", "20", "--warmup", "5", "--check"]
     four = run_plain("--gpus", "4", "--share-gpu", *common)
     ch = four["config"]["transport_choice"]
     assert four["config"]["transport"] == "ipc" and ch["chosen"] == "ipc" and ch["requested"] == "auto", ch
@@ -199,8 +199,8 @@ def test_bench_rehearsal_then_verification(transport):
     over a 1-rank RCCL communicator / the IPC loop transport), then the
     verification problem on a fresh solver: the loop transports' teardown
     leaves no HIP error behind for the next launch."""
-    d = run_plain("--rehearse-comm", "--transport", transport, "--grid", "4096", "--rows", "1024", "--steps", "20",
-                  "--warmup", "5")
+    d = run_plain("--full", "--rehearse-comm", "--transport", transport, "--grid", "4096", "--rows", "1024", "--steps",
+                  "20", "--warmup", "5")
     assert d["config"]["transport"] == f"{transport}-loop" and d["verified"] is True, d
     assert d["halo_bytes"] > 0
     # what the fabric reports (RCCL: ncclCommCount / ncclCommCuDevice of the 1-rank communicator)
@@ -223,8 +223,8 @@ def test_bench_ipc_attach_is_bounded(transport):
     env = dict(os.environ, HEAT2D_IPC_ATTACH_STALL="1", HEAT2D_IPC_ATTACH_TIMEOUT="5", OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
     t0 = time.time()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--grid", "2048",
-                        "--steps", "4", "--warmup", "1", "--transport", transport, "--edge-shift", "0"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--share-gpu", "--grid",
+                        "2048", "--steps", "4", "--warmup", "1", "--transport", transport, "--edge-shift", "0"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert "did not return within" in p.stderr, p.stderr[-3000:]
     assert time.time() - t0 < 240
@@ -249,8 +249,8 @@ def test_bench_ipc_field_in_the_stalling_size_window():
     the timed run and its field check go through (bitwise)."""
     env = dict(os.environ, HEAT2D_IPC_ATTACH_TIMEOUT="20", HEAT2D_IPC_ATTACH_LOG="1", OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--transport",
-                        "ipc", "--grid", "23170", "--steps", "4", "--warmup", "1", "--verify", "off"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--share-gpu",
+                        "--transport", "ipc", "--grid", "23170", "--steps", "4", "--warmup", "1", "--verify", "off"],
                        capture_output=True, text=True, timeout=280, env=env)
     assert p.returncode == 0, failure_text(p.stderr)
     d = json.loads(p.stdout.strip().splitlines()[-1])
@@ -320,8 +320,8 @@ def test_bench_timed_field_check_windows_cpu(nproc):
     """--field-check windows (what a grid too big for a second copy gets): row
     windows at both slab boundaries and the middle of every slab, each run by a
     single-rank reference solver with steps + 1 rows of margin, bitwise."""
-    args = ["--backend", "cpu", "--gpus", str(nproc), "--grid", "150", "--steps", "12", "--warmup", "3", "--tb", "4",
-            "--field-check", "windows", "--window-rows", "16", "--verify", "off"]
+    args = ["--full", "--backend", "cpu", "--gpus", str(nproc), "--grid", "150", "--steps", "12", "--warmup", "3", "--tb",
+            "4", "--field-check", "windows", "--window-rows", "16", "--verify", "off"]
     d = run_plain(*args)
     fc = d["timed_field_check"]
     assert fc["mode"] == "windows" and fc["ok"] is True and fc["mismatches"] == 0, fc
@@ -334,8 +334,8 @@ def test_bench_edge_shift_cpu(field_check):
     of a slab) to the middle ones; the timed field is checked against a
     reference on the same shifted layout (full) or by row windows, and the
     JSON reports the rows."""
-    d = run_plain("--backend", "cpu", "--gpus", "4", "--grid", "100", "--steps", "12", "--warmup", "3", "--tb", "4",
-                  "--edge-shift", "5", "--field-check", field_check)
+    d = run_plain("--full", "--backend", "cpu", "--gpus", "4", "--grid", "100", "--steps", "12", "--warmup", "3", "--tb",
+                  "4", "--edge-shift", "5", "--field-check", field_check)
     dec = d["config"]["decomposition"]
     assert dec["edge_shift"] == 5 and dec["rows"] == [20, 30, 30, 20] and dec["balance"] is None
     assert [r["rows"] for r in d["per_rank"]] == [20, 30, 30, 20]
@@ -349,7 +349,7 @@ def test_bench_edge_shift_measured_cpu():
     default (every rank rehearses its own slab, the shifts are gathered and
     decided alike on every rank, the real run is built on the kept shift),
     with the CPU twin's timings; whatever it decides, the run is bitwise."""
-    d = run_bench(4, "--grid", "400", "--steps", "12", "--warmup", "3", "--tb", "4", "--edge-shift", "measure",
+    d = run_bench(4, "--full", "--grid", "400", "--steps", "12", "--warmup", "3", "--tb", "4", "--edge-shift", "measure",
                   port=29574)
     dec = d["config"]["decomposition"]
     bal = dec["balance"]
@@ -369,8 +369,8 @@ def test_bench_hotspot_jacobi_check_cpu(ic):
     r * sum form and against the reference rounding — bitwise on the
     Sterbenz-safe reference IC, within the stated bound on the hot spot
     (values in [0, 1]: sum - 4c can round)."""
-    d = run_plain("--backend", "cpu", "--gpus", "2", "--grid", "257", "--steps", "40", "--warmup", "3", "--tb", "6",
-                  "--ic", ic, "--verify", "off")
+    d = run_plain("--full", "--backend", "cpu", "--gpus", "2", "--grid", "257", "--steps", "40", "--warmup", "3", "--tb",
+                  "6", "--ic", ic, "--verify", "off")
     assert d["config"]["arith"] == "jacobi (r = 1/4)" and d["config"]["ic"] == ic
     fc = d["timed_field_check"]
     assert fc["ok"] is True and fc["engine"] == "cpu-jacobi" and fc["mismatches"] == 0, fc
@@ -384,12 +384,12 @@ def test_bench_timed_field_check_sigma_fast_cpu():
     """A non-reference arithmetic is checked within its stated bound (fast form,
     sigma 0.2); the contracted form at that sigma is checked bitwise against the
     contracted one-step reference."""
-    fast = run_plain("--backend", "cpu", "--grid", "96", "--steps", "10", "--warmup", "2", "--tb", "5", "--sigma", "0.2",
-                     "--arith", "fast", "--verify", "off")
+    fast = run_plain("--full", "--backend", "cpu", "--grid", "96", "--steps", "10", "--warmup", "2", "--tb", "5",
+                     "--sigma", "0.2", "--arith", "fast", "--verify", "off")
     fc = fast["timed_field_check"]
     assert fc["ok"] is True and "bound" in fc and fc["max_abs_diff"] <= fc["bound"], fc
-    fma = run_plain("--backend", "cpu", "--grid", "96", "--steps", "10", "--warmup", "2", "--tb", "5", "--sigma", "0.2",
-                    "--arith", "fma")
+    fma = run_plain("--full", "--backend", "cpu", "--grid", "96", "--steps", "10", "--warmup", "2", "--tb", "5", "--sigma",
+                    "0.2", "--arith", "fma")
     assert fma["timed_field_check"]["ok"] is True and fma["timed_field_check"]["mismatches"] == 0
     assert fma["verified"] is True and "bound" in fma["verify"], fma["verify"]
 
@@ -399,12 +399,12 @@ def test_bench_timed_field_check_windows_gpu():
     """The full-HBM grids' check (row windows at the slab boundaries and middle,
     single-rank JIT reference runs) on a 4-rank shared-GPU run, and the fast
     arithmetic within its bound."""
-    d = run_plain("--gpus", "4", "--share-gpu", "--grid", "4099", "--steps", "23", "--warmup", "3",
+    d = run_plain("--full", "--gpus", "4", "--share-gpu", "--grid", "4099", "--steps", "23", "--warmup", "3",
                   "--field-check", "windows", "--verify", "off")
     fc = d["timed_field_check"]
     assert fc["mode"] == "windows" and fc["ok"] is True and fc["mismatches"] == 0, fc
     assert fc["rows_checked"] == 4 * 3 * 64
-    f = run_plain("--grid", "4096", "--steps", "20", "--warmup", "3", "--sigma", "0.2", "--arith", "fast",
+    f = run_plain("--full", "--grid", "4096", "--steps", "20", "--warmup", "3", "--sigma", "0.2", "--arith", "fast",
                   "--verify", "off")
     fc = f["timed_field_check"]
     assert fc["ok"] is True and fc["max_abs_diff"] <= fc["bound"] and fc["mode"] == "full", fc

@@ -64,7 +64,7 @@ def test_bench_grid_max_cpu():
     is the one run, reported with its plan; weak mode plans over the ranks."""
     env = dict(os.environ, OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--backend", "cpu", "--grid", "max",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--backend", "cpu", "--grid", "max",
                         "--dtype", "fp32", "--steps", "4", "--warmup", "1", "--tb", "4", "--verify", "off",
                         "--weak", "--gpus", "2"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -103,8 +103,8 @@ def one_gpu_stats():
 @pytest.mark.parametrize("transport", ["rccl", "ipc", "auto", "best"])
 @pytest.mark.parametrize("P", SIZES)
 def test_bench_multi_gpu_matches_one_gpu(one_gpu_stats, transport, P):
-    d = run_bench("--gpus", str(P), "--grid", "8192", "--steps", "40", "--warmup", "5", "--check", "--transport",
-                  transport)
+    d = run_bench("--full", "--gpus", str(P), "--grid", "8192", "--steps", "40", "--warmup", "5", "--check",
+                  "--transport", transport)
     ch = d["config"]["transport_choice"]
     assert ch["requested"] == transport and d["config"]["transport"] == ch["chosen"]
     if transport in ("rccl", "ipc"):

@@ -134,8 +134,8 @@ def test_bench_multi_rank_cpu_under_asan(tmp_path):
                HEAT2D_LIB=os.path.join(ASAN_DIR, "libheat2d.so"), OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([os.path.join(ASAN_DIR, "python"), os.path.join(root, "bench.py"), "--backend", "cpu",
-                        "--gpus", "3", "--grid", "100", "--steps", "24", "--warmup", "4", "--tb", "4", "--check",
+    p = subprocess.run([os.path.join(ASAN_DIR, "python"), os.path.join(root, "bench.py"), "--full", "--backend",
+                        "cpu", "--gpus", "3", "--grid", "100", "--steps", "24", "--warmup", "4", "--tb", "4", "--check",
                         "--edge-shift", "4"], cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
     assert "AddressSanitizer" not in p.stderr, p.stderr[-4000:]
     assert p.returncode == 0, p.stderr[-3000:]
