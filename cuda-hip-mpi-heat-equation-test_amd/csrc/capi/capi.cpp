@@ -434,6 +434,10 @@ int heat2d_solver_info(void* s, int32_t* tb, int64_t* band, int64_t* steps, void
   });
 }
 
+int heat2d_solver_arith(void* s, int32_t* out) {
+  return guarded([&] { *out = static_cast<Solver*>(s)->config().arith; });
+}
+
 int heat2d_group_create(const heat2d_config* cfg, int nranks, void** out) {
   return guarded([&] { *out = new LoopbackGroup(to_cfg(cfg), nranks); });
 }

@@ -180,6 +180,8 @@ int heat2d_solver_plan(void* s, int k, heat2d_split_plan* out, float* tuned_ms);
 int heat2d_solver_plans_made(void* s, int64_t* out);
 int heat2d_solver_info(void* s, int32_t* tb, int64_t* band, int64_t* steps, void** field,
                        void** stream);
+/* the arithmetic form the solver runs (0 .. 3): cfg.arith with -1 (auto) resolved */
+int heat2d_solver_arith(void* s, int32_t* out);
 
 /* Loopback group: P slabs on one device (or host). */
 int heat2d_group_create(const heat2d_config* cfg, int nranks, void** out);

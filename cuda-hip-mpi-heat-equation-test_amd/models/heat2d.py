@@ -66,6 +66,13 @@ def _cycle_hist(h, reset: bool) -> dict:
     return {k: int(out[k]) for k in range(n) if out[k]}
 
 
+def _arith(h) -> int:
+    """The arithmetic form (ops._native.ARITH code) a native solver runs: "auto" resolved."""
+    v = C.c_int32()
+    N.call("heat2d_solver_arith", h, C.byref(v))
+    return v.value
+
+
 class HeatSolver:
     """Distributed FTCS solver for one rank.
 
@@ -199,6 +206,8 @@ class HeatSolver:
                C.byref(stream))
         return {"tb": tb.value, "band": band.value, "steps": steps.value, "field": field.value,
                 "stream": stream.value, "backend": self.backend, "transport": self.transport.name,
+                "arith": _arith(self._h),  # the resolved code: 0 exact, 1 fma, 2 jacobi, 3 fast
+
                 "rank": self.rank, "size": self.size, "layout": self.layout.as_dict()}
 
     def set_timing(self, on: bool = True) -> None:
@@ -478,6 +487,10 @@ class LoopbackGroup:
 
     def cycle_hist(self, i: int, reset: bool = False) -> dict:
         return _cycle_hist(self._member(i), reset)
+
+    def arith_code(self, i: int) -> int:
+        """The arithmetic form member i runs ("auto" resolved; as HeatSolver.info()["arith"])."""
+        return _arith(self._member(i))
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -177,6 +177,7 @@ _SIGS = {
     "heat2d_solver_layout": (C.c_int, [_P, _LP]),
     "heat2d_solver_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(_I64), C.POINTER(_I64),
                                      C.POINTER(_P), C.POINTER(_P)]),
+    "heat2d_solver_arith": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "heat2d_group_create": (C.c_int, [C.POINTER(Config), C.c_int, C.POINTER(_P)]),
     "heat2d_group_free": (C.c_int, [_P]),
     "heat2d_group_init": (C.c_int, [_P, C.POINTER(IcParams), _P, _P]),

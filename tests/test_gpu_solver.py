@@ -1,6 +1,11 @@
 """GPU numerics: the native HIP engine against the NumPy golden (fp64 reference
 order, bitwise) on a real MI355X. Every test runs the HIP kernels through
-_native/libheat2d.so — there is no fallback path."""
+_native/libheat2d.so — there is no fallback path. Every problem here has
+r = 1/4, where the default ``arith="auto"`` picks ``fma``: these tests run the
+contracted kernels (same bits as the reference rounding at a power-of-two r).
+The one exception, n = 777 (r = 0.25 - 2^-55), runs on smooth sine data, on
+which the two forms cannot be told apart; the unfused form at r != 1/4 on
+rough data is covered in tests/test_exact_general_r.py."""
 import numpy as np
 import pytest
 
