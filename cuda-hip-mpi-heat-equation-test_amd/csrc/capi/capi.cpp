@@ -197,6 +197,28 @@ int heat2d_tb(int dtype, const void* src, void* dst, const heat2d_layout* L, int
   });
 }
 
+int heat2d_tb_bc(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                 double r, void* stream, int64_t tile_rows, int arith, int bc) {
+  return guarded([&] {
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, arith, bc);
+  });
+}
+
+int heat2d_wrap_cols(int dtype, void* field, const heat2d_layout* L, int64_t r0, int64_t r1, void* stream,
+                     int on_device) {
+  return guarded([&] {
+    if (on_device) kern::launch_wrap_cols((DType)dtype, field, to_layout(L), r0, r1, as_stream(stream));
+    else cpu::wrap_cols((DType)dtype, field, to_layout(L), r0, r1);
+  });
+}
+
+int heat2d_wrap_rows(int dtype, void* field, const heat2d_layout* L, int64_t k, void* stream, int on_device) {
+  return guarded([&] {
+    if (on_device) kern::launch_wrap_rows((DType)dtype, field, to_layout(L), k, as_stream(stream));
+    else cpu::wrap_rows((DType)dtype, field, to_layout(L), k);
+  });
+}
+
 int heat2d_init_field(int dtype, void* field, const heat2d_layout* L, const heat2d_ic* ic,
                       const double* xc, const double* yc, void* stream) {
   return guarded([&] { kern::launch_init((DType)dtype, field, to_layout(L), to_ic(ic), xc, yc, as_stream(stream)); });
@@ -230,6 +252,11 @@ int heat2d_unpack_rows(int dtype, void* field, const heat2d_layout* L, int64_t r
 int heat2d_cpu_tb(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                   double r, int arith) {
   return guarded([&] { cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, arith); });
+}
+
+int heat2d_cpu_tb_bc(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                     double r, int arith, int bc) {
+  return guarded([&] { cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, arith, bc); });
 }
 
 int heat2d_cpu_init_field(int dtype, void* field, const heat2d_layout* L, const heat2d_ic* ic, const double* xc,
@@ -362,6 +389,14 @@ int heat2d_solver_upload(void* s, const void* host, int64_t ld) {
   return guarded([&] { static_cast<Solver*>(s)->upload(host, ld); });
 }
 
+int heat2d_solver_upload_field(void* s, const void* host, int64_t ld) {
+  return guarded([&] { static_cast<Solver*>(s)->upload_field(host, ld); });
+}
+
+int heat2d_solver_download_region(void* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, void* host, int64_t ld) {
+  return guarded([&] { static_cast<Solver*>(s)->download_region(r0, r1, c0, c1, host, ld); });
+}
+
 int heat2d_solver_layout(void* s, heat2d_layout* out) {
   return guarded([&] {
     const SlabLayout& L = static_cast<Solver*>(s)->layout();
@@ -438,6 +473,13 @@ int heat2d_solver_arith(void* s, int32_t* out) {
   return guarded([&] { *out = static_cast<Solver*>(s)->config().arith; });
 }
 
+int heat2d_solver_bc(void* s, int32_t* bc_x, int32_t* bc_y) {
+  return guarded([&] {
+    *bc_x = static_cast<Solver*>(s)->config().bc_x;
+    *bc_y = static_cast<Solver*>(s)->config().bc_y;
+  });
+}
+
 int heat2d_group_create(const heat2d_config* cfg, int nranks, void** out) {
   return guarded([&] { *out = new LoopbackGroup(to_cfg(cfg), nranks); });
 }
@@ -456,6 +498,10 @@ int heat2d_group_step(void* g, int64_t n) {
 
 int heat2d_group_upload(void* g, const void* host, int64_t ld) {
   return guarded([&] { static_cast<LoopbackGroup*>(g)->upload(host, ld); });
+}
+
+int heat2d_group_upload_field(void* g, const void* host, int64_t ld) {
+  return guarded([&] { static_cast<LoopbackGroup*>(g)->upload_field(host, ld); });
 }
 
 int heat2d_group_member(void* g, int i, void** solver) {

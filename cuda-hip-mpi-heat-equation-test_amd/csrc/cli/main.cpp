@@ -79,6 +79,9 @@ struct Args {
   bool share_gpu = false;          // --share-gpu: every rank on device 0 (peer transport; tests / rehearsals)
   int autotune = -1;               // --autotune auto|on|off (SolverConfig::autotune)
   int edge_shift = 0;              // --edge-shift N: rows each edge slab gives the middle ones (>= 3 ranks)
+  // --bc-x / --bc-y dirichlet|periodic (SolverConfig::bc_x / bc_y; x = rows, decomposed over ranks).
+  // Empty: not given — dirichlet, or a restart's checkpointed setting
+  std::string bc_x, bc_y;
 };
 
 void usage() {
@@ -89,7 +92,8 @@ void usage() {
       "              [--n N|max] [--ntime N] [--quiet] [--timers] [--engine tb|jit] [--arith auto|exact|fma|jacobi|fast]\n"
       "              [--time-transfers]\n"
       "              [--checkpoint DIR [--checkpoint-every N]] [--restart DIR]\n"
-      "              [--transport auto|rccl|peer] [--share-gpu] [--autotune auto|on|off] [--edge-shift N]\n");
+      "              [--transport auto|rccl|peer] [--share-gpu] [--autotune auto|on|off] [--edge-shift N]\n"
+      "              [--bc-x dirichlet|periodic] [--bc-y dirichlet|periodic]\n");
 }
 
 Args parse_args(int argc, char** argv) {
@@ -134,6 +138,14 @@ Args parse_args(int argc, char** argv) {
     else if (s == "--restart") a.restart = need("--restart");
     else if (s == "--transport") a.transport = need("--transport");
     else if (s == "--share-gpu") a.share_gpu = true;
+    else if (s == "--bc-x" || s == "--bc-y") {
+      const std::string v = need(s.c_str());
+      if (v != "dirichlet" && v != "periodic") {
+        std::fprintf(stderr, "%s must be dirichlet or periodic\n", s.c_str());
+        std::exit(2);
+      }
+      (s == "--bc-x" ? a.bc_x : a.bc_y) = v;
+    }
     else if (s == "--edge-shift") {
       a.edge_shift = std::atoi(need("--edge-shift").c_str());
       if (a.edge_shift < 0) {
@@ -203,7 +215,9 @@ void save_checkpoint(Shared& sh, Solver& s, Transport& tr, int rank, int64_t ste
     m.nu = sh.in.nu;
     m.dom_len = sh.in.dom_len;
     m.r = sh.prob.r;
-    m.edge_shift = a.edge_shift;
+    m.edge_shift = s.config().edge_shift;  // (0 with periodic x: no edge slabs)
+    m.bc_x = s.config().bc_x ? "periodic" : "dirichlet";
+    m.bc_y = s.config().bc_y ? "periodic" : "dirichlet";
     ckpt::write_meta(a.checkpoint, name, m);
   }
   tr.barrier();
@@ -276,6 +290,20 @@ void run_rank(Shared& sh, int rank) {
     // (auto: slabs of >= 2^24 points — decided from the thinnest slab, the same on every rank)
     cfg.autotune = a.autotune;
     cfg.edge_shift = a.edge_shift;
+    // boundary conditions: the flags, or a restart's checkpointed settings (a
+    // flag that says otherwise fails: the resumed run would not be the saved one)
+    std::string bc_x = a.bc_x.empty() ? "dirichlet" : a.bc_x, bc_y = a.bc_y.empty() ? "dirichlet" : a.bc_y;
+    if (!a.restart.empty()) {
+      const ckpt::Meta m0 = ckpt::read_meta(a.restart);
+      HEAT2D_REQUIRE(a.bc_x.empty() || a.bc_x == m0.bc_x,
+                     "--bc-x " + a.bc_x + " conflicts with the checkpoint's bc_x = " + m0.bc_x);
+      HEAT2D_REQUIRE(a.bc_y.empty() || a.bc_y == m0.bc_y,
+                     "--bc-y " + a.bc_y + " conflicts with the checkpoint's bc_y = " + m0.bc_y);
+      bc_x = m0.bc_x;
+      bc_y = m0.bc_y;
+    }
+    cfg.bc_x = bc_x == "periodic" ? 1 : 0;
+    cfg.bc_y = bc_y == "periodic" ? 1 : 0;
     if (a.engine != "tb" && a.engine != "jit") fail(__FILE__, __LINE__, "--engine must be tb or jit");
     cfg.engine = a.engine == "jit" ? 1 : 0;  // jit: hipRTC kernel rendered for this slab (python/cuda/cuda.py)
     if (a.arith != "exact" && a.arith != "fma" && a.arith != "jacobi" && a.arith != "fast" && a.arith != "auto")

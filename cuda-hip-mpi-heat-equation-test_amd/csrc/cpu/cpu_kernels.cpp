@@ -79,7 +79,25 @@ bool host_has_fma() {
 }
 
 template <typename T>
-void tb_impl(const T* src, T* dst, const SlabLayout& L, int64_t rb, int64_t re, int k, T r, int arith) {
+void wrap_cols_impl(T* f, const SlabLayout& L, int64_t r0, int64_t r1) {
+  for (int64_t i = r0; i < r1; ++i) {
+    T* row = f + L.offset(i, 0);
+    for (int64_t j = 0; j < kern::kWrapCols; ++j) {
+      row[-1 - j] = row[L.ncols - 1 - j];
+      row[L.ncols + j] = row[j];
+    }
+  }
+}
+
+// bc (kernels.hpp kBcPeriodicX / kBcPeriodicY), as the device march: periodic
+// x pins no row, periodic y pins no column — level s is computed over the
+// ghost columns [-(k - s), ncols + (k - s)) too, from level-0 wrap images k
+// columns deep, and the ghost columns of the rows written are refreshed.
+template <typename T>
+void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re, int k, T r, int arith, int bc) {
+  const SlabLayout L = kern::bc_layout(L0, bc & kern::kBcPeriodicX);  // (the columns: free_cols below)
+  const bool free_cols = (bc & kern::kBcPeriodicY) != 0;
+  if (free_cols) HEAT2D_REQUIRE(L.ncols >= kern::kWrapCols, "periodic y needs at least kWrapCols (24) owned columns");
   const int64_t R = re - rb + 2 * k;  // level-0 rows [rb-k, re+k)
   const int64_t P = L.pitch;
   std::vector<T> A((size_t)(R * P)), B((size_t)(R * P));
@@ -96,21 +114,23 @@ void tb_impl(const T* src, T* dst, const SlabLayout& L, int64_t rb, int64_t re, 
     parallel_rows(s, R - s, [&](int64_t lb, int64_t le) {
       for (int64_t li = lb; li < le; ++li) {
         const int64_t row = rb - k + li;  // local slab row
-        const T* up = a + (li - 1) * P + c;
-        const T* mid = a + li * P + c;
-        const T* dn = a + (li + 1) * P + c;
-        T* out = b + li * P + c;
+        const int64_t g = free_cols ? k - s : 0;  // ghost columns this level still needs
+        const T* up = a + (li - 1) * P + c - g;
+        const T* mid = a + li * P + c - g;
+        const T* dn = a + (li + 1) * P + c - g;
+        T* out = b + li * P + c - g;
         if (row < fixed_lo || row >= fixed_hi) {
-          std::memcpy(out, mid, sizeof(T) * (size_t)L.ncols);
+          std::memcpy(out, mid, sizeof(T) * (size_t)(L.ncols + 2 * g));
           continue;
         }
-        row_update(up, mid, dn, out, L.ncols, r);
+        row_update(up, mid, dn, out, L.ncols + 2 * g, r);
       }
     }, L.ncols);
     std::swap(a, b);
   }
   for (int64_t i = rb; i < re; ++i)
     std::memcpy(dst + L.offset(i, 0), a + (i - rb + k) * P + c, sizeof(T) * (size_t)L.ncols);
+  if (free_cols) wrap_cols_impl(dst, L, rb, re);
 }
 
 template <typename T>
@@ -189,7 +209,7 @@ int num_threads() {
 }
 
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end,
-        int k, double r, int arith) {
+        int k, double r, int arith, int bc) {
   HEAT2D_REQUIRE(k >= 1 && k <= L.halo, "k out of range");
   HEAT2D_REQUIRE(arith >= 0 && arith <= 3, "arith must be 0, 1, 2 or 3");
   HEAT2D_REQUIRE(arith != 2 || r == 0.25, "arith 2 (jacobi) needs r == 1/4 exactly");
@@ -199,9 +219,9 @@ void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_b
   if (arith == 3) arith = 1;
   if (row_end <= row_begin) return;
   if (dt == DType::F32)
-    tb_impl<float>(static_cast<const float*>(src), static_cast<float*>(dst), L, row_begin, row_end, k, (float)r, arith);
+    tb_impl<float>(static_cast<const float*>(src), static_cast<float*>(dst), L, row_begin, row_end, k, (float)r, arith, bc);
   else
-    tb_impl<double>(static_cast<const double*>(src), static_cast<double*>(dst), L, row_begin, row_end, k, r, arith);
+    tb_impl<double>(static_cast<const double*>(src), static_cast<double*>(dst), L, row_begin, row_end, k, r, arith, bc);
 }
 
 void init(DType dt, void* field, const SlabLayout& L, const kern::IcParams& ic, const double* xc,
@@ -217,6 +237,24 @@ void stats(DType dt, const void* field, const void* other, const SlabLayout& L, 
     stats_impl<float>(static_cast<const float*>(field), static_cast<const float*>(other), L, out);
   else
     stats_impl<double>(static_cast<const double*>(field), static_cast<const double*>(other), L, out);
+}
+
+void wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1) {
+  if (r1 <= r0) return;
+  HEAT2D_REQUIRE(r0 >= -L.halo && r1 <= L.nrows + L.halo, "wrap_cols: rows outside the allocation");
+  HEAT2D_REQUIRE(L.ncols >= kern::kWrapCols, "periodic y needs at least kWrapCols (24) owned columns");
+  if (dt == DType::F32) wrap_cols_impl<float>(static_cast<float*>(field), L, r0, r1);
+  else wrap_cols_impl<double>(static_cast<double*>(field), L, r0, r1);
+}
+
+void wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k) {
+  if (k <= 0) return;
+  HEAT2D_REQUIRE(k <= L.halo && k <= L.nrows, "wrap_rows: depth exceeds the halo or the owned rows");
+  const size_t es = dtype_size(dt), bytes = (size_t)(k * L.pitch) * es;
+  char* base = static_cast<char*>(field);
+  auto row = [&](int64_t i) { return base + (size_t)((i + L.halo) * L.pitch) * es; };
+  std::memcpy(row(-k), row(L.nrows - k), bytes);
+  std::memcpy(row(L.nrows), row(0), bytes);
 }
 
 void pack_rows(DType dt, const void* field, const SlabLayout& L, int64_t row, int64_t nrows, void* buf) {

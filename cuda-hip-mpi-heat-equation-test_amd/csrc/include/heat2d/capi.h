@@ -35,6 +35,7 @@ typedef struct heat2d_config {
   int32_t engine, arith; /* arith: 0 reference rounding, 1 contracted fma, 2 jacobi (r = 1/4) */
   int32_t edge_shift; /* rows each edge slab gives the middle ones (common.hpp decompose) */
   int64_t slab_row0, slab_rows_global; /* 1-rank rehearsal of a middle slab (0: the slab is the grid) */
+  int32_t bc_x, bc_y; /* boundary condition of the row / column axis: 0 dirichlet, 1 periodic */
 } heat2d_config;
 
 typedef struct heat2d_tb_plan {
@@ -93,6 +94,16 @@ int heat2d_parse_input(const char* text, double* out7);
  * `stream` is a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream). */
 int heat2d_tb(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb,
               int64_t re, int k, double r, void* stream, int64_t tile_rows, int arith);
+/* heat2d_tb with boundary conditions: bc = 1 (periodic x: no row pinned) | 2 (periodic y: no
+ * column pinned, ghost columns of the rows written refreshed behind the launch) */
+int heat2d_tb_bc(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb,
+                 int64_t re, int k, double r, void* stream, int64_t tile_rows, int arith, int bc);
+/* Periodic wrap fills. wrap_cols: 24 ghost columns on each side of rows [r0, r1) from the owned
+ * columns; wrap_rows: whole padded rows [nrows-k, nrows) -> [-k, 0), [0, k) -> [nrows, nrows+k).
+ * on_device = 0: host memory (the CPU twins; stream ignored). */
+int heat2d_wrap_cols(int dtype, void* field, const heat2d_layout* L, int64_t r0, int64_t r1, void* stream,
+                     int on_device);
+int heat2d_wrap_rows(int dtype, void* field, const heat2d_layout* L, int64_t k, void* stream, int on_device);
 int heat2d_init_field(int dtype, void* field, const heat2d_layout* L, const heat2d_ic* ic,
                       const double* xcoord_dev, const double* ycoord_dev, void* stream);
 int heat2d_stats(int dtype, const void* field, const void* other, const heat2d_layout* L,
@@ -107,6 +118,8 @@ int heat2d_unpack_rows(int dtype, void* field, const heat2d_layout* L, int64_t r
 
 int heat2d_cpu_tb(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb,
                   int64_t re, int k, double r, int arith);
+int heat2d_cpu_tb_bc(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb,
+                     int64_t re, int k, double r, int arith, int bc);
 int heat2d_cpu_init_field(int dtype, void* field, const heat2d_layout* L, const heat2d_ic* ic,
                           const double* xcoord, const double* ycoord);
 int heat2d_cpu_stats(int dtype, const void* field, const void* other, const heat2d_layout* L,
@@ -151,6 +164,11 @@ int heat2d_solver_pref_depth(void* s, int32_t* out);
 int heat2d_solver_sync(void* s);
 int heat2d_solver_stats(void* s, double* out6, int residual);
 int heat2d_solver_download(void* s, void* host, int64_t ld);
+/* the frame-inclusive local field, (nrows + 2) x (ncols + 2): owned points and the frame lines of
+   Dirichlet axes (entries on periodic axes are ignored and become wrap images), then a halo exchange */
+int heat2d_solver_upload_field(void* s, const void* host, int64_t ld);
+/* any rectangle of the current field, local rows [r0, r1) x columns [c0, c1), ghost / frame included */
+int heat2d_solver_download_region(void* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, void* host, int64_t ld);
 // memory-fit planner (runtime.hpp solver_footprint / plan_max_grid): out3 =
 // {field bytes, workspace bytes, total} of a Solver of cfg on rank of nranks
 int heat2d_solver_footprint(const heat2d_config* cfg, int rank, int nranks, int64_t* out3);
@@ -182,6 +200,8 @@ int heat2d_solver_info(void* s, int32_t* tb, int64_t* band, int64_t* steps, void
                        void** stream);
 /* the arithmetic form the solver runs (0 .. 3): cfg.arith with -1 (auto) resolved */
 int heat2d_solver_arith(void* s, int32_t* out);
+/* boundary conditions the solver runs: 0 dirichlet, 1 periodic, per axis */
+int heat2d_solver_bc(void* s, int32_t* bc_x, int32_t* bc_y);
 
 /* Loopback group: P slabs on one device (or host). */
 int heat2d_group_create(const heat2d_config* cfg, int nranks, void** out);
@@ -189,6 +209,8 @@ int heat2d_group_free(void* g);
 int heat2d_group_init(void* g, const heat2d_ic* ic, const double* xg, const double* yg);
 int heat2d_group_step(void* g, int64_t n);
 int heat2d_group_download(void* g, void* host, int64_t ld);
+/* the whole frame-inclusive field (n + 2)^2 to the members' slabs (heat2d_solver_upload_field each) */
+int heat2d_group_upload_field(void* g, const void* host, int64_t ld);
 /* whole global owned region -> the members' slabs, then a loopback halo exchange */
 int heat2d_group_upload(void* g, const void* host, int64_t ld);
 /* member i's solver (borrowed handle: valid while the group lives; plan / info / hist queries) */

@@ -37,17 +37,62 @@ struct TbPlan {
 TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end, int k,
                int64_t tile_rows = 0, int cus = 0, int arith = 0);
 
+// Boundary conditions (SolverConfig::bc_x / bc_y as one bit set): every stencil
+// launcher below takes it after arith. 0 = the Dirichlet frame on both axes.
+//   kBcPeriodicX: no row is pinned — the slab is marched as a middle slab
+//     whatever its place in the grid (bc_layout); its ghost rows are wrap
+//     images, kept by the halo exchange (one rank: launch_wrap_rows).
+//   kBcPeriodicY: no owned or ghost column is pinned — the kWrapCols ghost
+//     columns on each side are wrap images of the owned columns, and every
+//     launcher refreshes them over the rows it wrote (launch_wrap_cols, same
+//     stream, right behind its stencil launch). The march itself is the
+//     Dirichlet one, unchanged, on a grid widened by the ghost columns
+//     (bc_layout): its "frame" columns are the pad columns beyond them. It
+//     stores meaningless values into the ghost columns of the rows it writes
+//     (level K there is cut off from its wrap neighbours; the straddling lane
+//     adds up to V - 1 pad columns), which the fill overwrites: kWrapCols must
+//     be >= the depth of any pass (kMaxTB) and >= V (4).
+constexpr int kBcPeriodicX = 1, kBcPeriodicY = 2;
+// ghost columns per side kept as wrap images: the deepest pass (kMaxTB) reads that many
+constexpr int64_t kWrapCols = kMaxTB;
+static_assert(kWrapCols <= kColPad && kWrapCols >= 4, "ghost columns must fit the column padding");
+// The layout the planners and kernels see. Periodic x: the global frame rows
+// are moved out of reach of every march (row0 and nrows_global shifted by
+// kBcRowShift), so each slab plans and runs as a middle slab: no edge kind 1 /
+// 3 item, boundary bands on the interior kernel. Periodic y: column 0 of the
+// widened grid is ghost column -kWrapCols, and it has ncols + 2 kWrapCols
+// "owned" columns (same pitch, same memory): a garbage value entering from a
+// pinned pad column moves one column per level, so after K <= kWrapCols levels
+// it has not reached the real owned columns. Dirichlet: L itself.
+constexpr int64_t kBcRowShift = int64_t(1) << 24;
+inline SlabLayout bc_layout(SlabLayout L, int bc) {
+  if (bc & kBcPeriodicX) {
+    L.row0 += kBcRowShift;
+    L.nrows_global += 2 * kBcRowShift;
+  }
+  if (bc & kBcPeriodicY) {
+    L.cpad -= kWrapCols;
+    L.ncols += 2 * kWrapCols;
+  }
+  return L;
+}
+// Ghost-column fill of rows [r0, r1) (ghost / frame rows allowed) and the
+// k-row self wrap of whole padded rows: rows [nrows-k, nrows) -> [-k, 0),
+// [0, k) -> [nrows, nrows+k) (periodic x on one rank).
+void launch_wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1, hipStream_t stream);
+void launch_wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k, hipStream_t stream);
+
 // dst(rows [row_begin,row_end)) = k FTCS steps of src. `src`/`dst` are
 // allocation bases laid out per `L`. Requires k <= L.halo and the k ghost rows
 // on both sides of the range to hold valid data at time t (Dirichlet rows are
 // recognised from L.row0 / L.nrows_global and kept fixed).
 void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
                int64_t row_end, int k, double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0,
-               int arith = 0);
+               int arith = 0, int bc = 0);
 // Same for TWO disjoint row ranges [rb0, re0) and [rb1, re1) in one launch.
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
                 int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0,
-                int arith = 0);
+                int arith = 0, int bc = 0);
 
 // Split schedule of one cycle (k steps over the whole slab) into two launches
 // on two streams:
@@ -108,10 +153,10 @@ bool edges_on_main(const SlabLayout& L, const SplitPlan& p);
 // stays clear of the global frame rows, else the general one (edge ranks).
 bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i);
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
-                      hipStream_t stream, int arith = 0);
+                      hipStream_t stream, int arith = 0, int bc = 0);
 // queue: 2 device counters (zeroed once) for plans with flags & kPlanDynamic (dynamic items)
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
-                  double r, hipStream_t stream, int arith = 0, uint32_t* queue = nullptr);
+                  double r, hipStream_t stream, int arith = 0, uint32_t* queue = nullptr, int bc = 0);
 
 // Initial / boundary condition kinds (covers every IC of the reference
 // variants, see models/presets.py for the mapping).
@@ -157,8 +202,10 @@ int64_t max_stats_waves();
 // Diagnostics: per-wave {start, end, wave id, 0} (wall clock ticks) of the
 // last tb_kernel launch when HEAT2D_WAVE_TIMES=1; returns the waves copied.
 int64_t wave_times(uint64_t* out, int64_t max_waves);
+// (bc: kBcPeriodicX only — with periodic y the march's widened grid would
+// count ghost columns; the solver takes its unfused statistics path there)
 void launch_tb_stats(DType dt, const void* src, void* dst, const SlabLayout& L, int k, double r, double* partials,
-                     double* out6, hipStream_t stream, int arith = 0);
+                     double* out6, hipStream_t stream, int arith = 0, int bc = 0);
 void launch_reduce_partials(const double* partials, int64_t nparts, double* out6, hipStream_t stream);
 
 // Field comparison (the bench's check of its timed field against an

@@ -55,7 +55,16 @@ struct SolverConfig {
   // so its bands are interior bands, as on rank 3 of 8 (0: the slab is the grid)
   int64_t slab_row0;
   int64_t slab_rows_global;
+  // Boundary condition per axis: 0 Dirichlet (the frame keeps its values),
+  // 1 periodic (the n owned points are the period; frame entries are wrap
+  // images). x is the row axis (decomposed over ranks), y the column axis.
+  int32_t bc_x;
+  int32_t bc_y;
 };
+// the kernels' bit set (kernels.hpp kBcPeriodicX / kBcPeriodicY) of a config
+inline int config_bc(const SolverConfig& c) {
+  return (c.bc_x ? kern::kBcPeriodicX : 0) | (c.bc_y ? kern::kBcPeriodicY : 0);
+}
 
 // ---------------------------------------------------------------- transports
 
@@ -84,6 +93,14 @@ class Transport {
   virtual void graph_launched(hipStream_t /*stream*/) {}
   // true if exchange() moves data (size > 1, or a 1-rank periodic rehearsal)
   virtual bool exchanges() const { return size() > 1; }
+  // Periodic x (SolverConfig::bc_x): rank 0's lower neighbour is rank
+  // size - 1 and the reverse; on one rank the exchange wraps the slab onto
+  // itself. Returns false if the transport cannot do that (the solver then
+  // refuses the configuration, or on one rank takes the self transport).
+  virtual bool set_periodic_x(bool on) { return !on; }
+  // exchange() moves whole padded rows (ghost columns travel with them);
+  // false: the owned columns only (packed host staging)
+  virtual bool whole_rows() const { return true; }
   // Failure detection: raise if the fabric reported an asynchronous error
   // (RCCL: ncclCommGetAsyncError). Polled at every synchronisation point.
   virtual void check() {}
@@ -137,21 +154,37 @@ struct IoPhase {
 //   to / from rank-1: send rows [0, k),          receive into [-k, 0)
 //   to / from rank+1: send rows [nrows-k, nrows), receive into [nrows, nrows+k)
 // (the reference's two MPI_Sendrecv per step, fortran/hip/heat.F90:212-213)
+// wrap (periodic x, size > 1): rank 0's lower neighbour is rank size - 1 and
+// the reverse; on 2 ranks both messages go to the same peer, told apart by
+// their direction (a lower message pairs with the peer's upper one).
 struct HaloMsg {
   int peer;
   int64_t send_row, recv_row;
+  bool lower() const { return recv_row < 0; }  // toward rank - 1
 };
-inline int halo_msgs(int rank, int size, const SlabLayout& L, int64_t k, HaloMsg out[2]) {
+inline int halo_msgs(int rank, int size, const SlabLayout& L, int64_t k, HaloMsg out[2], bool wrap = false) {
   int n = 0;
-  if (rank > 0) out[n++] = HaloMsg{rank - 1, 0, -k};
-  if (rank < size - 1) out[n++] = HaloMsg{rank + 1, L.nrows - k, L.nrows};
+  wrap = wrap && size > 1;
+  if (rank > 0 || wrap) out[n++] = HaloMsg{rank > 0 ? rank - 1 : size - 1, 0, -k};
+  if (rank < size - 1 || wrap) out[n++] = HaloMsg{rank < size - 1 ? rank + 1 : 0, L.nrows - k, L.nrows};
   return n;
+}
+// The row `peer` sends toward `rank` for rank's message m (peer's layout PL): -1 if none.
+inline int64_t halo_peer_send_row(int rank, int size, const HaloMsg& m, const SlabLayout& PL, int64_t k, bool wrap) {
+  HaloMsg pm[2];
+  const int np = halo_msgs(m.peer, size, PL, k, pm, wrap);
+  for (int j = 0; j < np; ++j)
+    if (pm[j].peer == rank && pm[j].lower() != m.lower()) return pm[j].send_row;
+  return -1;
 }
 inline size_t halo_row_bytes(const SlabLayout& L, int64_t row, size_t es) {
   return (size_t)((row + L.halo) * L.pitch) * es;
 }
 inline size_t halo_msg_bytes(const SlabLayout& L, int64_t k, size_t es) { return (size_t)(k * L.pitch) * es; }
 
+// One rank. With set_periodic_x(true) its exchange wraps the slab onto itself
+// (kern::launch_wrap_rows on the given stream, capturable; host fields:
+// cpu::wrap_rows), so the solver runs its exchanging cycle.
 std::shared_ptr<Transport> make_self_transport();
 // P ranks of one process (one device, or host memory): halos move by
 // device-to-device copies on the receiving rank's exchange stream, ordered by
@@ -208,7 +241,9 @@ std::shared_ptr<Transport> make_ipc_loop_transport(int device);
 
 namespace cpu {
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
-        int64_t row_end, int k, double r, int arith = 0);
+        int64_t row_end, int k, double r, int arith = 0, int bc = 0);
+void wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1);
+void wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k);
 void init(DType dt, void* field, const SlabLayout& L, const kern::IcParams& ic,
           const double* xcoord, const double* ycoord);
 void stats(DType dt, const void* field, const void* other, const SlabLayout& L, double out[6]);
@@ -369,6 +404,10 @@ class Solver {
   // Halo rows each cycle exchanged since the last reset (sum over cycles).
   int64_t halo_rows_exchanged(bool reset);
   void upload_owned(const void* host, int64_t ld);  // upload() without the halo exchange
+  // the frame-inclusive local field (nrows + 2) x (ncols + 2), Dirichlet frame
+  // lines included (both buffers); no halo exchange (exchange_post / exchange_now follow)
+  void upload_framed(const void* host, int64_t ld);
+  void upload_field(const void* host, int64_t ld);  // upload_framed, then the halo exchange (collective, as upload)
   // Cycles launched by step() since the last reset, by depth: hist[k] for
   // k = 0..kMaxTB (graph replays count their two cycles each).
   void cycle_hist(int64_t out[kMaxTB + 1], bool reset);
@@ -456,6 +495,9 @@ class Solver {
   SolverConfig cfg_;
   std::shared_ptr<Transport> tr_;
   SlabLayout L_{};
+  SlabLayout Lk_{};  // kern::bc_layout(L_, bc_): what the planners see (periodic x: a middle slab)
+  int bc_ = 0;       // config_bc(cfg_)
+  void wrap_cols_all(void* field);  // periodic y: ghost columns of every allocated row (init, upload, restart)
   bool hip_ = true;
   void* buf_[2] = {nullptr, nullptr};
   int cur_ = 0;
@@ -530,13 +572,15 @@ class Solver {
 // GPU and must be bitwise identical to P = 1.
 class LoopbackGroup {
  public:
-  LoopbackGroup(const SolverConfig& cfg, int nranks);
+  LoopbackGroup(const SolverConfig& cfg, int nranks);  // (cfg.bc_x / bc_y: periodic boundaries, as Solver)
   ~LoopbackGroup();
   void init(const kern::IcParams& ic, const double* xg, const double* yg);
   void step(int64_t n);
   void synchronize();
   void download(void* host, int64_t ld);  // whole global owned region
   void upload(const void* host, int64_t ld);  // whole global owned region, then a halo exchange
+  // the whole frame-inclusive field (n + 2) x (n_cols + 2) (Solver::upload_framed per member), then a halo exchange
+  void upload_field(const void* host, int64_t ld);
   int nranks() const { return (int)members_.size(); }
   Solver& member(int i) { return *members_[i]; }
 

@@ -262,6 +262,36 @@ __global__ __launch_bounds__(256) void read16_kernel(const uint4* __restrict__ s
   if (acc == 0x9e3779b9u) sink[0] = acc;  // keep the loads alive
 }
 
+// Periodic y: the kWrapCols ghost columns on each side of rows [r0, r1) as
+// wrap images of the owned columns — column -1-j <- ncols-1-j, column ncols+j
+// <- j. One thread per (row, ghost column); the sources are owned columns
+// (host check: ncols >= kWrapCols), so no thread reads what another writes.
+template <typename T>
+__global__ __launch_bounds__(256) void wrap_cols_kernel(T* __restrict__ f, SlabLayout L, int64_t r0, int64_t r1) {
+  constexpr int64_t G = kWrapCols;
+  const int64_t total = (r1 - r0) * 2 * G;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t i = t / (2 * G), q = t - i * (2 * G);
+    T* row = f + L.offset(r0 + i, 0);
+    if (q < G) row[-1 - q] = row[L.ncols - 1 - q];
+    else row[L.ncols + (q - G)] = row[q - G];
+  }
+}
+
+// Periodic x on one rank: whole padded rows [nrows-k, nrows) -> [-k, 0) and
+// [0, k) -> [nrows, nrows+k), 16 B per lane (n16 vectors per block of k rows;
+// k <= nrows: sources and destinations are disjoint).
+__global__ __launch_bounds__(256) void wrap_rows_kernel(uint4* __restrict__ lo_dst, const uint4* __restrict__ lo_src,
+                                                        uint4* __restrict__ hi_dst, const uint4* __restrict__ hi_src,
+                                                        int64_t n16) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * n16; i += stride) {
+    if (i < n16) lo_dst[i] = lo_src[i];
+    else hi_dst[i - n16] = hi_src[i - n16];
+  }
+}
+
 inline unsigned grid_for(int64_t n) {
   int64_t b = (n + 255) / 256;
   if (b > 8192) b = 8192;  // grid-stride beyond 8 blocks per CU
@@ -361,6 +391,32 @@ void launch_unpack_rows(DType dt, void* field, const SlabLayout& L, int64_t row,
   else
     hipLaunchKernelGGL(unpack_rows_kernel<double>, dim3(g), dim3(256), 0, stream, static_cast<double*>(field), L, row, nrows, static_cast<const double*>(buf));
   check_launch("unpack_rows");
+}
+
+void launch_wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1, hipStream_t stream) {
+  if (r1 <= r0) return;
+  HEAT2D_REQUIRE(r0 >= -L.halo && r1 <= L.nrows + L.halo, "wrap_cols: rows outside the allocation");
+  HEAT2D_REQUIRE(L.ncols >= kWrapCols, "periodic y needs at least kWrapCols (24) owned columns");
+  HEAT2D_REQUIRE(L.cpad >= kWrapCols && L.col_hi() - L.ncols >= kWrapCols, "wrap_cols: column padding too small");
+  const unsigned g = grid_for((r1 - r0) * 2 * kWrapCols);
+  if (dt == DType::F32)
+    hipLaunchKernelGGL(wrap_cols_kernel<float>, dim3(g), dim3(256), 0, stream, static_cast<float*>(field), L, r0, r1);
+  else
+    hipLaunchKernelGGL(wrap_cols_kernel<double>, dim3(g), dim3(256), 0, stream, static_cast<double*>(field), L, r0, r1);
+  check_launch("wrap_cols");
+}
+
+void launch_wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k, hipStream_t stream) {
+  if (k <= 0) return;
+  HEAT2D_REQUIRE(k <= L.halo && k <= L.nrows, "wrap_rows: depth exceeds the halo or the owned rows");
+  const size_t es = dtype_size(dt);
+  HEAT2D_REQUIRE((L.pitch * es) % 16 == 0, "wrap_rows: rows must be whole 16-byte vectors");
+  char* base = static_cast<char*>(field);
+  auto row = [&](int64_t i) { return reinterpret_cast<uint4*>(base + (size_t)((i + L.halo) * L.pitch) * es); };
+  const int64_t n16 = (int64_t)((size_t)(k * L.pitch) * es / 16);
+  hipLaunchKernelGGL(wrap_rows_kernel, dim3(grid_for(2 * n16)), dim3(256), 0, stream, row(-k), row(L.nrows - k),
+                     row(L.nrows), row(0), n16);
+  check_launch("wrap_rows");
 }
 
 }  // namespace kern

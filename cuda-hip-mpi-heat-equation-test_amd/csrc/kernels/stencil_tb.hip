@@ -162,7 +162,9 @@ void dispatch_t(int ring, bool main, int arith, int k, unsigned nblocks, const T
 void check_layout(DType dt, const SlabLayout& L, int k) {
   HEAT2D_REQUIRE(k >= 1 && k <= max_tb(dt), "k must be in [1, max_tb(dtype)] (24)");
   HEAT2D_REQUIRE(k <= L.halo, "temporal depth exceeds the halo depth");
-  HEAT2D_REQUIRE(L.cpad >= (k + 1) / 2 * 2 + 4, "column padding too small for the strip halo");
+  // (a periodic-y widened layout, bc_layout: its left pad is what lies beyond the ghost columns)
+  HEAT2D_REQUIRE(L.cpad >= (k + 1) / 2 * 2 + 4 || L.cpad == kColPad - kWrapCols,
+                 "column padding too small for the strip halo");
   // the march keeps row indices in 32 bits (scalar compares)
   HEAT2D_REQUIRE(L.nrows_global + 2 * L.halo < (int64_t(1) << 31) && L.row0 < (int64_t(1) << 31),
                  "row count exceeds the 32-bit row index of the stencil kernel");
@@ -239,10 +241,22 @@ int64_t choose_bands(int64_t rows, int64_t ns, int64_t simds, int k, int64_t pri
 
 // Launch `rects` (item counts from their nb and strip ranges) on `nwaves` waves.
 // partials != nullptr: the fused-statistics kernel (general, ring 4). Returns the waves launched.
-int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L, int k, int ring, bool main,
+// bc: kernels.hpp kBcPeriodicX / kBcPeriodicY; L is the slab's own layout (the
+// kernels see bc_layout(L, bc)). Periodic y: the ghost columns of the rows
+// written are refreshed right behind the stencil launch, on the same stream,
+// so whatever orders a consumer after this launch orders it after the fill.
+int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
                      const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
-                     double* partials = nullptr, uint32_t* queue = nullptr) {
+                     double* partials = nullptr, uint32_t* queue = nullptr, int bc = 0) {
   HEAT2D_REQUIRE(nrect >= 1 && nrect <= (main ? kMainRects : kMaxRects), "bad rect count");
+  HEAT2D_REQUIRE((bc & ~(kBcPeriodicX | kBcPeriodicY)) == 0, "bc must be a set of kBcPeriodicX | kBcPeriodicY");
+  const SlabLayout L = bc_layout(L0, bc);
+  check_layout(dt, L, k);  // (the shifted rows must still fit the march's 32-bit row index)
+  if (bc & kBcPeriodicY) {
+    HEAT2D_REQUIRE(L0.ncols >= kWrapCols, "periodic y needs at least kWrapCols (24) owned columns");
+    HEAT2D_REQUIRE(L0.cpad == kColPad && L0.col_hi() - L0.ncols >= kColPad, "periodic y needs make_layout's padding");
+    HEAT2D_REQUIRE(!partials, "the fused-statistics kernel has no periodic y");
+  }
   TbArgs a{};
   a.pitch = L.pitch;
   a.ncols = L.ncols;
@@ -299,6 +313,31 @@ int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L, 
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) fail(__FILE__, __LINE__, std::string("tb_kernel launch: ") + hipGetErrorString(e));
+  if (bc & kBcPeriodicY) {
+    // one fill per run of rows the rects cover (rects of one launch share rows
+    // strip by strip, or are disjoint bands): never a row another launch writes
+    int64_t lo[kMaxRects], hi[kMaxRects];
+    int n = 0;
+    for (int i = 0; i < a.nrect; ++i) {
+      int64_t b = a.rect[i].r0, t = a.rect[i].r1;
+      for (int j = 0; j < n;) {  // absorb every run [lo, hi) that touches [b, t)
+        if (lo[j] <= t && b <= hi[j]) {
+          b = std::min(b, lo[j]);
+          t = std::max(t, hi[j]);
+          lo[j] = lo[n - 1];
+          hi[j] = hi[n - 1];
+          --n;
+          j = 0;
+        } else {
+          ++j;
+        }
+      }
+      lo[n] = b;
+      hi[n] = t;
+      ++n;
+    }
+    for (int j = 0; j < n; ++j) launch_wrap_cols(dt, dst, L0, lo[j], hi[j], stream);
+  }
   return a.nwaves;
 }
 
@@ -345,17 +384,18 @@ TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end
 }
 
 void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end, int k,
-               double r, hipStream_t stream, int64_t tile_rows, int cus, int arith) {
-  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith);
+               double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc) {
+  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith, bc);
 }
 
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
-                int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows, int cus, int arith) {
+                int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc) {
   check_layout(dt, L, k);
   const int64_t n0 = std::max<int64_t>(0, re0 - rb0), n1 = std::max<int64_t>(0, re1 - rb1);
   if (n0 + n1 == 0) return;
   // plan over the concatenated rows, then give each range its share of bands
-  const TbPlan p = plan_tb(dt, L, 0, std::min<int64_t>(n0 + n1, L.nrows), k, tile_rows, cus, arith);
+  // (strips of the grid the kernels see)
+  const TbPlan p = plan_tb(dt, bc_layout(L, bc), 0, std::min<int64_t>(n0 + n1, L.nrows), k, tile_rows, cus, arith);
   TbRect rects[2];
   int nr = 0;
   if (p.ntiles < 0) {  // segments, shared out over the two ranges by rows
@@ -363,7 +403,7 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
     const int64_t s0 = n1 == 0 ? ns : (n0 == 0 ? 0 : std::max<int64_t>(1, (ns * n0 + (n0 + n1) / 2) / (n0 + n1)));
     if (n0 > 0) rects[nr++] = TbRect{rb0, re0, 0, p.nstrips, -std::min<int64_t>(s0, n0 * p.nstrips)};
     if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, -std::min<int64_t>(std::max<int64_t>(1, ns - s0), n1 * p.nstrips)};
-    launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, p.nwaves, r, stream, arith);
+    launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, p.nwaves, r, stream, arith, nullptr, nullptr, bc);
     return;
   }
   const int64_t nb = std::max<int64_t>(p.ntiles, (n0 > 0) + (n1 > 0));
@@ -371,7 +411,7 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
   if (n0 > 0) rects[nr++] = TbRect{rb0, re0, 0, p.nstrips, std::min<int64_t>(nb0, n0)};
   if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, std::min<int64_t>(nb - nb0, n1)};
   const int64_t slots = (int64_t)(cus > 0 ? cus : cu_count()) * p.blocks_per_cu * 4;
-  launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, slots, r, stream, arith);
+  launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, slots, r, stream, arith, nullptr, nullptr, bc);
 }
 
 // r = 1/4 kernels (arith 2): an interior item costs 3 adds + 2 DPP moves per
@@ -585,7 +625,7 @@ int64_t wave_times(uint64_t* out, int64_t max_waves) {
 int64_t max_stats_waves() { return (int64_t)cu_count() * 32; }  // 8 x 256-thread blocks per CU
 
 void launch_tb_stats(DType dt, const void* src, void* dst, const SlabLayout& L, int k, double r, double* partials,
-                     double* out6, hipStream_t stream, int arith) {
+                     double* out6, hipStream_t stream, int arith, int bc) {
   check_layout(dt, L, k);
   HEAT2D_REQUIRE(partials && out6, "statistics buffers required");
   const int64_t U = useful_width(dt, k);
@@ -594,7 +634,7 @@ void launch_tb_stats(DType dt, const void* src, void* dst, const SlabLayout& L, 
   const int64_t nb = std::max<int64_t>(
       1, std::min<int64_t>(choose_bands(L.nrows, ns, balance_units(dt, 0, occupancy_stats(dt, k, arith)), k), L.nrows));
   const TbRect rect{0, L.nrows, 0, ns, nb};
-  const int64_t nw = launch_rects(dt, src, dst, L, k, 4, false, &rect, 1, slots, r, stream, arith, partials);
+  const int64_t nw = launch_rects(dt, src, dst, L, k, 4, false, &rect, 1, slots, r, stream, arith, partials, nullptr, bc);
   launch_reduce_partials(partials, nw, out6, stream);
 }
 
@@ -619,17 +659,18 @@ bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i) {
 }
 
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
-                      hipStream_t stream, int arith) {
+                      hipStream_t stream, int arith, int bc) {
   HEAT2D_REQUIRE(i >= 0 && i < p.nedge, "edge rect index");
   const TbRect& R = p.edge[i];
-  const bool on_main = edges_on_main(L, p.k, &R, 1);
+  const bool on_main = edges_on_main(bc_layout(L, bc), p.k, &R, 1);
   const int64_t items = R.nb > 0 ? R.nb * (R.s1 - R.s0) : -R.nb;
   const int64_t slots = (int64_t)cu_count() * occupancy(dt, p.ring, on_main, p.k, arith) * 4;
-  launch_rects(dt, src, dst, L, p.k, p.ring, on_main, &R, 1, std::min<int64_t>(items, slots), r, stream, arith);
+  launch_rects(dt, src, dst, L, p.k, p.ring, on_main, &R, 1, std::min<int64_t>(items, slots), r, stream, arith,
+               nullptr, nullptr, bc);
 }
 
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
-                  double r, hipStream_t stream, int arith, uint32_t* queue) {
+                  double r, hipStream_t stream, int arith, uint32_t* queue, int bc) {
   // (SplitPlan::flags & kPlanDynamic: the main part takes its items from the dynamic queue)
   uint32_t* q = (p.flags & kPlanDynamic) ? queue : nullptr;
   HEAT2D_REQUIRE(p.valid, "invalid split plan");
@@ -638,14 +679,14 @@ void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, con
   const int nm = p.nrects > 0 ? p.nrects : 1;
   if (p.valid == 2) {  // single general launch over the whole slab (no edge part)
     if (main_part)
-      launch_rects(dt, src, dst, L, p.k, p.ring, false, mr, nm, p.main_waves, r, stream, arith, nullptr, q);
+      launch_rects(dt, src, dst, L, p.k, p.ring, false, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc);
     return;
   }
   if (main_part)
-    launch_rects(dt, src, dst, L, p.k, p.ring, true, mr, nm, p.main_waves, r, stream, arith, nullptr, q);
+    launch_rects(dt, src, dst, L, p.k, p.ring, true, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc);
   else
-    launch_rects(dt, src, dst, L, p.k, p.ring, edges_on_main(L, p.k, p.edge, p.nedge), p.edge, p.nedge, p.edge_waves,
-                 r, stream, arith);
+    launch_rects(dt, src, dst, L, p.k, p.ring, edges_on_main(bc_layout(L, bc), p.k, p.edge, p.nedge), p.edge, p.nedge,
+                 p.edge_waves, r, stream, arith, nullptr, nullptr, bc);
 }
 
 }  // namespace kern

@@ -224,9 +224,11 @@ void write_meta(const std::string& dir, const std::string& name, const Meta& m) 
                 "{\n \"format\": \"%s\",\n \"step\": %lld,\n \"nranks\": %d,\n \"dtype\": \"%s\",\n"
                 " \"n_owned\": %lld,\n \"n_input\": %lld,\n \"convention\": \"%s\",\n \"sigma\": %.17g,\n"
                 " \"nu\": %.17g,\n \"dom_len\": %.17g,\n \"r\": %.17g,\n \"edge_shift\": %lld,\n"
+                " \"bc_x\": \"%s\",\n \"bc_y\": \"%s\",\n"
                 " \"writer\": \"heat2d-cli\"\n}\n",
                 kFormat, (long long)m.step, m.nranks, m.dtype == 0 ? "fp32" : "fp64", (long long)m.n_owned,
-                (long long)m.n_input, m.convention.c_str(), m.sigma, m.nu, m.dom_len, m.r, (long long)m.edge_shift);
+                (long long)m.n_input, m.convention.c_str(), m.sigma, m.nu, m.dom_len, m.r, (long long)m.edge_shift,
+                m.bc_x.c_str(), m.bc_y.c_str());
   write_atomic(join(join(dir, name), "meta.json"), buf);  // + fsync of the step directory (rank files' entries)
   write_atomic(join(dir, "latest"), name + "\n");  // the commit point
   // prune: keep the two newest complete saves, ordered by (step, generation)
@@ -279,6 +281,10 @@ Meta read_meta(const std::string& dir) {
   m.dom_len = std::atof(json_value(js, "dom_len").c_str());
   m.r = std::atof(json_value(js, "r").c_str());
   if (js.find("\"edge_shift\"") != std::string::npos) m.edge_shift = std::atoll(json_value(js, "edge_shift").c_str());
+  if (js.find("\"bc_x\"") != std::string::npos) m.bc_x = json_value(js, "bc_x");
+  if (js.find("\"bc_y\"") != std::string::npos) m.bc_y = json_value(js, "bc_y");
+  HEAT2D_REQUIRE((m.bc_x == "dirichlet" || m.bc_x == "periodic") && (m.bc_y == "dirichlet" || m.bc_y == "periodic"),
+                 dir + ": meta.json: bc_x / bc_y must be dirichlet or periodic");
   HEAT2D_REQUIRE(m.nranks >= 1 && m.step >= 0 && m.n_owned >= 1, dir + ": inconsistent meta.json");
   return m;
 }

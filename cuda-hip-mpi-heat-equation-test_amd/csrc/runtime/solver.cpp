@@ -66,7 +66,8 @@ SlabLayout solver_layout(const SolverConfig& cfg, int rank, int nranks) {
     HEAT2D_REQUIRE(cfg.slab_row0 >= 0 && cfg.slab_row0 + cfg.n_rows <= cfg.slab_rows_global, "slab outside the grid");
     return make_layout(cfg.n_rows, cfg.n_cols, halo, cfg.slab_row0, cfg.slab_rows_global);
   }
-  const SlabRange sr = decompose(cfg.n_rows, nranks, rank, cfg.edge_shift);
+  // (periodic x: no slab is an edge slab, nothing to shift)
+  const SlabRange sr = decompose(cfg.n_rows, nranks, rank, cfg.bc_x ? 0 : cfg.edge_shift);
   return make_layout(sr.nrows, cfg.n_cols, halo, sr.row0, cfg.n_rows);
 }
 
@@ -135,6 +136,32 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
                  "arith must be 0 (reference rounding), 1 (fma), 2 (jacobi, r = 1/4), 3 (fast) or -1 (auto)");
   HEAT2D_REQUIRE(cfg_.arith != 2 || cfg_.r == 0.25, "arith 2 (jacobi) needs r == 1/4 exactly (sigma = 0.25)");
   HEAT2D_REQUIRE(cfg_.arith != 3 || cfg_.r > 0, "arith 3 (fast) needs r > 0");
+  HEAT2D_REQUIRE((cfg_.bc_x == 0 || cfg_.bc_x == 1) && (cfg_.bc_y == 0 || cfg_.bc_y == 1),
+                 "bc_x / bc_y must be 0 (dirichlet) or 1 (periodic)");
+  bc_ = config_bc(cfg_);
+  if (bc_) {
+    HEAT2D_REQUIRE(cfg_.engine == 0, "periodic boundaries need the temporal-blocked engine (engine \"jit\" is Dirichlet only)");
+    HEAT2D_REQUIRE(!cfg_.copy_swap, "periodic boundaries have no copy-swap mode (Dirichlet only)");
+    HEAT2D_REQUIRE(cfg_.slab_rows_global == 0, "periodic boundaries: no middle-slab rehearsal (slab_rows_global)");
+  }
+  if (cfg_.bc_y)
+    HEAT2D_REQUIRE(cfg_.n_cols >= kern::kWrapCols,
+                   "grid too small for periodic y: " + std::to_string(cfg_.n_cols) + " owned columns, the ghost depth is " +
+                       std::to_string(kern::kWrapCols));
+  if (cfg_.bc_x) {
+    // the wrap images of a slab's ghost rows must come from ONE rank's owned rows
+    const int64_t need = tb_given ? std::min<int64_t>(cfg_.tb, max_tb(dtype())) : 1;
+    HEAT2D_REQUIRE(cfg_.n_rows / P >= need, "grid too small for periodic x: " + std::to_string(cfg_.n_rows / P) +
+                                                " owned rows per rank, the ghost depth (tb) is " + std::to_string(need));
+    cfg_.edge_shift = 0;  // no edge slabs
+    if (!tr_->set_periodic_x(true) || !tr_->exchanges()) {
+      HEAT2D_REQUIRE(P == 1, "the " + tr_->name() + " transport does not pair the first rank with the last: periodic x "
+                                 "on more than one rank runs on the loopback, host-thread and callback (host-staged) "
+                                 "transports");
+      tr_ = make_self_transport();  // one rank: the slab wraps onto itself
+      tr_->set_periodic_x(true);
+    }
+  }
   if (cfg_.engine == 1) {
     HEAT2D_REQUIRE(hip_, "the jit engine runs on the HIP backend");
     HEAT2D_REQUIRE(!cfg_.copy_swap, "the jit engine has no copy-swap mode");
@@ -154,6 +181,7 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
   k_pref_ = tb_given ? K : std::min(K, tb_pref);
   HEAT2D_REQUIRE((cfg_.halo > 0 ? cfg_.halo : kDefaultHalo) >= K, "halo must be >= temporal depth");
   L_ = solver_layout(cfg_, rank, P);
+  Lk_ = kern::bc_layout(L_, bc_);
 
   const size_t bytes = (size_t)L_.elems() * dtype_size(dtype());
   if (hip_) {
@@ -266,26 +294,46 @@ void Solver::init(const kern::IcParams& ic, const double* xg, const double* yg) 
   } else {
     for (int b = 0; b < 2; ++b) cpu::init(dtype(), buf_[b], L_, ic, xg, yg);
   }
+  for (int b = 0; b < 2; ++b) wrap_cols_all(buf_[b]);
   // ghost rows are filled from the global IC directly: no exchange needed
   cur_ = 0;
   steps_ = 0;
-  ghost_ = (int)band_;
+  ghost_ = cfg_.bc_x ? 0 : (int)band_;
   last_x_[0] = last_x_[1] = 0;
   last_k_ = 0;
+  // ... except with periodic x, where they are wrap images: one exchange, as
+  // after upload() (init is collective; a loopback group runs it for its members)
+  if (cfg_.bc_x && tr_->collective()) {
+    exchange_post();
+    exchange_now();
+    synchronize();
+  }
+}
+
+void Solver::wrap_cols_all(void* field) {
+  if (!cfg_.bc_y) return;
+  if (hip_) kern::launch_wrap_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo, s_compute_);
+  else cpu::wrap_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo);
 }
 
 void Solver::launch_tb(const void* src, void* dst, int64_t rb, int64_t re, int k) {
   if (re <= rb) return;
   if (hip_)
-    kern::launch_tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, s_compute_, cfg_.tile_rows, compute_cus_, cfg_.arith);
+    kern::launch_tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, s_compute_, cfg_.tile_rows, compute_cus_, cfg_.arith, bc_);
   else
-    cpu::tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, cfg_.arith);
+    cpu::tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, cfg_.arith, bc_);
 }
 
 void Solver::exchange_on(void* field, int64_t k, hipStream_t s) {
   if (!tr_->exchanges()) return;
   HEAT2D_REQUIRE(k >= 1 && k <= band_, "halo exchange depth outside [1, band]");
   tr_->exchange(field, L_, dtype(), k, s, hip_);
+  if (cfg_.bc_y && !tr_->whole_rows()) {  // the ghost rows arrived without their ghost columns
+    for (int64_t r0 : {-k, L_.nrows}) {
+      if (hip_) kern::launch_wrap_cols(dtype(), field, L_, r0, r0 + k, s);
+      else cpu::wrap_cols(dtype(), field, L_, r0, r0 + k);
+    }
+  }
   halo_rows_ += k;
 }
 
@@ -370,7 +418,7 @@ void Solver::launch_stats_cycle(int k) {
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_comm_, 0));
   kern::launch_tb_stats(dtype(), buf_[cur_], buf_[cur_ ^ 1], L_, k, cfg_.r, d_part_,
-                        d_work_ + kern::stats_work_elems(), s_compute_, cfg_.arith);
+                        d_work_ + kern::stats_work_elems(), s_compute_, cfg_.arith, bc_);
   H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
   H2D_HIP(hipEventRecord(ev_int_, s_compute_));
   if (tr_->exchanges()) tr_->post(buf_[cur_ ^ 1], L_, ev_bnd_);
@@ -394,7 +442,7 @@ void Solver::cycle_finish() {
     if (pe) H2D_HIP(hipEventRecord(pe->ev[5], s_comm_));
     if (pend_frame_ >= 0) {  // the edge rank's frame-side band (launch_overlap), after the exchange
       kern::launch_edge_rect(dtype(), buf_[cur_], dst, L_, split_plan_banded(pend_k_, pend_frame_b_), pend_frame_, cfg_.r,
-                             s_comm_, cfg_.arith);
+                             s_comm_, cfg_.arith, bc_);
       // the next cycle's compute-stream work waits for it (and so for the
       // exchange ahead of it); ev_bnd_, posted to the transport, is left alone
       H2D_HIP(hipEventRecord(ev_frame_, s_comm_));
@@ -486,7 +534,7 @@ const kern::SplitPlan& Solver::split_plan(int k) {
     // room for RCCL's workgroups beside the two stencil launches when exchanging
     const int spare = spare_waves();
     // bands of k rows (split_plan_banded widens them when a deeper exchange follows)
-    p = kern::plan_split(dtype(), L_, k, k, compute_cus_, spare, 0, 0, cfg_.arith);
+    p = kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, 0, 0, cfg_.arith);
     p.k = k;
     ++plans_made_;
     plan_origin_[k] = 0;
@@ -509,7 +557,7 @@ const kern::SplitPlan& Solver::split_plan(int k) {
         p.flags |= kern::kPlanLead;
       }
       if (o == "single" && !tr_->exchanges()) {
-        p = kern::plan_single(dtype(), L_, k, compute_cus_, 0, 0, cfg_.arith);
+        p = kern::plan_single(dtype(), Lk_, k, compute_cus_, 0, 0, cfg_.arith);
         p.k = k;
       }
     }
@@ -522,8 +570,8 @@ const kern::SplitPlan& Solver::split_plan(int k) {
       const int64_t nseg = env_seg ? std::atoll(env_seg) : -std::atoll(env_bands);  // < 0: bands
       if (nseg != 0 && p.valid) {
         const int valid = p.valid, ring = p.ring;
-        p = valid == 2 ? kern::plan_single(dtype(), L_, k, compute_cus_, ring, -nseg, cfg_.arith)
-                       : kern::plan_split(dtype(), L_, k, k, compute_cus_, spare, ring, -nseg, cfg_.arith);
+        p = valid == 2 ? kern::plan_single(dtype(), Lk_, k, compute_cus_, ring, -nseg, cfg_.arith)
+                       : kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, ring, -nseg, cfg_.arith);
         if (p.valid) p.valid = valid;
         p.k = k;
       }
@@ -548,7 +596,7 @@ const kern::SplitPlan& Solver::split_plan_banded(int k, int64_t B) {
   if (it != banded_.end()) return it->second;
   // the same choice (order, ring, interior bands / segments) over the interior
   // left between B-row bands; too thin for that: valid = 0 (serial cycle)
-  kern::SplitPlan d = kern::plan_split(dtype(), L_, k, B, compute_cus_, spare_waves(), base.ring, base.main.nb,
+  kern::SplitPlan d = kern::plan_split(dtype(), Lk_, k, B, compute_cus_, spare_waves(), base.ring, base.main.nb,
                                        cfg_.arith);
   if (d.valid) {
     if (base.nedge > 0 && base.edge[0].nb > 1) d = kern::with_edge_bands(dtype(), d, base.edge[0].nb, cfg_.arith);
@@ -627,8 +675,8 @@ void Solver::trial_cycle(const kern::SplitPlan& c) {
   last_k_ = 0;  // the other buffer no longer holds T_{n-1}: stats(residual) reports NaN
   if (c.valid == 3) {  // edge-first: both parts in order on the compute stream
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
-    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_compute_, cfg_.arith);
-    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_);
+    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_);
+    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_);
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
     return;
@@ -636,15 +684,15 @@ void Solver::trial_cycle(const kern::SplitPlan& c) {
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
   H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));
   if (c.flags & kern::kPlanLead) {  // lead: the band launch issued first
-    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith);
-    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_);
+    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_);
+    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_);
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
     return;
   }
-  kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_);
+  kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_);
   H2D_HIP(hipEventRecord(ev_int_, s_compute_));
-  kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith);
+  kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_);
   H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
 }
 
@@ -702,12 +750,12 @@ std::string Solver::cache_ctx() const {
     arch = prop.gcnArchName;
     ncu = prop.multiProcessorCount;
   }
-  const int pos = (L_.row0 == 0 ? 1 : 0) | (L_.row0 + L_.nrows == L_.nrows_global ? 2 : 0);
+  const int pos = (Lk_.row0 == 0 ? 1 : 0) | (Lk_.row0 + Lk_.nrows == Lk_.nrows_global ? 2 : 0);
   char b[640];
-  std::snprintf(b, sizeof(b), "%s|cu%d|%s|ar%d|%lldx%lld|p%lld|h%lld|pos%d|ccu%d|sp%d|x%d|tr=%s|env%016llx",
+  std::snprintf(b, sizeof(b), "%s|cu%d|%s|ar%d|%lldx%lld|p%lld|h%lld|pos%d|ccu%d|sp%d|x%d|tr=%s|bc%d%d|env%016llx",
                 arch.c_str(), ncu, dtype_name(dtype()), cfg_.arith, (long long)L_.nrows, (long long)L_.ncols,
                 (long long)L_.pitch, (long long)L_.halo, pos, compute_cus_, spare_waves(), tr_->exchanges() ? 1 : 0,
-                tr_->name().c_str(), (unsigned long long)plan_env_hash());
+                tr_->name().c_str(), (int)cfg_.bc_x, (int)cfg_.bc_y, (unsigned long long)plan_env_hash());
   return b;
 }
 
@@ -719,7 +767,7 @@ bool Solver::cached_split(int k) {
   float ms = 0.f;
   if (!plancache::get_plan(cache_ctx(), k, k, &c, &ms) || ms <= 0.f) return false;
   // geometry must match this slab (defensive: the key already pins it)
-  const kern::SplitPlan fresh = kern::plan_split(dtype(), L_, k, k, compute_cus_, spare_waves(), c.ring,
+  const kern::SplitPlan fresh = kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare_waves(), c.ring,
                                                  c.main.nb, cfg_.arith);
   if (!c.valid || (c.valid != 2 && !fresh.valid) || c.main.r1 > L_.nrows || c.nedge > 4) return false;
   // semantic checks on top of the key: a plan kind this run may not use
@@ -818,8 +866,8 @@ void Solver::autotune_split(int k) {
       const kern::SplitPlan& q = split_[nk];
       if (q.k != nk || !q.valid) continue;
       kern::SplitPlan c = q.valid == 2
-                              ? kern::plan_single(dtype(), L_, k, compute_cus_, q.ring, q.main.nb, cfg_.arith)
-                              : kern::plan_split(dtype(), L_, k, k, compute_cus_, spare, q.ring, q.main.nb, cfg_.arith);
+                              ? kern::plan_single(dtype(), Lk_, k, compute_cus_, q.ring, q.main.nb, cfg_.arith)
+                              : kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, q.ring, q.main.nb, cfg_.arith);
       if (!c.valid) continue;
       c.valid = q.valid;
       c.flags = q.flags;
@@ -838,7 +886,7 @@ void Solver::autotune_split(int k) {
   const int64_t nb0 = best.main.nb;
   // without an exchange to hide, a single general launch per cycle competes too
   const bool single_ok = !tr_->exchanges();
-  const int64_t nb1 = single_ok ? kern::plan_single(dtype(), L_, k, compute_cus_, 0, 0, cfg_.arith).main.nb : 0;
+  const int64_t nb1 = single_ok ? kern::plan_single(dtype(), Lk_, k, compute_cus_, 0, 0, cfg_.arith).main.nb : 0;
   // mode 1: split, interior and bands concurrently on two streams; mode 2
   // (no exchange): one general launch; mode 3 (exchange): edge-first split —
   // the short band launch first on the whole chip, then the interior, with the
@@ -877,8 +925,8 @@ void Solver::autotune_split(int k) {
       for (double f : factors) {
         const int64_t nb = std::max<int64_t>(1, (int64_t)((mode == 2 ? nb1 : nb0) * f + 0.5));
         if (mode == 1 && ring == best.ring && nb == best.main.nb) continue;
-        kern::SplitPlan c = mode == 2 ? kern::plan_single(dtype(), L_, k, compute_cus_, ring, nb, cfg_.arith)
-                                      : kern::plan_split(dtype(), L_, k, k, compute_cus_, spare, ring, nb,
+        kern::SplitPlan c = mode == 2 ? kern::plan_single(dtype(), Lk_, k, compute_cus_, ring, nb, cfg_.arith)
+                                      : kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, ring, nb,
                                                          cfg_.arith);
         if (!c.valid) continue;
         if (mode == 3) c.valid = 3;
@@ -893,7 +941,7 @@ void Solver::autotune_split(int k) {
       // by noise and then ran 1.7 % slower than bands on 32768^2 (interleaved A/B,
       // profiles/thin_slab.md §4), while single launches over segments win 4096^2
       if (dtype() == DType::F32 && mode != 2) continue;
-      const int64_t w0 = mode == 2 ? kern::plan_single(dtype(), L_, k, compute_cus_, ring, 0, cfg_.arith).main_waves
+      const int64_t w0 = mode == 2 ? kern::plan_single(dtype(), Lk_, k, compute_cus_, ring, 0, cfg_.arith).main_waves
                                    : best.main_waves;
       std::vector<int64_t> segs;
       for (double f : long_cycles ? std::vector<double>{1.0} : std::vector<double>{0.5, 1.0, 1.5, 2.0})
@@ -903,7 +951,7 @@ void Solver::autotune_split(int k) {
         // r = 1/4 single launches: strip-aligned segment counts too (a whole
         // number per strip), whose frame-row items the plan can weight
         // (stencil_tb.hip weighted_main) — one per SIMD and one per wave
-        const int64_t ns = kern::plan_single(dtype(), L_, k, compute_cus_, ring, 0, cfg_.arith).main.s1;
+        const int64_t ns = kern::plan_single(dtype(), Lk_, k, compute_cus_, ring, 0, cfg_.arith).main.s1;
         const int64_t simds = (int64_t)(compute_cus_ > 0 ? compute_cus_ : device_cus_of(cfg_.device)) * 4;
         for (int64_t target : {simds, w0, 2 * simds}) {
           const int64_t q = target / std::max<int64_t>(ns, 1);
@@ -913,8 +961,8 @@ void Solver::autotune_split(int k) {
       std::sort(segs.begin(), segs.end());
       segs.erase(std::unique(segs.begin(), segs.end()), segs.end());
       for (int64_t nseg : segs) {
-        kern::SplitPlan c = mode == 2 ? kern::plan_single(dtype(), L_, k, compute_cus_, ring, -nseg, cfg_.arith)
-                                      : kern::plan_split(dtype(), L_, k, k, compute_cus_, spare, ring, -nseg,
+        kern::SplitPlan c = mode == 2 ? kern::plan_single(dtype(), Lk_, k, compute_cus_, ring, -nseg, cfg_.arith)
+                                      : kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, ring, -nseg,
                                                          cfg_.arith);
         if (!c.valid) continue;
         if (mode == 3) c.valid = 3;
@@ -985,7 +1033,7 @@ void Solver::launch_overlap(int k, int64_t B) {
   // one-cycle step, edge-first 640: profiles/r5/ad/)
   const bool lead = (sp.valid == 1 || sp.valid == 3) &&
                     ((sp.flags & kern::kPlanLead) ||
-                     (first_cycle_ && tr_->exchanges() && lead_first() && kern::edges_on_main(L_, sp)));
+                     (first_cycle_ && tr_->exchanges() && lead_first() && kern::edges_on_main(Lk_, sp)));
   // An edge rank's first cycle: its two bands apart. The far band (the one
   // the exchange sends, clear of the global frame) leads on the interior
   // kernel as on a middle rank; the frame-side band — which no exchange
@@ -994,16 +1042,16 @@ void Solver::launch_overlap(int k, int64_t B) {
   // items leaves free.
   int frame_rect = -1;
   if (!lead && (sp.valid == 1 || sp.valid == 3) && first_cycle_ && tr_->exchanges() && lead_first() &&
-      sp.nedge == 2 && kern::edge_rect_on_main(L_, sp, 0) != kern::edge_rect_on_main(L_, sp, 1))
-    frame_rect = kern::edge_rect_on_main(L_, sp, 0) ? 1 : 0;
+      sp.nedge == 2 && kern::edge_rect_on_main(Lk_, sp, 0) != kern::edge_rect_on_main(Lk_, sp, 1))
+    frame_rect = kern::edge_rect_on_main(Lk_, sp, 0) ? 1 : 0;
   first_cycle_ = false;
   if (frame_rect >= 0) {
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));  // edge part c-1
     H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));     // main part c-1
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_comm_));
-    kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, cfg_.arith);
+    kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, cfg_.arith, bc_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_);
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_comm_));
@@ -1019,12 +1067,12 @@ void Solver::launch_overlap(int k, int64_t B) {
     // comm stream (cycle_finish) = [bands(c) done] exchange(c), beside the interior.
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_comm_, 0));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, cfg_.arith);
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
     if (tr_->exchanges()) tr_->post(dst, L_, ev_bnd_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_);
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     pend_ = Pending::EdgeFirst;
@@ -1035,23 +1083,23 @@ void Solver::launch_overlap(int k, int64_t B) {
   if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_comm_));
   if (lead) {
     // lead: the band launch first (comm stream), then the interior beside it
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith);
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_);
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
   } else if (sp.valid) {
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_);
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith);
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_);
   } else {  // slab too thin / narrow to split: all of it beside the exchange
     if (pe) {
       H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
       H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     }
-    kern::launch_tb(dtype(), src, dst, L_, 0, L_.nrows, k, cfg_.r, s_comm_, 0, 0, cfg_.arith);
+    kern::launch_tb(dtype(), src, dst, L_, 0, L_.nrows, k, cfg_.r, s_comm_, 0, 0, cfg_.arith, bc_);
   }
   if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_comm_));
   H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
@@ -1353,7 +1401,7 @@ float Solver::prescan_ms(int k) {
     if (tuned_ms_[k] > 0.f) {
       v = tuned_ms_[k];
     } else {
-      const kern::SplitPlan base = kern::plan_split(dtype(), L_, k, k, compute_cus_, spare_waves(), 0, 0, cfg_.arith);
+      const kern::SplitPlan base = kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare_waves(), 0, 0, cfg_.arith);
       if (base.valid) {
         synchronize();
         v = time_plan(base, 2);
@@ -1742,7 +1790,8 @@ void Solver::synchronize() {
 void Solver::step_stats(int64_t n, double out[6]) {
   HEAT2D_REQUIRE(n >= 1, "step_stats needs n >= 1");
   if (hip_) H2D_HIP(hipSetDevice(cfg_.device));
-  if (!hip_ || jit_ || cfg_.copy_swap) {
+  // (periodic y: the fused-statistics march would count its ghost columns)
+  if (!hip_ || jit_ || cfg_.copy_swap || cfg_.bc_y) {
     step(n - 1);
     step(1);
     stats(out, true);
@@ -1868,6 +1917,39 @@ void Solver::upload(const void* host, int64_t ld) {
   synchronize();
 }
 
+// The frame-inclusive local field, rows [-1, nrows] x columns [-1, ncols]
+// ((nrows + 2) x (ncols + 2), leading dimension ld): the owned points into the
+// current buffer, the frame lines of a Dirichlet axis into both (they are
+// never rewritten), then the wrap fills and the halo exchange of upload().
+// Frame entries on a periodic axis are ignored — the fills and the exchange
+// replace them with wrap images — as are rows -1 / nrows of a slab that is not
+// at the global frame (ghost rows: the exchange fills them).
+void Solver::upload_framed(const void* host, int64_t ld) {
+  const size_t es = dtype_size(dtype());
+  const int64_t h = L_.nrows + 2, w = L_.ncols + 2;
+  if (hip_) synchronize();
+  for (int b = 0; b < 2; ++b) {
+    char* dst = static_cast<char*>(buf_[b]) + (size_t)L_.offset(-1, -1) * es;
+    if (hip_) {
+      H2D_HIP(hipMemcpy2DAsync(dst, (size_t)L_.pitch * es, host, (size_t)ld * es, (size_t)w * es, (size_t)h,
+                               hipMemcpyHostToDevice, s_compute_));
+    } else {
+      for (int64_t i = 0; i < h; ++i)
+        std::memcpy(dst + (size_t)(i * L_.pitch) * es, static_cast<const char*>(host) + (size_t)(i * ld) * es,
+                    (size_t)w * es);
+    }
+    wrap_cols_all(buf_[b]);
+  }
+  if (hip_) H2D_HIP(hipStreamSynchronize(s_compute_));
+}
+
+void Solver::upload_field(const void* host, int64_t ld) {
+  upload_framed(host, ld);
+  exchange_post();
+  exchange_now();
+  synchronize();
+}
+
 void Solver::upload_owned(const void* host, int64_t ld) {
   const size_t es = dtype_size(dtype());
   char* dst = static_cast<char*>(buf_[cur_]) + (size_t)L_.origin() * es;
@@ -1880,6 +1962,7 @@ void Solver::upload_owned(const void* host, int64_t ld) {
       std::memcpy(dst + (size_t)(i * L_.pitch) * es, static_cast<const char*>(host) + (size_t)(i * ld) * es,
                   (size_t)L_.ncols * es);
   }
+  wrap_cols_all(buf_[cur_]);  // (the exchange that follows moves the ghost rows' columns too)
 }
 
 // ------------------------------------------------------------------ loopback
@@ -1902,6 +1985,12 @@ LoopbackGroup::~LoopbackGroup() {
 
 void LoopbackGroup::init(const kern::IcParams& ic, const double* xg, const double* yg) {
   for (auto& m : members_) m->init(ic, xg, yg);
+  if (members_[0]->config().bc_x) {  // periodic x: the ghost rows are wrap images (Solver::init)
+    for (auto& m : members_) m->synchronize();
+    for (auto& m : members_) m->exchange_post();
+    for (auto& m : members_) m->exchange_now();
+    synchronize();
+  }
 }
 
 // step()'s loop (balanced depths; no graphs: a capture cannot span the
@@ -1938,6 +2027,18 @@ void LoopbackGroup::upload(const void* host, int64_t ld) {
   for (auto& m : members_) {
     m->synchronize();
     m->upload_owned(static_cast<const char*>(host) + (size_t)(m->layout().row0 * ld) * es, ld);
+  }
+  for (auto& m : members_) m->exchange_post();
+  for (auto& m : members_) m->exchange_now();
+  synchronize();
+}
+
+void LoopbackGroup::upload_field(const void* host, int64_t ld) {
+  const size_t es = dtype_size(members_[0]->dtype());
+  for (auto& m : members_) {
+    m->synchronize();
+    // local row -1 is frame-inclusive global row row0
+    m->upload_framed(static_cast<const char*>(host) + (size_t)(m->layout().row0 * ld) * es, ld);
   }
   for (auto& m : members_) m->exchange_post();
   for (auto& m : members_) m->exchange_now();

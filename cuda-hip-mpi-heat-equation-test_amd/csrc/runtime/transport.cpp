@@ -47,11 +47,25 @@ class SelfTransport final : public Transport {
  public:
   int rank() const override { return 0; }
   int size() const override { return 1; }
-  void exchange(void*, const SlabLayout&, DType, int64_t, hipStream_t, bool) override {}
+  // periodic x: the slab's boundary rows onto its own ghost rows (one kernel on
+  // `stream`, nothing else: capturable), else nothing to exchange
+  void exchange(void* field, const SlabLayout& L, DType dt, int64_t k, hipStream_t stream, bool on_device) override {
+    if (!wrap_ || k <= 0) return;
+    if (on_device) kern::launch_wrap_rows(dt, field, L, k, stream);
+    else cpu::wrap_rows(dt, field, L, k);
+  }
   void allreduce(double*, int, int) override {}
   void barrier() override {}
-  std::string name() const override { return "self"; }
+  std::string name() const override { return wrap_ ? "self-wrap" : "self"; }
   bool capturable() const override { return true; }
+  bool exchanges() const override { return wrap_; }
+  bool set_periodic_x(bool on) override {
+    wrap_ = on;
+    return true;
+  }
+
+ private:
+  bool wrap_ = false;
 };
 
 // ------------------------------------------------------------------ RCCL
@@ -308,13 +322,23 @@ class CallbackTransport final : public Transport {
   int size() const override { return size_; }
   std::string name() const override { return "callback"; }
 
-  void exchange(void* field, const SlabLayout& L, DType dt, int64_t k, hipStream_t stream,
+  void exchange(void* field, const SlabLayout& L0, DType dt, int64_t k, hipStream_t stream,
                 bool on_device) override {
     if (size_ == 1 || k <= 0) return;
     const size_t es = dtype_size(dt);
+    // Periodic x: the packed rows carry the two frame columns as well (columns
+    // -1 .. ncols: the same layout seen one column to the left, two wider) — a
+    // wrapped ghost row's Dirichlet-y frame entries are the sender's, which
+    // init() cannot know from the global IC as it does for in-grid ghost rows.
+    SlabLayout L = L0;
+    if (wrap_) {
+      L.cpad -= 1;
+      L.ncols += 2;
+    }
     const int64_t count = k * L.ncols;
     const size_t bytes = (size_t)(4 * count) * es;
-    const bool has_lo = rank_ > 0, has_hi = rank_ < size_ - 1;
+    // (periodic x: every rank has both neighbours; the callbacks address them modulo size)
+    const bool has_lo = rank_ > 0 || wrap_, has_hi = rank_ < size_ - 1 || wrap_;
     if (on_device) {
       // device -> pinned host staging (the reference's path, kept for generic
       // transports): buffers grow once and are reused; the previous
@@ -365,10 +389,16 @@ class CallbackTransport final : public Transport {
     if (size_ == 1) return;
     HEAT2D_REQUIRE(ops_.barrier(ops_.ctx) == 0, "barrier callback failed");
   }
+  bool set_periodic_x(bool on) override {
+    wrap_ = on;
+    return true;
+  }
+  bool whole_rows() const override { return false; }
 
  private:
   CallbackOps ops_;
   int rank_, size_;
+  bool wrap_ = false;
   std::vector<char> stage_;      // host fields
   void* d_stage_ = nullptr;      // device fields: [send_lo | send_hi | recv_lo | recv_hi]
   void* h_stage_ = nullptr;      // pinned host mirror of d_stage_
@@ -434,7 +464,7 @@ class LoopbackTransport final : public Transport {
     const size_t es = dtype_size(dt);
     const size_t bytes = halo_msg_bytes(L, k, es);
     HaloMsg msg[2];
-    const int nmsg = halo_msgs(rank_, size(), L, k, msg);
+    const int nmsg = halo_msgs(rank_, size(), L, k, msg, wrap_);
     if (on_device) {
       for (auto& e : me.done)
         if (!e) H2D_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -444,11 +474,7 @@ class LoopbackTransport final : public Transport {
       HEAT2D_REQUIRE(peer.posted == c + 1, "loopback: peer has not posted this cycle");
       HEAT2D_REQUIRE(peer.L.pitch == L.pitch, "loopback: slabs of different pitch");
       // the peer's message toward this rank: its send rows
-      HaloMsg pm[2];
-      const int np = halo_msgs(msg[i].peer, size(), peer.L, k, pm);
-      int64_t send_row = -1;
-      for (int j = 0; j < np; ++j)
-        if (pm[j].peer == rank_) send_row = pm[j].send_row;
+      const int64_t send_row = halo_peer_send_row(rank_, size(), msg[i], peer.L, k, wrap_);
       HEAT2D_REQUIRE(send_row >= 0, "loopback: peer does not send to this rank");
       const char* src = static_cast<const char*>(peer.field) + halo_row_bytes(peer.L, send_row, es);
       char* dst = static_cast<char*>(field) + halo_row_bytes(L, msg[i].recv_row, es);
@@ -463,10 +489,15 @@ class LoopbackTransport final : public Transport {
     if (on_device) H2D_HIP(hipEventRecord(me.done[c & 1], stream));
     ++me.pulled;
   }
+  bool set_periodic_x(bool on) override {
+    wrap_ = on;
+    return true;
+  }
 
  private:
   std::shared_ptr<LoopbackHub> hub_;
   int rank_;
+  bool wrap_ = false;
 };
 
 // ------------------------------------------------------------------ host threads
@@ -555,17 +586,15 @@ class ThreadTransport final : public Transport {
     hub_->barrier(rank_);  // every rank's new field is published
     const size_t es = dtype_size(dt);
     HaloMsg msg[2];
-    const int nmsg = halo_msgs(rank_, size(), L, k, msg);
+    const int nmsg = halo_msgs(rank_, size(), L, k, msg, wrap_);
     for (int i = 0; i < nmsg; ++i) {
       const int p = msg[i].peer;
       const SlabLayout& PL = hub_->layout[(size_t)p];
       HEAT2D_REQUIRE(PL.pitch == L.pitch, "slabs of different pitch");
-      HaloMsg pm[2];
-      const int np = halo_msgs(p, size(), PL, k, pm);
-      for (int j = 0; j < np; ++j)
-        if (pm[j].peer == rank_)
-          std::memcpy(static_cast<char*>(field) + halo_row_bytes(L, msg[i].recv_row, es),
-                      hub_->field[(size_t)p] + halo_row_bytes(PL, pm[j].send_row, es), halo_msg_bytes(L, k, es));
+      const int64_t send_row = halo_peer_send_row(rank_, size(), msg[i], PL, k, wrap_);
+      if (send_row >= 0)
+        std::memcpy(static_cast<char*>(field) + halo_row_bytes(L, msg[i].recv_row, es),
+                    hub_->field[(size_t)p] + halo_row_bytes(PL, send_row, es), halo_msg_bytes(L, k, es));
     }
     hub_->barrier(rank_);  // nobody moves on (and overwrites its field) before all copies are done
   }
@@ -585,11 +614,16 @@ class ThreadTransport final : public Transport {
     hub_->barrier(rank_, io_ > 0);
   }
   void barrier() override { hub_->barrier(rank_, io_ > 0); }
+  bool set_periodic_x(bool on) override {
+    wrap_ = on;
+    return true;
+  }
 
  private:
   std::shared_ptr<ThreadHub> hub_;
   int rank_;
   int io_ = 0;
+  bool wrap_ = false;
 };
 
 // ------------------------------------------------------------------ peer

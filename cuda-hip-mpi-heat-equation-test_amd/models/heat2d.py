@@ -120,6 +120,13 @@ class HeatSolver:
             decomposition (common.hpp decompose): an edge slab's cycle costs
             more per row, and a step lasts as long as the slowest rank;
             bench.py measures the excess and picks the shift. Same on every rank.
+        bc_x, bc_y: boundary condition of the row (x, decomposed over ranks) and
+            column (y) axis: "dirichlet" (the frame keeps its values) or
+            "periodic" (the n owned points are the period). Periodic results
+            are bitwise equal to models.reference.ftcs(bc_x=, bc_y=) at any
+            depth, plan and rank count; engine "tb" only, no copy_swap; on more
+            than one rank periodic x runs on the loopback, host-thread and
+            torch.distributed (host-staged) transports.
     """
 
     def __init__(self, problem: Problem, *, dtype: str = "fp64", backend: str = "auto", tb: int = 0,
@@ -127,9 +134,11 @@ class HeatSolver:
                  tile_rows: int = 0, halo: int = 0, transport: Optional[T.Transport] = None,
                  device: Optional[int] = None, init: bool = True, rows: Optional[int] = None,
                  comm_cus: int = 0, autotune: int = -1, engine: str = "tb", arith: str = "auto",
-                 slab_row0: Optional[int] = None, edge_shift: int = 0):
+                 slab_row0: Optional[int] = None, edge_shift: int = 0, bc_x: str = "dirichlet",
+                 bc_y: str = "dirichlet"):
         self.problem = problem
-        self.edge_shift = int(edge_shift)
+        self.edge_shift = 0 if bc_x == "periodic" else int(edge_shift)  # (periodic x: no edge slabs)
+        self.bc_x, self.bc_y = bc_x, bc_y
         self.backend = resolve_backend(backend)
         self.dtype = DTYPES[dtype]
         self.np_dtype = NP_DTYPES[self.dtype]
@@ -162,6 +171,8 @@ class HeatSolver:
         cfg.comm_cus = comm_cus
         cfg.autotune = autotune
         cfg.edge_shift = self.edge_shift
+        cfg.bc_x = N.bc_code(bc_x, "bc_x")
+        cfg.bc_y = N.bc_code(bc_y, "bc_y")
         if engine not in ("tb", "jit"):
             raise ValueError("engine must be 'tb' (temporal-blocked kernels) or 'jit' (hipRTC, one step per launch)")
         cfg.engine = 1 if engine == "jit" else 0
@@ -207,8 +218,13 @@ class HeatSolver:
         return {"tb": tb.value, "band": band.value, "steps": steps.value, "field": field.value,
                 "stream": stream.value, "backend": self.backend, "transport": self.transport.name,
                 "arith": _arith(self._h),  # the resolved code: 0 exact, 1 fma, 2 jacobi, 3 fast
-
+                "bc_x": self._bc()[0], "bc_y": self._bc()[1],  # "dirichlet" | "periodic", as the native solver runs
                 "rank": self.rank, "size": self.size, "layout": self.layout.as_dict()}
+
+    def _bc(self) -> tuple:
+        bx, by = C.c_int32(), C.c_int32()
+        N.call("heat2d_solver_bc", self._h, C.byref(bx), C.byref(by))
+        return N.BC_NAMES[bx.value], N.BC_NAMES[by.value]
 
     def set_timing(self, on: bool = True) -> None:
         """Record hipEvent phase timers for every cycle from now on (HIP backend)."""
@@ -358,11 +374,29 @@ class HeatSolver:
         N.call("heat2d_solver_download", self._h, out.ctypes.data_as(C.c_void_p), self.ncols)
         return out
 
+    def download_field(self) -> np.ndarray:
+        """This rank's rows with their frame, (nrows + 2) x (ncols + 2): local
+        rows -1 .. nrows (the global frame rows on the first / last rank, else
+        the neighbours' rows) and columns -1 .. ncols. On a periodic axis the
+        frame entries are wrap images of the owned points."""
+        out = np.empty((self.nrows + 2, self.ncols + 2), dtype=self.np_dtype)
+        N.call("heat2d_solver_download_region", self._h, -1, self.nrows + 1, -1, self.ncols + 1,
+               out.ctypes.data_as(C.c_void_p), self.ncols + 2)
+        return out
+
     def upload(self, arr: np.ndarray) -> None:
-        """Set this rank's owned rows (collective: followed by a halo exchange)."""
+        """Set this rank's owned rows (collective: followed by a halo exchange).
+        ``arr``: the owned points (nrows, ncols), or the frame-inclusive local
+        field (nrows + 2, ncols + 2) — then the frame lines of a Dirichlet axis
+        are set too, and the entries on a periodic axis are ignored (they become
+        wrap images of the owned points)."""
         a = np.ascontiguousarray(arr, dtype=self.np_dtype)
+        if a.shape == (self.nrows + 2, self.ncols + 2):
+            N.call("heat2d_solver_upload_field", self._h, a.ctypes.data_as(C.c_void_p), self.ncols + 2)
+            return
         if a.shape != (self.nrows, self.ncols):
-            raise ValueError(f"expected {(self.nrows, self.ncols)}, got {a.shape}")
+            raise ValueError(f"expected {(self.nrows, self.ncols)} (or the frame-inclusive "
+                             f"{(self.nrows + 2, self.ncols + 2)}), got {a.shape}")
         N.call("heat2d_solver_upload", self._h, a.ctypes.data_as(C.c_void_p), self.ncols)
 
     def compare(self, other: "HeatSolver", r0: int = 0, nrows: Optional[int] = None, other_r0: Optional[int] = None
@@ -420,8 +454,10 @@ class LoopbackGroup:
 
     def __init__(self, problem: Problem, nranks: int, *, dtype: str = "fp64", backend: str = "auto",
                  tb: int = 0, tile_rows: int = 0, device: Optional[int] = None, arith: str = "auto",
-                 overlap: bool = True, autotune: int = -1, comm_cus: int = 0, edge_shift: int = 0):
+                 overlap: bool = True, autotune: int = -1, comm_cus: int = 0, edge_shift: int = 0,
+                 bc_x: str = "dirichlet", bc_y: str = "dirichlet"):
         self.problem = problem
+        self.bc_x, self.bc_y = bc_x, bc_y
         self.backend = resolve_backend(backend)
         self.dtype = DTYPES[dtype]
         if self.backend == "hip" and device is None:
@@ -441,6 +477,8 @@ class LoopbackGroup:
         cfg.tile_rows = tile_rows
         cfg.arith = N.ARITH[arith]
         cfg.edge_shift = int(edge_shift)
+        cfg.bc_x = N.bc_code(bc_x, "bc_x")
+        cfg.bc_y = N.bc_code(bc_y, "bc_y")
         self.nranks = nranks
         h = C.c_void_p()
         N.call("heat2d_group_create", C.byref(cfg), nranks, C.byref(h))
@@ -457,8 +495,11 @@ class LoopbackGroup:
         """Whole owned grid -> the members' slabs, then a loopback halo exchange."""
         m = self.problem.n_owned
         a = np.ascontiguousarray(arr, dtype=NP_DTYPES[self.dtype])
+        if a.shape == (m + 2, m + 2):  # frame-inclusive (HeatSolver.upload)
+            N.call("heat2d_group_upload_field", self._h, a.ctypes.data_as(C.c_void_p), m + 2)
+            return
         if a.shape != (m, m):
-            raise ValueError(f"expected {(m, m)}, got {a.shape}")
+            raise ValueError(f"expected {(m, m)} (or the frame-inclusive {(m + 2, m + 2)}), got {a.shape}")
         N.call("heat2d_group_upload", self._h, a.ctypes.data_as(C.c_void_p), m)
 
     def download(self) -> np.ndarray:

@@ -46,10 +46,29 @@ def initial_field(problem: Problem, dtype=np.float64) -> np.ndarray:
     return np.ascontiguousarray(T, dtype=np.float64).astype(dtype)
 
 
-def ftcs_step(T: np.ndarray, r, arith: str = "exact") -> np.ndarray:
-    """One FTCS step of a frame-inclusive field (frame kept fixed).
+def wrap_frame(T: np.ndarray, bc_x: str = "dirichlet", bc_y: str = "dirichlet") -> np.ndarray:
+    """The frame-inclusive field with its frame entries on periodic axes
+    replaced by wrap images of the owned points (``np.pad(mode="wrap")``). With
+    only y periodic the Dirichlet frame rows wrap too: the point (0, -1) reads
+    (-1, -1). Dirichlet on both axes: T itself."""
+    for name, bc in (("bc_x", bc_x), ("bc_y", bc_y)):
+        if bc not in ("dirichlet", "periodic"):
+            raise ValueError(f"{name} must be 'dirichlet' or 'periodic', got {bc!r}")
+    px, py = bc_x == "periodic", bc_y == "periodic"
+    if not (px or py):
+        return T
+    core = T[(1 if px else 0):(-1 if px else None), (1 if py else 0):(-1 if py else None)]
+    return np.pad(core, ((1, 1) if px else (0, 0), (1, 1) if py else (0, 0)), mode="wrap")
+
+
+def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet") -> np.ndarray:
+    """One FTCS step of a frame-inclusive field. On a Dirichlet axis the frame
+    is kept fixed; on a periodic one it is refreshed from the owned points
+    before the step (:func:`wrap_frame`) — the update and its operation order
+    are the same — and holds the wrap images of T at time t on return.
     arith "jacobi" (r == 1/4 only): r * sum, the zero centre weight folded
     away — the engine's arith 2."""
+    T = wrap_frame(T, bc_x, bc_y)
     r = T.dtype.type(r)
     four = T.dtype.type(4)
     c = T[1:-1, 1:-1]
@@ -68,13 +87,14 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact") -> np.ndarray:
 
 
 def ftcs(problem: Problem, nsteps: int | None = None, dtype=np.float64, T0: np.ndarray | None = None,
-         arith: str = "exact") -> np.ndarray:
-    """Run FTCS; returns the frame-inclusive field."""
+         arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet") -> np.ndarray:
+    """Run FTCS; returns the frame-inclusive field (frame entries on periodic
+    axes: wrap images of the returned owned points)."""
     T = initial_field(problem, dtype) if T0 is None else T0.astype(dtype)
     n = problem.ntime if nsteps is None else nsteps
     for _ in range(n):
-        T = ftcs_step(T, problem.r, arith)
-    return T
+        T = ftcs_step(T, problem.r, arith, bc_x, bc_y)
+    return wrap_frame(T, bc_x, bc_y)
 
 
 def fast_error_bound(nsteps: int, dtype, tmax: float) -> float:
@@ -121,6 +141,19 @@ def eigen_factor(problem: Problem, kx: float = 1.0, ky: float = 1.0) -> float:
     L = problem.x[-1] - problem.x[0]
     d = problem.delta
     return 1.0 - 4.0 * problem.r * (np.sin(kx * np.pi * d / (2 * L)) ** 2 + np.sin(ky * np.pi * d / (2 * L)) ** 2)
+
+
+def periodic_eigen_factor(r: float, n: int, k: int = 1, l: int = 1) -> float:
+    """Per-step amplification of the mode cos(2 pi k i / n) cos(2 pi l j / n)
+    on the fully periodic n x n grid: g = 1 - 4r (sin^2(pi k / n) + sin^2(pi l / n))."""
+    return 1.0 - 4.0 * r * (np.sin(np.pi * k / n) ** 2 + np.sin(np.pi * l / n) ** 2)
+
+
+def periodic_eigenmode(r: float, n: int, nsteps: int, k: int = 1, l: int = 1) -> np.ndarray:
+    """Closed-form FTCS solution (owned n x n points) from that mode: g^nsteps T_0."""
+    i = np.arange(n)
+    T0 = np.cos(2 * np.pi * k * i / n)[:, None] * np.cos(2 * np.pi * l * i / n)[None, :]
+    return T0 * periodic_eigen_factor(r, n, k, l) ** nsteps
 
 
 def eigenmode(problem: Problem, nsteps: int) -> np.ndarray:

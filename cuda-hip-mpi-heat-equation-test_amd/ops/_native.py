@@ -41,6 +41,17 @@ def arith_code(arith: str, r: float) -> int:
         raise ValueError("arith 'jacobi' needs r == 1/4 exactly (sigma = 0.25)")
     return ARITH[arith]
 BACKEND_HIP, BACKEND_CPU = 0, 1
+# boundary condition of an axis (Config.bc_x / bc_y); the raw ops take the bit
+# set BC_PERIODIC_X | BC_PERIODIC_Y (kernels.hpp)
+BC = {"dirichlet": 0, "periodic": 1}
+BC_NAMES = {v: k for k, v in BC.items()}
+BC_PERIODIC_X, BC_PERIODIC_Y = 1, 2
+
+
+def bc_code(name: str, what: str = "bc") -> int:
+    if name not in BC:
+        raise ValueError(f"{what} must be one of {sorted(BC)}, got {name!r}")
+    return BC[name]
 
 
 class Layout(C.Structure):
@@ -81,6 +92,7 @@ class Config(C.Structure):
         ("comm_cus", C.c_int32), ("autotune", C.c_int32),
         ("engine", C.c_int32), ("arith", C.c_int32),
         ("edge_shift", C.c_int32), ("slab_row0", C.c_int64), ("slab_rows_global", C.c_int64),
+        ("bc_x", C.c_int32), ("bc_y", C.c_int32),
     ]
 
 
@@ -139,6 +151,9 @@ _SIGS = {
     "heat2d_solver_plan": (C.c_int, [_P, C.c_int, C.POINTER(SplitPlan), C.POINTER(C.c_float)]),
     "heat2d_solver_plans_made": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "heat2d_tb": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, _P, _I64, C.c_int]),
+    "heat2d_tb_bc": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, _P, _I64, C.c_int, C.c_int]),
+    "heat2d_wrap_cols": (C.c_int, [C.c_int, _P, _LP, _I64, _I64, _P, C.c_int]),
+    "heat2d_wrap_rows": (C.c_int, [C.c_int, _P, _LP, _I64, _P, C.c_int]),
     "heat2d_init_field": (C.c_int, [C.c_int, _P, _LP, C.POINTER(IcParams), _P, _P, _P]),
     "heat2d_stats": (C.c_int, [C.c_int, _P, _P, _LP, _P, _P, _P]),
     "heat2d_stats_work_elems": (_I64, []),
@@ -147,6 +162,7 @@ _SIGS = {
     "heat2d_pack_rows": (C.c_int, [C.c_int, _P, _LP, _I64, _I64, _P, _P]),
     "heat2d_unpack_rows": (C.c_int, [C.c_int, _P, _LP, _I64, _I64, _P, _P]),
     "heat2d_cpu_tb": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, C.c_int]),
+    "heat2d_cpu_tb_bc": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, C.c_int, C.c_int]),
     "heat2d_cpu_init_field": (C.c_int, [C.c_int, _P, _LP, C.POINTER(IcParams), _P, _P]),
     "heat2d_cpu_stats": (C.c_int, [C.c_int, _P, _P, _LP, _P]),
     "heat2d_rccl_unique_id": (C.c_int, [_P]),
@@ -169,6 +185,9 @@ _SIGS = {
     "heat2d_solver_sync": (C.c_int, [_P]),
     "heat2d_solver_stats": (C.c_int, [_P, _P, C.c_int]),
     "heat2d_solver_download": (C.c_int, [_P, _P, _I64]),
+    "heat2d_solver_upload_field": (C.c_int, [_P, _P, _I64]),
+    "heat2d_solver_download_region": (C.c_int, [_P, _I64, _I64, _I64, _I64, _P, _I64]),
+    "heat2d_group_upload_field": (C.c_int, [_P, _P, _I64]),
     "heat2d_solver_compare": (C.c_int, [_P, _P, _I64, _I64, _I64, _P]),
     "heat2d_solver_footprint": (C.c_int, [C.POINTER(Config), C.c_int, C.c_int, C.POINTER(_I64)]),
     "heat2d_plan_max_grid": (C.c_int, [C.c_int, C.c_int, _I64, C.POINTER(_I64)]),
@@ -178,6 +197,7 @@ _SIGS = {
     "heat2d_solver_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(_I64), C.POINTER(_I64),
                                      C.POINTER(_P), C.POINTER(_P)]),
     "heat2d_solver_arith": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "heat2d_solver_bc": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "heat2d_group_create": (C.c_int, [C.POINTER(Config), C.c_int, C.POINTER(_P)]),
     "heat2d_group_free": (C.c_int, [_P]),
     "heat2d_group_init": (C.c_int, [_P, C.POINTER(IcParams), _P, _P]),

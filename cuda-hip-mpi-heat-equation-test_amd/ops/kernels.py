@@ -85,11 +85,16 @@ def init_field(field: torch.Tensor, layout: N.Layout, ic, xcoord: np.ndarray,
 
 
 def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: float,
-            rows: Optional[tuple[int, int]] = None, tile_rows: int = 0, arith: str = "exact") -> None:
+            rows: Optional[tuple[int, int]] = None, tile_rows: int = 0, arith: str = "exact",
+            bc_x: str = "dirichlet", bc_y: str = "dirichlet") -> None:
     """dst[rows] = k FTCS steps of src (temporal-blocked kernel). The k ghost rows
     around ``rows`` must be valid in ``src``; Dirichlet rows/cols are kept.
     ``arith``: "exact" (reference rounding), "fma" (contracted update) or
-    "jacobi" (r == 1/4: r * sum)."""
+    "jacobi" (r == 1/4: r * sum).
+    ``bc_y="periodic"``: no column is pinned — ``src`` must hold wrap images in
+    its ghost columns (:func:`wrap_cols`), and the ghost columns of the rows
+    written are refreshed in ``dst``. ``bc_x="periodic"``: no row is pinned
+    (the ghost rows hold wrap images: :func:`wrap_rows`)."""
     _check_field(src, layout)
     _check_field(dst, layout)
     if src.dtype != dst.dtype or src.device != dst.device:
@@ -98,12 +103,34 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
         raise ValueError("tb_step is out-of-place (ping-pong fields)")
     rb, re = (0, layout.nrows) if rows is None else rows
     ar = N.arith_code(arith, r)
+    bc = (N.BC_PERIODIC_X if N.bc_code(bc_x, "bc_x") else 0) | (N.BC_PERIODIC_Y if N.bc_code(bc_y, "bc_y") else 0)
     if src.is_cuda:
-        N.call("heat2d_tb", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
-               C.byref(layout), rb, re, k, r, _stream(src), tile_rows, ar)
+        N.call("heat2d_tb_bc", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+               C.byref(layout), rb, re, k, r, _stream(src), tile_rows, ar, bc)
     else:
-        N.call("heat2d_cpu_tb", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
-               C.byref(layout), rb, re, k, r, ar)
+        N.call("heat2d_cpu_tb_bc", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+               C.byref(layout), rb, re, k, r, ar, bc)
+
+
+WRAP_COLS = 24  # ghost columns per side that wrap_cols fills (kernels.hpp kWrapCols)
+
+
+def wrap_cols(field: torch.Tensor, layout: N.Layout, rows: Optional[tuple[int, int]] = None) -> None:
+    """Periodic y: fill the WRAP_COLS ghost columns on each side of ``rows``
+    (default: every allocated row, ghost rows included) with wrap images of the
+    owned columns: column -1-j <- ncols-1-j, column ncols+j <- j."""
+    _check_field(field, layout)
+    r0, r1 = (-layout.halo, layout.nrows + layout.halo) if rows is None else rows
+    N.call("heat2d_wrap_cols", dtype_code(field), C.c_void_p(field.data_ptr()), C.byref(layout), r0, r1,
+           _stream(field) if field.is_cuda else None, int(field.is_cuda))
+
+
+def wrap_rows(field: torch.Tensor, layout: N.Layout, k: int) -> None:
+    """Periodic x on one slab: whole padded rows [nrows-k, nrows) -> ghost rows
+    [-k, 0) and [0, k) -> [nrows, nrows+k) (k <= halo, k <= nrows)."""
+    _check_field(field, layout)
+    N.call("heat2d_wrap_rows", dtype_code(field), C.c_void_p(field.data_ptr()), C.byref(layout), k,
+           _stream(field) if field.is_cuda else None, int(field.is_cuda))
 
 
 def stats(field: torch.Tensor, layout: N.Layout, other: Optional[torch.Tensor] = None) -> dict:

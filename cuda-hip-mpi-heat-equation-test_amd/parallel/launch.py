@@ -52,6 +52,12 @@ def build_parser():
                          "number, auto (GPU ranks: measured before the run — every rank times its own slab on a "
                          "1-rank loop exchange, uniform and shifted, parallel/select.balance_edges, as bench.py "
                          "does) or measure (the same on any backend)")
+    ap.add_argument("--bc-x", default=None, choices=["dirichlet", "periodic"],
+                    help="boundary condition of the x (row) axis, the one decomposed over ranks (default: "
+                         "dirichlet, or a restart's checkpointed setting; a flag that contradicts the checkpoint "
+                         "fails). periodic on more than one rank: host-staged halos (--transport auto picks them)")
+    ap.add_argument("--bc-y", default=None, choices=["dirichlet", "periodic"],
+                    help="boundary condition of the y (column) axis")
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--ntime", type=int, default=None)
     ap.add_argument("--print-every", type=int, default=0)
@@ -222,10 +228,24 @@ def run(argv=None) -> int:
         return {"torch-dist": T.TorchDistTransport, "self": T.SelfTransport,
                 "rccl": lambda: T.RcclTransport(rank, world, local), "peer": lambda: T.IpcTransport(local)}[kind]()
 
+    # boundary conditions: the flags, or the restart checkpoint's settings
+    bc = {"bc_x": a.bc_x or "dirichlet", "bc_y": a.bc_y or "dirichlet"}
+    if a.restart:
+        saved = checkpoint.load_meta(a.restart)
+        for k, flag in (("bc_x", a.bc_x), ("bc_y", a.bc_y)):
+            bc[k] = saved.get(k, "dirichlet")
+            if flag is not None and flag != bc[k]:
+                raise SystemExit(f"heat2d: --{k.replace('_', '-')} {flag} conflicts with the checkpoint's {k} = {bc[k]}")
+    if bc["bc_x"] == "periodic" and world > 1 and backend == "hip" and a.transport in ("rccl", "peer"):
+        raise SystemExit(f"heat2d: --transport {a.transport} does not pair the first rank with the last: periodic x "
+                         "on more than one rank needs --transport host (or auto)")
+
     if world == 1:
         kinds = ["self"]
     elif backend != "hip":
         kinds = ["torch-dist"]
+    elif bc["bc_x"] == "periodic":
+        kinds = ["torch-dist"]  # the device-direct fabrics refuse the wrap pairing (README: known limits)
     else:
         # auto ends with the host-staged exchange (pinned staging + gloo): the
         # run still completes where neither RCCL nor the IPC mappings attach
@@ -235,7 +255,8 @@ def run(argv=None) -> int:
     edge_shift = 0
     if a.edge_shift not in ("auto", "measure"):
         edge_shift = int(a.edge_shift)
-    elif world >= 3 and (backend == "hip" or a.edge_shift == "measure") and engine == "tb":
+    elif world >= 3 and (backend == "hip" or a.edge_shift == "measure") and engine == "tb" and \
+            bc["bc_x"] != "periodic":  # (periodic x: no edge slabs)
         edge_shift = _measure_edge_shift(prob, a, rank, world, local, backend, kinds[0], engine, arith,
                                          min(nsteps, 48), root and not a.quiet)
 
@@ -243,7 +264,7 @@ def run(argv=None) -> int:
         return HeatSolver(prob, dtype=a.dtype, backend=backend, tb=a.tb, overlap=not a.no_overlap,
                           copy_swap=a.copy_swap, managed=a.managed or var.managed, graph=a.graph, transport=tr,
                           device=local if backend == "hip" else None, engine=engine, arith=arith,
-                          edge_shift=edge_shift)
+                          edge_shift=edge_shift, **bc)
 
     tr, s, kind, fallback = _make_solver(kinds, make_transport, make_solver, world)
     if fallback and root and not a.quiet:
@@ -362,11 +383,12 @@ def _write_inclusive(s, prob, path, world):
     m = prob.n_owned
     T = np.empty((m + 2, m + 2), dtype=full.dtype)
     T[1:-1, 1:-1] = full
-    # frame values: the IC on the frame (kept fixed by the solver)
-    from heat2d.models.reference import initial_field
+    # frame values: the IC on the frame (kept fixed by the solver); on a
+    # periodic axis the wrap images of the owned points
+    from heat2d.models.reference import initial_field, wrap_frame
     frame = initial_field(prob, full.dtype)
     T[0, :], T[-1, :], T[:, 0], T[:, -1] = frame[0, :], frame[-1, :], frame[:, 0], frame[:, -1]
-    io.write_xyz(path, T, prob.x, prob.x)
+    io.write_xyz(path, wrap_frame(T, s.bc_x, s.bc_y), prob.x, prob.x)
 
 
 def _barrier(world):

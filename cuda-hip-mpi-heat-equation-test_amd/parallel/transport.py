@@ -122,7 +122,9 @@ class CallbackTransport(Transport):
     """Transport driven by Python callables on host buffers.
 
     exchange(send_lo, send_hi, recv_lo, recv_hi) receives numpy arrays (or None at the
-    domain ends) of ``k*ncols`` elements; allreduce(vals, op) gets a float64 numpy array
+    domain ends) of ``k*ncols`` elements — with periodic x (``HeatSolver(bc_x="periodic")``)
+    all four on every rank, ``k*(ncols+2)`` elements each (the rows with their two frame
+    columns), the first rank's lower neighbour being the last rank; allreduce(vals, op) gets a float64 numpy array
     to reduce in place (op 0 sum, 1 max, 2 min); barrier() blocks.
     """
 
@@ -180,16 +182,33 @@ class TorchDistTransport(CallbackTransport):
         rank, size = dist.get_rank(group), dist.get_world_size(group)
         self._group = group
 
+        # neighbours modulo size: with periodic x the first rank also has a lower
+        # neighbour (the last rank) and the reverse — the native side then passes
+        # all four buffers on every rank; on 2 ranks both messages go to the same
+        # peer, told apart by their tags
+        lo, hi = (rank - 1) % size, (rank + 1) % size
+
         def exchange(s_lo, s_hi, r_lo, r_hi):
+            if lo == hi and s_lo is not None and s_hi is not None:
+                # periodic x on 2 ranks: both messages go to the one peer — as ONE
+                # message each way (gloo does not keep two tagged messages
+                # between the same pair apart): [first rows | last rows]
+                out, got = torch.from_numpy(np.concatenate([s_lo, s_hi])), torch.empty(2 * len(s_lo), dtype=torch.from_numpy(s_lo).dtype)
+                for w in dist.batch_isend_irecv([dist.P2POp(dist.isend, out, lo, group, self.TAG_DOWN),
+                                                 dist.P2POp(dist.irecv, got, lo, group, self.TAG_DOWN)]):
+                    w.wait()
+                r_hi[:] = got[:len(s_lo)].numpy()  # the peer's first rows: my high ghost rows
+                r_lo[:] = got[len(s_lo):].numpy()  # the peer's last rows: my low ghost rows
+                return
             ops = []
             if s_lo is not None:  # my first rows -> rank-1 (its high ghost rows)
-                ops.append(dist.P2POp(dist.isend, torch.from_numpy(s_lo), rank - 1, group, self.TAG_DOWN))
+                ops.append(dist.P2POp(dist.isend, torch.from_numpy(s_lo), lo, group, self.TAG_DOWN))
             if r_hi is not None:
-                ops.append(dist.P2POp(dist.irecv, torch.from_numpy(r_hi), rank + 1, group, self.TAG_DOWN))
+                ops.append(dist.P2POp(dist.irecv, torch.from_numpy(r_hi), hi, group, self.TAG_DOWN))
             if s_hi is not None:  # my last rows -> rank+1 (its low ghost rows)
-                ops.append(dist.P2POp(dist.isend, torch.from_numpy(s_hi), rank + 1, group, self.TAG_UP))
+                ops.append(dist.P2POp(dist.isend, torch.from_numpy(s_hi), hi, group, self.TAG_UP))
             if r_lo is not None:
-                ops.append(dist.P2POp(dist.irecv, torch.from_numpy(r_lo), rank - 1, group, self.TAG_UP))
+                ops.append(dist.P2POp(dist.irecv, torch.from_numpy(r_lo), lo, group, self.TAG_UP))
             if ops:
                 for w in dist.batch_isend_irecv(ops):
                     w.wait()

@@ -114,6 +114,7 @@ def save(solver, directory: str, step: Optional[int] = None, extra: Optional[dic
             "convention": p.convention,
             "sigma": p.sigma, "nu": p.nu, "dom_len": p.dom_len, "r": p.r,
             "edge_shift": int(getattr(solver, "edge_shift", 0)),
+            "bc_x": getattr(solver, "bc_x", "dirichlet"), "bc_y": getattr(solver, "bc_y", "dirichlet"),
         }
         meta.update(extra or {})
         _write_atomic(os.path.join(sd, "meta.json"), json.dumps(meta, indent=1))
@@ -150,6 +151,9 @@ def load(solver, directory: str) -> dict:
         raise ValueError(f"checkpoint grid {meta['n_owned']} != solver grid {solver.problem.n_owned}")
     if meta["convention"] != solver.problem.convention:
         raise ValueError("checkpoint grid convention differs")
+    for k in ("bc_x", "bc_y"):  # (older saves: dirichlet)
+        if meta.get(k, "dirichlet") != getattr(solver, k, "dirichlet"):
+            raise ValueError(f"checkpoint {k} = {meta.get(k, 'dirichlet')} != solver {k} = {getattr(solver, k, 'dirichlet')}")
     want = "fp64" if solver.np_dtype == np.float64 else "fp32"
     if meta["dtype"] != want:
         raise ValueError(f"checkpoint dtype {meta['dtype']} != solver dtype {want}")
