@@ -405,7 +405,8 @@ def check_timed_field(timed, make_ref: Callable[..., object], steps: int, *, ari
                 finally:
                     ref.close()
                 d = res["max_abs_diff"]
-                diff = d if (d != d or diff != diff) else max(diff, d)
+                # a NaN from any window sticks (a later finite window must not clear it)
+                diff = diff if diff != diff else (d if d != d else max(diff, d))
                 mism += float(res["mismatches"])
                 rows += m
         nan = diff != diff

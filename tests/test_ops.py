@@ -2,6 +2,8 @@
 stats, pack/unpack — and NaN guard bands: every element the kernel must not
 write is pre-filled with NaN and checked afterwards (catches the out-of-bounds
 class of bugs the reference's CUDA kernels have)."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -138,7 +140,22 @@ def test_ops_gpu_matches_cpu(native, gpu):
             a, b = b, a
         outs.append(K.owned(a, L).cpu())
     assert torch.equal(outs[0], outs[1])
-    st = K.stats(outs[0].contiguous().view(-1), K.make_layout(150, 150, halo=0)) if False else None  # noqa
+    # the device statistics of the stepped field, and its difference from the
+    # IC, against math.fsum over the host copy: N u sum|v| for the sum (N terms,
+    # u = 2^-53), (N + 2) u sum v^2 for the squares; min / max / max diff exact
+    ic = torch.empty_like(a)
+    K.init_field(ic, L, p.ic, p.x)
+    st = K.stats(a, L, other=ic)
+    v = outs[0].numpy().astype(np.float64).ravel()
+    d = v - K.owned(ic, L).cpu().numpy().astype(np.float64).ravel()
+    u = 2.0 ** -53
+    assert np.abs(d).max() > 0.0  # the hot spot has diffused
+    assert abs(st["sum"] - math.fsum(v)) <= v.size * u * math.fsum(np.abs(v))
+    assert abs(st["sum_sq"] - math.fsum(v * v)) <= (v.size + 2) * u * math.fsum(v * v)
+    assert st["min"] == v.min() and st["max"] == v.max()
+    assert abs(st["diff_l2"] ** 2 - math.fsum(d * d)) <= (d.size + 2) * u * math.fsum(d * d)
+    assert st["diff_max"] == np.abs(d).max()
+    assert K.stats(a, L, other=ic) == st and K.stats(a.cpu(), L, other=ic.cpu())["min"] == st["min"]
     buf = K.pack_rows(a, L, 0, 4)
     assert torch.equal(buf.view(4, 150).cpu(), K.owned(a, L)[:4].cpu())
     c = torch.empty_like(a)
