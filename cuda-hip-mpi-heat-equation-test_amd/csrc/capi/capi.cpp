@@ -706,6 +706,14 @@ int heat2d_solver_plan_origin(void* s, int k, int32_t* out) {
   return guarded([&] { *out = static_cast<Solver*>(s)->plan_origin(k); });
 }
 
+int heat2d_solver_plan_strip_shape(void* s, int k, int64_t* strip_w, int64_t* useful_w) {
+  return guarded([&] {
+    Solver& sv = *static_cast<Solver*>(s);
+    HEAT2D_REQUIRE(k >= 1 && k <= kMaxTB, "k out of range");
+    kern::plan_strip_shape(sv.dtype(), sv.plan_for(k), strip_w, useful_w);
+  });
+}
+
 int heat2d_autotune_slabs(int64_t n_rows, int64_t n_cols, int nranks, int autotune, int32_t* out) {
   return guarded([&] { *out = autotune_slabs(n_rows, n_cols, nranks, autotune) ? 1 : 0; });
 }

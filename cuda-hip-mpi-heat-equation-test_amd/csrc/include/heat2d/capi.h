@@ -244,6 +244,8 @@ int heat2d_plan_cache_get_schedule(const char* ctx, int64_t n, int32_t* depths, 
 // Where the depth-k split plan came from: 0 planned (not autotuned), 1 autotuned in
 // this process, 2 the plan cache (re-validated), -1 not planned yet.
 int heat2d_solver_plan_origin(void* s, int k, int32_t* out);
+/* strip width and useful width (columns) of the main launch of the depth-k plan */
+int heat2d_solver_plan_strip_shape(void* s, int k, int64_t* strip_w, int64_t* useful_w);
 // Autotune / measured-schedule eligibility of a decomposition (the same on every rank).
 int heat2d_autotune_slabs(int64_t n_rows, int64_t n_cols, int nranks, int autotune, int32_t* out);
 /* the schedule search itself on given cycle times t_ms[k] (k = 1..kmax; t_ms[0] unused): depths in out */

@@ -115,6 +115,7 @@ struct TbRect {
 constexpr int kMaxPlanRects = 6;
 constexpr int32_t kPlanDynamic = 2;  // SplitPlan::flags
 constexpr int32_t kPlanLead = 4;     // SplitPlan::flags (valid = 1)
+constexpr int32_t kPlanPipe = 8;     // SplitPlan::flags (valid = 1 / 3): the main launch is the wave-pair kernel
 struct SplitPlan {
   int32_t k, ring, valid, nedge;
   TbRect main;
@@ -127,7 +128,11 @@ struct SplitPlan {
   // exchanging slabs): the concurrent order with the band launch issued
   // FIRST — its waves take their slots before the interior's, the interior's
   // last-dispatched waves (its one-item waves) start behind them, and the
-  // exchange follows the bands on the comm stream.
+  // exchange follows the bands on the comm stream. flags & kPlanPipe (fp64,
+  // depths with a tb_kernel_pipe instance): the main launch runs the
+  // wave-pair kernel — its rects count WIDE strips (256 columns, 32 B per
+  // lane), its items go to pairs of waves: main_waves counts pairs. The edge
+  // rects keep the one-wave strips.
   int32_t nrects, flags;
   TbRect rects[kMaxPlanRects];
 };
@@ -138,8 +143,19 @@ struct SplitPlan {
 SplitPlan with_edge_bands(DType dt, const SplitPlan& p, int64_t nb, int arith = 0);
 // ring_override: 4 | 6 (0: default); main_bands: MAIN row bands (0: persistent default;
 // < 0: -main_bands segments, TbRect)
+// pipe: plan the main launch for the wave-pair kernel (kPlanPipe; needs pipe_available)
 SplitPlan plan_split(DType dt, const SlabLayout& L, int k, int64_t band, int cus = 0, int spare_waves = 0,
-                     int ring_override = 0, int64_t main_bands = 0, int arith = 0);
+                     int ring_override = 0, int64_t main_bands = 0, int arith = 0, bool pipe = false);
+// Whether the wave-pair interior kernel exists for this dtype, depth and
+// arithmetic form (an instance that keeps 2 waves/SIMD without scratch: fp64,
+// depths 16..24, all four forms).
+bool pipe_available(DType dt, int k, int arith);
+// Strip width and useful width (columns) of a plan's main launch.
+void plan_strip_shape(DType dt, const SplitPlan& p, int64_t* strip_w, int64_t* useful_w);
+// The pair kernel's waits are bounded: a wave that gave up set a status word.
+// Raises if any launch since the last call did, and clears the word (call
+// after a synchronise; the field is invalid from that launch on).
+void pipe_check();
 // The alternative the autotuner weighs against the split (valid = 2): ONE
 // general launch over the whole slab (no edge part), e.g. for small grids
 // where the second launch costs more than it saves.

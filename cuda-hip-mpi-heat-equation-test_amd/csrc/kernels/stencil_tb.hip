@@ -36,10 +36,25 @@
 //     zero centre weight folded away — 3 adds + 2 DPP moves per interior point
 //     and level (levels carried scaled by 4^level, tb_impl.hpp); bitwise equal
 //     to its CPU twin, and to arith 0 on data where sum - 4c is exact.
+//
+// The wave-pair interior kernel (tb_kernel_pipe, tb_pipe_impl.hpp; fp64, all
+// four arithmetic forms, depths 16..24): the deep fp64 interior pass sits at
+// the VALU issue roof, and a one-wave strip cannot widen its lanes past 16 B (the level
+// registers of 20 levels at 32 B per lane do not fit 2 waves/SIMD). There a
+// PAIR of waves marches one 256-column strip: the producer levels 1..K1 from
+// global memory, the consumer levels K1+1..K to global memory, each with half
+// the level registers and 4 doubles per lane (0.65x the lane-instructions per
+// useful point and level at K = 20), coupled one way through an LDS row FIFO
+// with counters — no barrier, no vmcnt drain, every wait bounded. Plans carry
+// kPlanPipe: their main rects count wide strips and their items go to pairs
+// (two per 256-thread workgroup); the boundary bands keep the one-wave
+// kernels. Same operations in the same order per point: bitwise identical.
+// The autotuner times pipe candidates beside the strip candidates
+// (HEAT2D_PIPE=0 off, 1 forced). Measured: profiles/r7/pipe/.
 #include <cmath>
 #include <type_traits>
 
-#include "tb_impl.hpp"
+#include "tb_pipe_impl.hpp"
 
 namespace heat2d {
 namespace kern {
@@ -68,6 +83,26 @@ int halo_cols(DType dt, int k) {
   return (k + v - 1) / v * v;
 }
 int useful_width(DType dt, int k) { return 64 * vec_elems(dt) - 2 * halo_cols(dt, k); }
+// the wave-pair kernel's wide strips (fp64, 4 doubles per lane); must match PipeShape
+int useful_width_pipe(int k) { return 256 - 2 * ((k + 3) / 4 * 4); }
+
+// The pair kernel's status word: host memory every device can write (one per
+// process; allocated when the first pipe plan is made, never during a launch,
+// so graph capture keeps working).
+uint32_t* pipe_status_word(bool create) {
+  static std::mutex mu;
+  static uint32_t* w = nullptr;
+  std::lock_guard<std::mutex> g(mu);
+  if (!w && create) {
+    void* p = nullptr;
+    if (hipHostMalloc(&p, sizeof(uint32_t), hipHostMallocPortable | hipHostMallocMapped) != hipSuccess)
+      fail(__FILE__, __LINE__, "pipe status word: host allocation failed");
+    w = static_cast<uint32_t*>(p);
+    *w = 0u;
+  }
+  return w;
+}
+
 
 // Level-0 row ring per wave (RING - 2 rows in flight; the march loop is
 // unrolled RING times). Override: HEAT2D_TB_RING=4|6.
@@ -247,8 +282,9 @@ int64_t choose_bands(int64_t rows, int64_t ns, int64_t simds, int k, int64_t pri
 // so whatever orders a consumer after this launch orders it after the fill.
 int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
                      const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
-                     double* partials = nullptr, uint32_t* queue = nullptr, int bc = 0) {
+                     double* partials = nullptr, uint32_t* queue = nullptr, int bc = 0, bool pipe = false) {
   HEAT2D_REQUIRE(nrect >= 1 && nrect <= (main ? kMainRects : kMaxRects), "bad rect count");
+  HEAT2D_REQUIRE(!pipe || (main && !partials && pipe_available(dt, k, arith)), "no wave-pair kernel for this launch");
   HEAT2D_REQUIRE((bc & ~(kBcPeriodicX | kBcPeriodicY)) == 0, "bc must be a set of kBcPeriodicX | kBcPeriodicY");
   const SlabLayout L = bc_layout(L0, bc);
   check_layout(dt, L, k);  // (the shifted rows must still fit the march's 32-bit row index)
@@ -283,7 +319,7 @@ int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0,
   a.nitems = items;
   a.nwaves = std::max<int64_t>(1, std::min<int64_t>(nwaves, items));
   a.partials = partials;
-  a.wtimes = wave_times_buf(a.nwaves);
+  a.wtimes = pipe ? nullptr : wave_times_buf(a.nwaves);  // (the pair kernel records no wave times)
   if (arith == 3) {  // scaled levels (tb_impl.hpp AR 3): coefficients of this depth, in double
     HEAT2D_REQUIRE(r > 0.0, "arith 3 (fast) needs r > 0");
     a.fb = (1.0 - 4.0 * r) / r;
@@ -295,7 +331,14 @@ int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0,
   a.queue = (queue && !partials && items > a.nwaves) ? queue : nullptr;
   const unsigned nblocks = (unsigned)((a.nwaves + 3) / 4);
   const int64_t o = L.origin();
-  if (partials) {
+  if (pipe) {  // a.nwaves counts pairs: two per 256-thread workgroup
+    uint32_t* status = pipe_status_word(false);
+    HEAT2D_REQUIRE(status, "pipe plan launched without its status word");
+    with_ar(arith, [&](auto ar) {
+      dispatch_pipe<decltype(ar)::value>(k, (unsigned)((a.nwaves + 1) / 2), static_cast<const double*>(src) + o,
+                                         static_cast<double*>(dst) + o, a, r, status, stream);
+    });
+  } else if (partials) {
     HEAT2D_REQUIRE(a.nwaves <= max_stats_waves(), "statistics partials buffer too small");
     const float* s32 = static_cast<const float*>(src) + o;
     const double* s64 = static_cast<const double*>(src) + o;
@@ -540,20 +583,28 @@ void weight_main(DType dt, const SlabLayout& L, SplitPlan& p, int arith, int64_t
 }
 
 SplitPlan plan_split(DType dt, const SlabLayout& L, int k, int64_t band, int cus, int spare_waves,
-                     int ring_override, int64_t main_bands, int arith) {
+                     int ring_override, int64_t main_bands, int arith, bool pipe) {
   check_layout(dt, L, k);
   SplitPlan p{};
   p.k = k;
   p.ring = ring_ok(dt, k, (ring_override == 4 || ring_override == 6) ? ring_override : default_ring(dt, k));
   const int64_t n = L.nrows, B = std::max<int64_t>(band, k);
   const int64_t U = useful_width(dt, k);
-  const int64_t ns = (L.ncols + U - 1) / U;
+  const int64_t ns_e = (L.ncols + U - 1) / U;  // one-wave strips (the boundary bands)
   const int64_t rows_m = n - 2 * B;
   if (rows_m < 4 * k) return p;  // valid = 0: too thin to split
-  // MAIN: the interior rows, all strips, persistent (one item per resident wave)
-  const int bpc = occupancy(dt, p.ring, true, k, arith);
-  const int64_t slots = (int64_t)(cus > 0 ? cus : cu_count()) * bpc * 4;
-  const int64_t mw = std::max<int64_t>(4, slots - std::max(0, spare_waves));
+  if (pipe) {
+    HEAT2D_REQUIRE(pipe_available(dt, k, arith), "no wave-pair kernel for this dtype, depth and arithmetic");
+    (void)pipe_status_word(true);
+    p.flags |= kPlanPipe;
+  }
+  // MAIN: the interior rows, all strips, persistent (one item per resident
+  // wave; pipe: wide strips, one item per resident PAIR — two per workgroup)
+  const int64_t ns = pipe ? (L.ncols + useful_width_pipe(k) - 1) / useful_width_pipe(k) : ns_e;
+  const int bpc = pipe ? std::max(1, with_ar(arith, [&](auto ar) { return occupancy_blocks_pipe<decltype(ar)::value>(k); }))
+                       : occupancy(dt, p.ring, true, k, arith);
+  const int64_t slots = (int64_t)(cus > 0 ? cus : cu_count()) * bpc * (pipe ? 2 : 4);
+  const int64_t mw = std::max<int64_t>(pipe ? 2 : 4, slots - std::max(0, pipe ? (spare_waves + 1) / 2 : spare_waves));
   // the fp32 interior kernel skips unneeded priming levels (tb_impl.hpp run<PS>)
   int64_t nb_m = choose_bands(rows_m, ns, dt == DType::F32 ? balance_units(dt, cus, bpc) : mw, k,
                               dt == DType::F32 ? std::max(1, k - 1) : -1);
@@ -567,10 +618,10 @@ SplitPlan plan_split(DType dt, const SlabLayout& L, int k, int64_t band, int cus
   // (B + 2k march rows per item): beside MAIN where wave slots allow, else
   // right after it — either way the halo exchange that follows overlaps the
   // NEXT cycle's MAIN, which does not wait for it.
-  p.edge[0] = TbRect{0, B, 0, ns, 1};
-  p.edge[1] = TbRect{n - B, n, 0, ns, 1};
+  p.edge[0] = TbRect{0, B, 0, ns_e, 1};
+  p.edge[1] = TbRect{n - B, n, 0, ns_e, 1};
   p.nedge = 2;
-  p.edge_items = 2 * ns;
+  p.edge_items = 2 * ns_e;
   const int bpc_e = occupancy(dt, p.ring, false, k, arith);
   p.edge_waves = std::min<int64_t>(p.edge_items, (int64_t)cu_count() * bpc_e * 4);
   p.valid = 1;
@@ -610,6 +661,24 @@ SplitPlan plan_single(DType dt, const SlabLayout& L, int k, int cus, int ring_ov
   p.nedge = 0;
   p.valid = 2;
   return p;
+}
+
+bool pipe_available(DType dt, int k, int arith) {
+  return dt == DType::F64 && arith >= 0 && arith <= 3 && k >= kPipeMinK && k <= kPipeMaxK;
+}
+
+void plan_strip_shape(DType dt, const SplitPlan& p, int64_t* strip_w, int64_t* useful_w) {
+  const bool pipe = (p.flags & kPlanPipe) != 0;
+  *strip_w = pipe ? 256 : 64 * vec_elems(dt);
+  *useful_w = pipe ? useful_width_pipe(p.k) : useful_width(dt, p.k);
+}
+
+void pipe_check() {
+  uint32_t* w = pipe_status_word(false);
+  if (w && *static_cast<volatile uint32_t*>(w) != 0u) {
+    *static_cast<volatile uint32_t*>(w) = 0u;  // reported once: later launches start clean
+    fail(__FILE__, __LINE__, "wave-pair kernel: a FIFO wait timed out (results are invalid)");
+  }
 }
 
 int64_t wave_times(uint64_t* out, int64_t max_waves) {
@@ -683,7 +752,8 @@ void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, con
     return;
   }
   if (main_part)
-    launch_rects(dt, src, dst, L, p.k, p.ring, true, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc);
+    launch_rects(dt, src, dst, L, p.k, p.ring, true, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc,
+                 (p.flags & kPlanPipe) != 0);
   else
     launch_rects(dt, src, dst, L, p.k, p.ring, edges_on_main(bc_layout(L, bc), p.k, p.edge, p.nedge), p.edge, p.nedge,
                  p.edge_waves, r, stream, arith, nullptr, nullptr, bc);

@@ -528,6 +528,8 @@ void Solver::phase_times(double out[5]) {
   for (double& v : phase_acc_) v = 0.0;
 }
 
+static int pipe_mode();  // HEAT2D_PIPE (below)
+
 const kern::SplitPlan& Solver::split_plan(int k) {
   kern::SplitPlan& p = split_[k];
   if (p.k != k) {
@@ -561,6 +563,21 @@ const kern::SplitPlan& Solver::split_plan(int k) {
         p.k = k;
       }
     }
+    // HEAT2D_PIPE=1: the interior on the wave-pair kernel wherever it exists
+    if (pipe_mode() == 1 && p.valid && !(p.flags & kern::kPlanPipe) && hip_ &&
+        kern::pipe_available(dtype(), k, cfg_.arith) && !(p.valid == 2 && tr_->exchanges())) {
+      kern::SplitPlan q = kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, p.valid == 2 ? 0 : p.ring, 0,
+                                           cfg_.arith, true);
+      if (q.valid) {
+        if (p.valid != 2) {
+          q.valid = p.valid;
+          q.flags |= p.flags;
+          if (p.nedge > 0 && p.edge[0].nb > 1) q = kern::with_edge_bands(dtype(), q, p.edge[0].nb, cfg_.arith);
+        }
+        q.k = k;
+        p = q;
+      }
+    }
     // HEAT2D_SEGMENTS=n / HEAT2D_BANDS=n re-plan the interior (or the single
     // launch) as n segment work items / n row bands, keeping the order and ring
     // (tests, A/B)
@@ -570,8 +587,9 @@ const kern::SplitPlan& Solver::split_plan(int k) {
       const int64_t nseg = env_seg ? std::atoll(env_seg) : -std::atoll(env_bands);  // < 0: bands
       if (nseg != 0 && p.valid) {
         const int valid = p.valid, ring = p.ring;
+        const bool pipe = (p.flags & kern::kPlanPipe) != 0;
         p = valid == 2 ? kern::plan_single(dtype(), Lk_, k, compute_cus_, ring, -nseg, cfg_.arith)
-                       : kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, ring, -nseg, cfg_.arith);
+                       : kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, ring, -nseg, cfg_.arith, pipe);
         if (p.valid) p.valid = valid;
         p.k = k;
       }
@@ -597,7 +615,7 @@ const kern::SplitPlan& Solver::split_plan_banded(int k, int64_t B) {
   // the same choice (order, ring, interior bands / segments) over the interior
   // left between B-row bands; too thin for that: valid = 0 (serial cycle)
   kern::SplitPlan d = kern::plan_split(dtype(), Lk_, k, B, compute_cus_, spare_waves(), base.ring, base.main.nb,
-                                       cfg_.arith);
+                                       cfg_.arith, (base.flags & kern::kPlanPipe) != 0);
   if (d.valid) {
     if (base.nedge > 0 && base.edge[0].nb > 1) d = kern::with_edge_bands(dtype(), d, base.edge[0].nb, cfg_.arith);
     d.flags = base.flags;
@@ -646,6 +664,18 @@ static bool dynamic_candidates() {
     return !e || std::atoi(e) != 0;
   }();
   return on;
+}
+
+// Wave-pair interior kernel (kern::kPlanPipe; fp64 depths with an instance):
+// HEAT2D_PIPE unset: the autotuner times pipe candidates beside the strip
+// candidates and keeps whichever is faster; 0: never; 1: every split plan that
+// can runs it (tests, A/B).
+static int pipe_mode() {
+  static const int m = [] {
+    const char* e = std::getenv("HEAT2D_PIPE");
+    return !e ? -1 : (std::atoi(e) != 0 ? 1 : 0);
+  }();
+  return m;
 }
 
 // The first cycle of a step() call on an exchanging slab runs in the lead
@@ -726,7 +756,7 @@ float Solver::time_plan(const kern::SplitPlan& c, int kTimed) {
 static uint64_t plan_env_hash() {
   static const uint64_t h = [] {
     uint64_t v = 1469598103934665603ull;
-    for (const char* name : {"HEAT2D_DYNAMIC", "HEAT2D_TB_RING",
+    for (const char* name : {"HEAT2D_DYNAMIC", "HEAT2D_PIPE", "HEAT2D_TB_RING",
                              "HEAT2D_SPLIT_ORDER", "HEAT2D_SEGMENTS", "HEAT2D_BANDS", "HEAT2D_MAX_WAVES",
                              "HEAT2D_EDGE_BANDS", "HEAT2D_GRAPH_MAX_CYCLE_US"}) {
       const char* e = std::getenv(name);
@@ -767,8 +797,11 @@ bool Solver::cached_split(int k) {
   float ms = 0.f;
   if (!plancache::get_plan(cache_ctx(), k, k, &c, &ms) || ms <= 0.f) return false;
   // geometry must match this slab (defensive: the key already pins it)
+  if ((c.flags & kern::kPlanPipe) &&
+      (pipe_mode() == 0 || c.valid == 2 || !kern::pipe_available(dtype(), k, cfg_.arith)))
+    return false;
   const kern::SplitPlan fresh = kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare_waves(), c.ring,
-                                                 c.main.nb, cfg_.arith);
+                                                 c.main.nb, cfg_.arith, (c.flags & kern::kPlanPipe) != 0);
   if (!c.valid || (c.valid != 2 && !fresh.valid) || c.main.r1 > L_.nrows || c.nedge > 4) return false;
   // semantic checks on top of the key: a plan kind this run may not use
   // (the dynamic queue is off under HEAT2D_DYNAMIC=0; a single launch cannot
@@ -865,12 +898,14 @@ void Solver::autotune_split(int k) {
       if (nk < 1 || nk > kMaxTB || (plan_origin_[nk] != 1 && plan_origin_[nk] != 2)) continue;
       const kern::SplitPlan& q = split_[nk];
       if (q.k != nk || !q.valid) continue;
+      const bool qpipe = (q.flags & kern::kPlanPipe) && kern::pipe_available(dtype(), k, cfg_.arith);
       kern::SplitPlan c = q.valid == 2
                               ? kern::plan_single(dtype(), Lk_, k, compute_cus_, q.ring, q.main.nb, cfg_.arith)
-                              : kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, q.ring, q.main.nb, cfg_.arith);
+                              : kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, q.ring, q.main.nb, cfg_.arith,
+                                                 qpipe);
       if (!c.valid) continue;
       c.valid = q.valid;
-      c.flags = q.flags;
+      c.flags = (q.flags & ~kern::kPlanPipe) | (c.flags & kern::kPlanPipe);
       if ((c.valid == 1 || c.valid == 3) && q.nedge > 0 && q.edge[0].nb > 1)
         c = kern::with_edge_bands(dtype(), c, q.edge[0].nb, cfg_.arith);
       const float t = time_plan(c, 2);
@@ -970,6 +1005,44 @@ void Solver::autotune_split(int k) {
       }
     }
   }
+  // The wave-pair interior kernel (fp64 depths with an instance): the same
+  // band / segment families over its wide strips, items per PAIR of waves,
+  // in the split orders (the boundary bands keep the one-wave strips).
+  if (pipe_mode() != 0 && best.valid != 2 && kern::pipe_available(dtype(), k, cfg_.arith)) {
+    const kern::SplitPlan p0 = kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, best.ring, 0, cfg_.arith, true);
+    if (p0.valid) {
+      for (int mode : {1, 3}) {
+        if (mode == 3 && (single_ok || best.valid != 1 || base_ms < kEdgeFirstMinCycleMs)) continue;
+        if (mode == 1 && best.valid == 3) continue;
+        for (double f : factors) {
+          const int64_t nb = std::max<int64_t>(1, (int64_t)(p0.main.nb * f + 0.5));
+          kern::SplitPlan c = kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, best.ring, nb, cfg_.arith, true);
+          if (!c.valid) continue;
+          c.valid = mode == 3 ? 3 : best.valid;
+          c.flags |= best.flags & kern::kPlanLead;
+          c.main_waves = std::min<int64_t>(c.main_items, std::max<int64_t>(c.main_waves, p0.main_waves));
+          add(c);
+        }
+        std::vector<int64_t> segs;
+        for (double f : long_cycles ? std::vector<double>{1.0} : std::vector<double>{1.0, 2.0})
+          segs.push_back(std::max<int64_t>(1, (int64_t)(p0.main_waves * f + 0.5)));
+        if (dynamic_candidates()) segs.push_back(4 * p0.main_waves);
+        for (int64_t nseg : segs) {
+          kern::SplitPlan c = kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, best.ring, -nseg, cfg_.arith, true);
+          if (!c.valid) continue;
+          c.valid = mode == 3 ? 3 : best.valid;
+          c.flags |= best.flags & kern::kPlanLead;
+          add(c);
+        }
+      }
+      if (pipe_mode() == 1) {  // forced: only the pipe candidates compete
+        std::vector<kern::SplitPlan> only;
+        for (const auto& c : cands)
+          if (c.flags & kern::kPlanPipe) only.push_back(c);
+        if (!only.empty()) cands.swap(only);
+      }
+    }
+  }
   // screening: (cycles per trial, candidates kept) per stage; stage A times
   // short cycles over up to 4 (a single ~50 us cycle is noisy; they are cheap)
   using Stage = std::pair<int, size_t>;
@@ -989,9 +1062,10 @@ void Solver::autotune_split(int k) {
     std::stable_sort(timed.begin(), timed.end(), [](const Timed& x, const Timed& y) { return x.score < y.score; });
     if (tune_log())
       for (const auto& t : timed)
-        std::fprintf(stderr, "heat2d tune k=%d cycles=%d: order %d ring %d bands %lld items %lld waves %lld dyn %d ms %.4f score %.4f\n",
+        std::fprintf(stderr, "heat2d tune k=%d cycles=%d: order %d ring %d bands %lld items %lld waves %lld dyn %d pipe %d ms %.4f score %.4f\n",
                      k, st.first, t.plan.valid, t.plan.ring, (long long)t.plan.main.nb, (long long)t.plan.main_items,
-                     (long long)t.plan.main_waves, (t.plan.flags & kern::kPlanDynamic) ? 1 : 0, t.ms, t.score);
+                     (long long)t.plan.main_waves, (t.plan.flags & kern::kPlanDynamic) ? 1 : 0,
+                     (t.plan.flags & kern::kPlanPipe) ? 1 : 0, t.ms, t.score);
     timed.resize(std::min(timed.size(), st.second));
   }
   best = timed.front().plan;
@@ -1764,6 +1838,7 @@ void Solver::synchronize() {
     H2D_HIP(hipStreamSynchronize(s_compute_));
     if (s_comm_ != s_compute_) H2D_HIP(hipStreamSynchronize(s_comm_));
     tr_->check();
+    kern::pipe_check();
     return;
   }
   // Exchanging ranks poll both streams, so that a transport abort (its
@@ -1785,6 +1860,7 @@ void Solver::synchronize() {
     if (s_comm_ == s_compute_) break;
   }
   tr_->check();
+  kern::pipe_check();
 }
 
 void Solver::step_stats(int64_t n, double out[6]) {

@@ -47,7 +47,11 @@ def _plan(h, k: int) -> dict:
     p, ms, org = N.SplitPlan(), C.c_float(), C.c_int32()
     N.call("heat2d_solver_plan", h, int(k), C.byref(p), C.byref(ms))
     N.call("heat2d_solver_plan_origin", h, int(k), C.byref(org))
-    return {"k": p.k, "ring": p.ring, "valid": p.valid,
+    # flags & 8: the interior runs the wave-pair kernel on wide strips; the
+    # strip shape of the main launch comes from the library either way
+    sw, uw = C.c_int64(), C.c_int64()
+    N.call("heat2d_solver_plan_strip_shape", h, int(k), C.byref(sw), C.byref(uw))
+    return {"main_strip_w": sw.value, "main_useful_w": uw.value, "pipe": int((p.flags >> 3) & 1), "k": p.k, "ring": p.ring, "valid": p.valid,
             "order": ("lead" if p.valid == 1 and p.flags & 4 else
                       {1: "concurrent", 2: "single", 3: "edge-first"}.get(p.valid, "serial")),
             "dynamic": int((p.flags >> 1) & 1), "origin": PLAN_ORIGINS.get(org.value, "?"),

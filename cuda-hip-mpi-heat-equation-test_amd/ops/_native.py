@@ -239,6 +239,7 @@ _SIGS = {
     "heat2d_plan_cache_get_schedule": (C.c_int, [C.c_char_p, _I64, C.POINTER(C.c_int32), _I64,
                                                  C.POINTER(C.c_int64)]),
     "heat2d_solver_plan_origin": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32)]),
+    "heat2d_solver_plan_strip_shape": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 _lib = None

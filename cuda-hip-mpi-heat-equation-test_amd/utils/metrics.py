@@ -43,18 +43,29 @@ def plan_hbm_bytes(plan: dict, dtype_bytes: int, nrows: int, ncols: int) -> dict
     included) and stores its useful U columns once. This counts no cache reuse
     between neighbouring strips / bands (rocprof measured 1.13-1.19x the field
     read per pass vs this model's W/U, profiles/hbm_model_check.md), so it is
-    an upper bound on the reads."""
+    an upper bound on the reads. A plan whose interior runs the wave-pair kernel
+    carries its own strip width (main_strip_w: wide strips, counted by
+    main_rect); the boundary bands keep the one-wave strips. A wide strip's
+    2 KiB row starts at an unaligned column and neighbouring strips share only
+    40-48 of its 256 columns, so little of it is re-read from the L2: the
+    model counts one more 128-B line per row there, which keeps it above the
+    measured reads (32768^2 fp64 K = 20: 1.232x the field measured, 1.229x
+    without the line, 1.306x with it; profiles/r7/pipe/)."""
     k = int(plan["k"])
     w, u = strip_geometry(dtype_bytes, k)
+    wm = w
+    if plan.get("pipe"):
+        wm = int(plan["main_strip_w"]) + 128 // dtype_bytes
     rects = [plan["main_rect"]] + list(plan.get("edge_rects", [])) if plan.get("valid", 0) else []
     if not rects:  # unsplit launch over the whole slab (one band per strip)
         nstrips = (ncols + u - 1) // u
         rects = [[0, nrows, 0, nstrips, 1]]
+        wm = w
     rd = 0.0
-    for r0, r1, s0, s1, nb in rects:
+    for i, (r0, r1, s0, s1, nb) in enumerate(rects):
         if r1 <= r0 or s1 <= s0:
             continue
-        rd += float((r1 - r0) * (s1 - s0) + 2 * k * work_pieces(r1 - r0, s1 - s0, nb)) * w * dtype_bytes
+        rd += float((r1 - r0) * (s1 - s0) + 2 * k * work_pieces(r1 - r0, s1 - s0, nb)) * (wm if i == 0 else w) * dtype_bytes
     wr = float(nrows) * ncols * dtype_bytes
     return {"read": rd, "write": wr, "total": rd + wr}
 

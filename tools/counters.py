@@ -30,7 +30,9 @@ def window(d):
     for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
         kt += list(csv.DictReader(open(f)))
     if kt:
-        kern = sorted({(r["Kernel_Name"].split("tb_kernel<")[1].split(">")[0], r["VGPR_Count"],
+        # (tb_kernel<...>, or the wave-pair kernel tb_kernel_pipe<K, AR>: "pipe: K, AR")
+        kern = sorted({(r["Kernel_Name"].split("tb_kernel", 1)[1].split(">")[0].replace("_pipe<", "pipe: ").lstrip("<"),
+                        r["VGPR_Count"],
                         r.get("Accum_VGPR_Count", ""), r["Grid_Size_X"])
                        for r in kt if "tb_kernel" in r["Kernel_Name"]})
         info["kernels"] = [{"template": t, "vgpr": v, "agpr": a, "grid_threads": g} for t, v, a, g in kern][-4:]

@@ -65,6 +65,7 @@ def kernels(so_path):
                 regs = ((vg + 7) // 8) * 8
                 out.append({"name": name, "triple": triple, "vgpr": vg, "agpr": ag,
                             "sgpr": field("sgpr_count"), "scratch": field("private_segment_fixed_size"),
+                            "lds": field("group_segment_fixed_size"),
                             "waves_per_simd": min(8, 512 // max(regs, 1))})
     return out
 
@@ -83,6 +84,16 @@ def tb_params(mangled):
     return p + ({"1": "stats"}.get(var, "var" + var),) if var != "0" else p
 
 
+# the wave-pair interior kernel (tb_pipe_impl.hpp): tb_kernel_pipe<K, AR>, fp64
+_PIPE = re.compile(r"tb_kernel_pipeILi(\d+)ELi(\d+)E")
+
+
+def pipe_params(mangled):
+    """(K, AR) of a tb_kernel_pipe instance, or None."""
+    m = _PIPE.search(mangled)
+    return (int(m.group(1)), int(m.group(2))) if m else None
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     filt = "tb_kernel"
@@ -97,6 +108,9 @@ def main():
         p = tb_params(k["name"])
         tag = (f"tb_kernel<{p[0]}, NV={p[1]}, K={p[2]:2d}, RING={p[3]}, {'main' if p[4] else 'gen '}, "
                f"{('exact', 'fma', 'jacobi', 'fast')[p[5]]}{', ' + p[6] if len(p) > 6 else ''}>") if p else k["name"][:60]
+        q = pipe_params(k["name"])
+        if q:
+            tag = f"tb_kernel_pipe<K={q[0]:2d}, {('exact', 'fma', 'jacobi', 'fast')[q[1]]}> lds {k['lds']}"
         print(f"{tag:55s} vgpr {k['vgpr']:3d} agpr {k['agpr']:3d} scratch {k['scratch']:4d} "
               f"waves/SIMD {k['waves_per_simd']}")
 
