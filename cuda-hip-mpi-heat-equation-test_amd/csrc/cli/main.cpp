@@ -79,7 +79,7 @@ struct Args {
   bool share_gpu = false;          // --share-gpu: every rank on device 0 (peer transport; tests / rehearsals)
   int autotune = -1;               // --autotune auto|on|off (SolverConfig::autotune)
   int edge_shift = 0;              // --edge-shift N: rows each edge slab gives the middle ones (>= 3 ranks)
-  // --bc-x / --bc-y dirichlet|periodic (SolverConfig::bc_x / bc_y; x = rows, decomposed over ranks).
+  // --bc-x / --bc-y dirichlet|periodic|insulated (SolverConfig::bc_x / bc_y; x = rows, decomposed over ranks).
   // Empty: not given — dirichlet, or a restart's checkpointed setting
   std::string bc_x, bc_y;
 };
@@ -93,7 +93,7 @@ void usage() {
       "              [--time-transfers]\n"
       "              [--checkpoint DIR [--checkpoint-every N]] [--restart DIR]\n"
       "              [--transport auto|rccl|peer] [--share-gpu] [--autotune auto|on|off] [--edge-shift N]\n"
-      "              [--bc-x dirichlet|periodic] [--bc-y dirichlet|periodic]\n");
+      "              [--bc-x dirichlet|periodic|insulated] [--bc-y dirichlet|periodic|insulated]\n");
 }
 
 Args parse_args(int argc, char** argv) {
@@ -140,8 +140,8 @@ Args parse_args(int argc, char** argv) {
     else if (s == "--share-gpu") a.share_gpu = true;
     else if (s == "--bc-x" || s == "--bc-y") {
       const std::string v = need(s.c_str());
-      if (v != "dirichlet" && v != "periodic") {
-        std::fprintf(stderr, "%s must be dirichlet or periodic\n", s.c_str());
+      if (v != "dirichlet" && v != "periodic" && v != "insulated") {
+        std::fprintf(stderr, "%s must be dirichlet, periodic or insulated\n", s.c_str());
         std::exit(2);
       }
       (s == "--bc-x" ? a.bc_x : a.bc_y) = v;
@@ -216,8 +216,9 @@ void save_checkpoint(Shared& sh, Solver& s, Transport& tr, int rank, int64_t ste
     m.dom_len = sh.in.dom_len;
     m.r = sh.prob.r;
     m.edge_shift = s.config().edge_shift;  // (0 with periodic x: no edge slabs)
-    m.bc_x = s.config().bc_x ? "periodic" : "dirichlet";
-    m.bc_y = s.config().bc_y ? "periodic" : "dirichlet";
+    const char* const bc_names[3] = {"dirichlet", "periodic", "insulated"};
+    m.bc_x = bc_names[s.config().bc_x];
+    m.bc_y = bc_names[s.config().bc_y];
     ckpt::write_meta(a.checkpoint, name, m);
   }
   tr.barrier();
@@ -302,8 +303,9 @@ void run_rank(Shared& sh, int rank) {
       bc_x = m0.bc_x;
       bc_y = m0.bc_y;
     }
-    cfg.bc_x = bc_x == "periodic" ? 1 : 0;
-    cfg.bc_y = bc_y == "periodic" ? 1 : 0;
+    auto bc_code = [](const std::string& v) { return v == "periodic" ? kBcPeriodic : v == "insulated" ? kBcInsulated : kBcDirichlet; };
+    cfg.bc_x = bc_code(bc_x);
+    cfg.bc_y = bc_code(bc_y);
     if (a.engine != "tb" && a.engine != "jit") fail(__FILE__, __LINE__, "--engine must be tb or jit");
     cfg.engine = a.engine == "jit" ? 1 : 0;  // jit: hipRTC kernel rendered for this slab (python/cuda/cuda.py)
     if (a.arith != "exact" && a.arith != "fma" && a.arith != "jacobi" && a.arith != "fast" && a.arith != "auto")

@@ -89,14 +89,30 @@ void wrap_cols_impl(T* f, const SlabLayout& L, int64_t r0, int64_t r1) {
   }
 }
 
+template <typename T>
+void ins_cols_impl(T* f, const SlabLayout& L, int64_t r0, int64_t r1) {
+  for (int64_t i = r0; i < r1; ++i) {
+    T* row = f + L.offset(i, 0);
+    row[-1] = row[0];
+    row[L.ncols] = row[L.ncols - 1];
+  }
+}
+
 // bc (kernels.hpp kBcPeriodicX / kBcPeriodicY), as the device march: periodic
 // x pins no row, periodic y pins no column — level s is computed over the
 // ghost columns [-(k - s), ncols + (k - s)) too, from level-0 wrap images k
 // columns deep, and the ghost columns of the rows written are refreshed.
+// kBcInsulatedX / kBcInsulatedY: at a point next to an insulated wall the
+// operand from beyond the wall is the point's own value, at every level (the
+// device march's substitution, tb_impl.hpp March INS) — here by giving the
+// frame entry beside it that value before each level reads it; the frame
+// images of the rows written are refreshed.
 template <typename T>
 void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re, int k, T r, int arith, int bc) {
   const SlabLayout L = kern::bc_layout(L0, bc & kern::kBcPeriodicX);  // (the columns: free_cols below)
   const bool free_cols = (bc & kern::kBcPeriodicY) != 0;
+  const bool ins_x = (bc & kern::kBcInsulatedX) != 0, ins_y = (bc & kern::kBcInsulatedY) != 0;
+  HEAT2D_REQUIRE(!(ins_x && (bc & kern::kBcPeriodicX)) && !(ins_y && free_cols), "an axis is periodic or insulated, not both");
   if (free_cols) HEAT2D_REQUIRE(L.ncols >= kern::kWrapCols, "periodic y needs at least kWrapCols (24) owned columns");
   const int64_t R = re - rb + 2 * k;  // level-0 rows [rb-k, re+k)
   const int64_t P = L.pitch;
@@ -111,6 +127,17 @@ void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re,
                      : arith == 1 ? (host_has_fma() ? &row_fma_hw<T> : &row_fma_sw<T>)
                                   : &row_exact<T>;
   for (int s = 1; s <= k; ++s) {
+    // insulated walls: level s - 1 rows [s - 1, R - s + 1) are read
+    if (ins_y)
+      for (int64_t li = s - 1; li < R - s + 1; ++li) {
+        a[li * P + c - 1] = a[li * P + c];
+        a[li * P + c + L.ncols] = a[li * P + c + L.ncols - 1];
+      }
+    if (ins_x)  // (after the columns; whole padded rows: periodic y's ghost columns too)
+      for (const int64_t w : {fixed_lo - 1, fixed_hi}) {
+        const int64_t li = w - (rb - k), from = w < fixed_lo ? li + 1 : li - 1;
+        if (li >= s - 1 && li < R - s + 1 && from >= 0 && from < R) std::memcpy(a + li * P, a + from * P, sizeof(T) * (size_t)P);
+      }
     parallel_rows(s, R - s, [&](int64_t lb, int64_t le) {
       for (int64_t li = lb; li < le; ++li) {
         const int64_t row = rb - k + li;  // local slab row
@@ -131,6 +158,13 @@ void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re,
   for (int64_t i = rb; i < re; ++i)
     std::memcpy(dst + L.offset(i, 0), a + (i - rb + k) * P + c, sizeof(T) * (size_t)L.ncols);
   if (free_cols) wrap_cols_impl(dst, L, rb, re);
+  if (ins_y) ins_cols_impl(dst, L, rb, re);
+  if (ins_x) {
+    const size_t rowb = sizeof(T) * (size_t)P;
+    if (L.row0 == 0 && rb <= 0 && re > 0) std::memcpy(dst + L.offset(-1, -L.cpad), dst + L.offset(0, -L.cpad), rowb);
+    if (L.row0 + L.nrows == L.nrows_global && rb < L.nrows && re >= L.nrows)
+      std::memcpy(dst + L.offset(L.nrows, -L.cpad), dst + L.offset(L.nrows - 1, -L.cpad), rowb);
+  }
 }
 
 template <typename T>
@@ -216,6 +250,8 @@ void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_b
   // arith 3 (the device kernels' scaled levels, tb_impl.hpp) is not bitwise
   // reproducible across launch plans; the CPU twin runs its unscaled
   // contracted form (arith 1), within the same stated bound of exact
+  HEAT2D_REQUIRE(arith != 3 || !(bc & (kern::kBcInsulatedX | kern::kBcInsulatedY)),
+                 "insulated boundaries have no arith 3 (fast) kernels");
   if (arith == 3) arith = 1;
   if (row_end <= row_begin) return;
   if (dt == DType::F32)
@@ -245,6 +281,22 @@ void wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r
   HEAT2D_REQUIRE(L.ncols >= kern::kWrapCols, "periodic y needs at least kWrapCols (24) owned columns");
   if (dt == DType::F32) wrap_cols_impl<float>(static_cast<float*>(field), L, r0, r1);
   else wrap_cols_impl<double>(static_cast<double*>(field), L, r0, r1);
+}
+
+void ins_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1) {
+  if (r1 <= r0) return;
+  HEAT2D_REQUIRE(r0 >= -L.halo && r1 <= L.nrows + L.halo, "ins_cols: rows outside the allocation");
+  if (dt == DType::F32) ins_cols_impl<float>(static_cast<float*>(field), L, r0, r1);
+  else ins_cols_impl<double>(static_cast<double*>(field), L, r0, r1);
+}
+
+void ins_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool hi) {
+  HEAT2D_REQUIRE(L.halo >= 1 && L.nrows >= 1, "ins_rows: no room for the frame rows");
+  const size_t es = dtype_size(dt), bytes = (size_t)L.pitch * es;
+  char* base = static_cast<char*>(field);
+  auto row = [&](int64_t i) { return base + (size_t)((i + L.halo) * L.pitch) * es; };
+  if (lo && L.row0 == 0) std::memcpy(row(-1), row(0), bytes);
+  if (hi && L.row0 + L.nrows == L.nrows_global) std::memcpy(row(L.nrows), row(L.nrows - 1), bytes);
 }
 
 void wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k) {

@@ -35,7 +35,7 @@ typedef struct heat2d_config {
   int32_t engine, arith; /* arith: 0 reference rounding, 1 contracted fma, 2 jacobi (r = 1/4) */
   int32_t edge_shift; /* rows each edge slab gives the middle ones (common.hpp decompose) */
   int64_t slab_row0, slab_rows_global; /* 1-rank rehearsal of a middle slab (0: the slab is the grid) */
-  int32_t bc_x, bc_y; /* boundary condition of the row / column axis: 0 dirichlet, 1 periodic */
+  int32_t bc_x, bc_y; /* boundary condition of the row / column axis: 0 dirichlet, 1 periodic, 2 insulated */
 } heat2d_config;
 
 typedef struct heat2d_tb_plan {
@@ -95,7 +95,9 @@ int heat2d_parse_input(const char* text, double* out7);
 int heat2d_tb(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb,
               int64_t re, int k, double r, void* stream, int64_t tile_rows, int arith);
 /* heat2d_tb with boundary conditions: bc = 1 (periodic x: no row pinned) | 2 (periodic y: no
- * column pinned, ghost columns of the rows written refreshed behind the launch) */
+ * column pinned, ghost columns of the rows written refreshed behind the launch) | 4 (insulated x) |
+ * 8 (insulated y): at a point next to an insulated wall the operand from beyond the wall is the
+ * point's own value; the frame images of the rows written are refreshed behind the launch */
 int heat2d_tb_bc(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb,
                  int64_t re, int k, double r, void* stream, int64_t tile_rows, int arith, int bc);
 /* Periodic wrap fills. wrap_cols: 24 ghost columns on each side of rows [r0, r1) from the owned
@@ -165,7 +167,8 @@ int heat2d_solver_sync(void* s);
 int heat2d_solver_stats(void* s, double* out6, int residual);
 int heat2d_solver_download(void* s, void* host, int64_t ld);
 /* the frame-inclusive local field, (nrows + 2) x (ncols + 2): owned points and the frame lines of
-   Dirichlet axes (entries on periodic axes are ignored and become wrap images), then a halo exchange */
+   Dirichlet axes (entries on periodic / insulated axes are ignored and become wrap / edge images), then a
+   halo exchange */
 int heat2d_solver_upload_field(void* s, const void* host, int64_t ld);
 /* any rectangle of the current field, local rows [r0, r1) x columns [c0, c1), ghost / frame included */
 int heat2d_solver_download_region(void* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, void* host, int64_t ld);
@@ -200,7 +203,7 @@ int heat2d_solver_info(void* s, int32_t* tb, int64_t* band, int64_t* steps, void
                        void** stream);
 /* the arithmetic form the solver runs (0 .. 3): cfg.arith with -1 (auto) resolved */
 int heat2d_solver_arith(void* s, int32_t* out);
-/* boundary conditions the solver runs: 0 dirichlet, 1 periodic, per axis */
+/* boundary conditions the solver runs: 0 dirichlet, 1 periodic, 2 insulated, per axis */
 int heat2d_solver_bc(void* s, int32_t* bc_x, int32_t* bc_y);
 
 /* Loopback group: P slabs on one device (or host). */

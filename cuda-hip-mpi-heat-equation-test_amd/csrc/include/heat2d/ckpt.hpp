@@ -18,7 +18,7 @@ struct Meta {
   std::string convention = "ghost";  // ghost | inclusive
   double sigma = 0, nu = 0, dom_len = 0, r = 0;
   int64_t edge_shift = 0;  // the writer's decomposition (common.hpp decompose); absent in older saves: 0
-  std::string bc_x = "dirichlet", bc_y = "dirichlet";  // dirichlet | periodic; absent in older saves: dirichlet
+  std::string bc_x = "dirichlet", bc_y = "dirichlet";  // dirichlet | periodic | insulated; absent in older saves: dirichlet
   std::string dir;  // read_meta: the directory holding this step's files
 };
 

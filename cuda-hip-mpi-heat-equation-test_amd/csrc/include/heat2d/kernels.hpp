@@ -52,7 +52,20 @@ TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end
 //     (level K there is cut off from its wrap neighbours; the straddling lane
 //     adds up to V - 1 pad columns), which the fill overwrites: kWrapCols must
 //     be >= the depth of any pass (kMaxTB) and >= V (4).
-constexpr int kBcPeriodicX = 1, kBcPeriodicY = 2;
+//   kBcInsulatedX / kBcInsulatedY: a zero-flux wall half a cell outside the
+//     first and last owned row / column. The frame entry is the image of the
+//     adjacent owned point (T[-1] = T[0], T[n] = T[n-1]). A mirrored ghost
+//     layer would not give the golden's bits (its points add their operands in
+//     the swapped order), so the layout is the Dirichlet one and the march has
+//     device code of its own: tb_kernel_ins (tb_impl.hpp), in which a point
+//     next to an insulated wall takes its own value for the operand beyond the
+//     wall, at every level. Every launch that would use the general kernel
+//     uses it; with insulated y the frame-column strips of an interior-kernel
+//     launch become rects of it. The launchers refresh the frame images of
+//     the rows they wrote (launch_ins_cols / launch_ins_rows, same stream).
+//     Not with arith 3, nor the fused statistics; an axis is periodic or
+//     insulated, not both.
+constexpr int kBcPeriodicX = 1, kBcPeriodicY = 2, kBcInsulatedX = 4, kBcInsulatedY = 8;
 // ghost columns per side kept as wrap images: the deepest pass (kMaxTB) reads that many
 constexpr int64_t kWrapCols = kMaxTB;
 static_assert(kWrapCols <= kColPad && kWrapCols >= 4, "ghost columns must fit the column padding");
@@ -81,6 +94,12 @@ inline SlabLayout bc_layout(SlabLayout L, int bc) {
 // [0, k) -> [nrows, nrows+k) (periodic x on one rank).
 void launch_wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1, hipStream_t stream);
 void launch_wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k, hipStream_t stream);
+// Insulated frame images. ins_cols: columns -1 <- 0 and ncols <- ncols - 1 of
+// rows [r0, r1) (ghost / frame rows allowed). ins_rows: the whole padded row
+// -1 <- 0 where the slab holds the global first row (lo) and nrows <- nrows - 1
+// where it holds the last (hi); a slab off that edge is left alone.
+void launch_ins_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1, hipStream_t stream);
+void launch_ins_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool hi, hipStream_t stream);
 
 // dst(rows [row_begin,row_end)) = k FTCS steps of src. `src`/`dst` are
 // allocation bases laid out per `L`. Requires k <= L.halo and the k ghost rows

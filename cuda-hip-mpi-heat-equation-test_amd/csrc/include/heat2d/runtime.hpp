@@ -57,13 +57,17 @@ struct SolverConfig {
   int64_t slab_rows_global;
   // Boundary condition per axis: 0 Dirichlet (the frame keeps its values),
   // 1 periodic (the n owned points are the period; frame entries are wrap
-  // images). x is the row axis (decomposed over ranks), y the column axis.
+  // images), 2 insulated (a zero-flux wall half a cell outside the first and
+  // last owned point; frame entries are images of the adjacent owned point).
+  // x is the row axis (decomposed over ranks), y the column axis.
   int32_t bc_x;
   int32_t bc_y;
 };
-// the kernels' bit set (kernels.hpp kBcPeriodicX / kBcPeriodicY) of a config
+constexpr int32_t kBcDirichlet = 0, kBcPeriodic = 1, kBcInsulated = 2;
+// the kernels' bit set (kernels.hpp kBcPeriodicX / ... / kBcInsulatedY) of a config
 inline int config_bc(const SolverConfig& c) {
-  return (c.bc_x ? kern::kBcPeriodicX : 0) | (c.bc_y ? kern::kBcPeriodicY : 0);
+  return (c.bc_x == kBcPeriodic ? kern::kBcPeriodicX : 0) | (c.bc_y == kBcPeriodic ? kern::kBcPeriodicY : 0) |
+         (c.bc_x == kBcInsulated ? kern::kBcInsulatedX : 0) | (c.bc_y == kBcInsulated ? kern::kBcInsulatedY : 0);
 }
 
 // ---------------------------------------------------------------- transports
@@ -244,6 +248,9 @@ void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_b
         int64_t row_end, int k, double r, int arith = 0, int bc = 0);
 void wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1);
 void wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k);
+// insulated frame images (kern::launch_ins_cols / launch_ins_rows)
+void ins_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1);
+void ins_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool hi);
 void init(DType dt, void* field, const SlabLayout& L, const kern::IcParams& ic,
           const double* xcoord, const double* ycoord);
 void stats(DType dt, const void* field, const void* other, const SlabLayout& L, double out[6]);
@@ -497,7 +504,12 @@ class Solver {
   SlabLayout L_{};
   SlabLayout Lk_{};  // kern::bc_layout(L_, bc_): what the planners see (periodic x: a middle slab)
   int bc_ = 0;       // config_bc(cfg_)
-  void wrap_cols_all(void* field);  // periodic y: ghost columns of every allocated row (init, upload, restart)
+  // periodic y: ghost columns of every allocated row; insulated axes: their
+  // frame images (init, upload, restart)
+  void wrap_cols_all(void* field);
+  // the wave-pair interior kernel for depth k in this run (not under insulated
+  // y: its wide frame-column strips are not carved out)
+  bool pipe_ok(int k) const;
   bool hip_ = true;
   void* buf_[2] = {nullptr, nullptr};
   int cur_ = 0;

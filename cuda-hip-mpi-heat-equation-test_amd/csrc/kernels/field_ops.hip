@@ -279,6 +279,19 @@ __global__ __launch_bounds__(256) void wrap_cols_kernel(T* __restrict__ f, SlabL
   }
 }
 
+// Insulated y: the frame columns of rows [r0, r1) as images of the adjacent
+// owned column. One thread per (row, side).
+template <typename T>
+__global__ __launch_bounds__(256) void ins_cols_kernel(T* __restrict__ f, SlabLayout L, int64_t r0, int64_t r1) {
+  const int64_t total = (r1 - r0) * 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+    T* row = f + L.offset(r0 + (t >> 1), 0);
+    if (t & 1) row[L.ncols] = row[L.ncols - 1];
+    else row[-1] = row[0];
+  }
+}
+
 // Periodic x on one rank: whole padded rows [nrows-k, nrows) -> [-k, 0) and
 // [0, k) -> [nrows, nrows+k), 16 B per lane (n16 vectors per block of k rows;
 // k <= nrows: sources and destinations are disjoint).
@@ -404,6 +417,35 @@ void launch_wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, in
   else
     hipLaunchKernelGGL(wrap_cols_kernel<double>, dim3(g), dim3(256), 0, stream, static_cast<double*>(field), L, r0, r1);
   check_launch("wrap_cols");
+}
+
+void launch_ins_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1, hipStream_t stream) {
+  if (r1 <= r0) return;
+  HEAT2D_REQUIRE(r0 >= -L.halo && r1 <= L.nrows + L.halo, "ins_cols: rows outside the allocation");
+  HEAT2D_REQUIRE(L.ncols >= 1 && L.cpad >= 1 && L.col_hi() > L.ncols, "ins_cols: no room for the frame columns");
+  const unsigned g = grid_for((r1 - r0) * 2);
+  if (dt == DType::F32)
+    hipLaunchKernelGGL(ins_cols_kernel<float>, dim3(g), dim3(256), 0, stream, static_cast<float*>(field), L, r0, r1);
+  else
+    hipLaunchKernelGGL(ins_cols_kernel<double>, dim3(g), dim3(256), 0, stream, static_cast<double*>(field), L, r0, r1);
+  check_launch("ins_cols");
+}
+
+void launch_ins_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool hi, hipStream_t stream) {
+  HEAT2D_REQUIRE(L.halo >= 1 && L.nrows >= 1, "ins_rows: no room for the frame rows");
+  const size_t es = dtype_size(dt);
+  HEAT2D_REQUIRE((L.pitch * es) % 16 == 0, "ins_rows: rows must be whole 16-byte vectors");
+  char* base = static_cast<char*>(field);
+  auto row = [&](int64_t i) { return reinterpret_cast<uint4*>(base + (size_t)((i + L.halo) * L.pitch) * es); };
+  const int64_t n16 = (int64_t)((size_t)L.pitch * es / 16);
+  if (lo && L.row0 == 0) {
+    hipLaunchKernelGGL(copy16_kernel, dim3(grid_for(n16)), dim3(256), 0, stream, row(0), row(-1), n16);
+    check_launch("ins_rows");
+  }
+  if (hi && L.row0 + L.nrows == L.nrows_global) {
+    hipLaunchKernelGGL(copy16_kernel, dim3(grid_for(n16)), dim3(256), 0, stream, row(L.nrows - 1), row(L.nrows), n16);
+    check_launch("ins_rows");
+  }
 }
 
 void launch_wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k, hipStream_t stream) {

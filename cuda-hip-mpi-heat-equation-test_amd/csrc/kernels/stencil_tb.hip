@@ -274,18 +274,77 @@ int64_t choose_bands(int64_t rows, int64_t ns, int64_t simds, int k, int64_t pri
   return best;
 }
 
+// Insulated edges (kBcInsulatedX / kBcInsulatedY): the kernel argument of tb_kernel_ins and its occupancy
+constexpr int kBcAll = kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY;
+int ins_edges(int bc) {
+  return ((bc & kBcInsulatedX) ? (kInsRowLo | kInsRowHi) : 0) | ((bc & kBcInsulatedY) ? (kInsColLo | kInsColHi) : 0);
+}
+int occupancy_ins(DType dt, int k, int arith) {
+  return with_ar(arith, [&](auto ar) {
+    constexpr int AR = decltype(ar)::value;
+    if constexpr (AR == 3) {
+      HEAT2D_REQUIRE(false, "insulated boundaries have no arith 3 (fast) kernels");
+      return 1;
+    } else {
+      return dt == DType::F32 ? occupancy_blocks_ins<float, AR>(k) : occupancy_blocks_ins<double, AR>(k);
+    }
+  });
+}
+
+// The frame entries the launchers keep behind a stencil launch over `rects`:
+// periodic y the ghost columns, insulated y the frame columns, insulated x the
+// frame row of a slab at the wall — one fill per run of rows the rects cover
+// (rects of one launch share rows strip by strip, or are disjoint bands):
+// never a row another launch writes. Same stream as the launch.
+void fill_frames(DType dt, void* dst, const SlabLayout& L0, const TbRect* rects, int nrect, int bc,
+                 hipStream_t stream) {
+  if (!(bc & (kBcPeriodicY | kBcInsulatedX | kBcInsulatedY))) return;
+  int64_t lo[2 * kMaxRects], hi[2 * kMaxRects];
+  int n = 0;
+  for (int i = 0; i < nrect; ++i) {
+    int64_t b = rects[i].r0, t = rects[i].r1;
+    if (t <= b || rects[i].s1 <= rects[i].s0 || rects[i].nb == 0) continue;
+    for (int j = 0; j < n;) {  // absorb every run [lo, hi) that touches [b, t)
+      if (lo[j] <= t && b <= hi[j]) {
+        b = std::min(b, lo[j]);
+        t = std::max(t, hi[j]);
+        lo[j] = lo[n - 1];
+        hi[j] = hi[n - 1];
+        --n;
+        j = 0;
+      } else {
+        ++j;
+      }
+    }
+    lo[n] = b;
+    hi[n] = t;
+    ++n;
+  }
+  for (int j = 0; j < n; ++j) {
+    if (bc & kBcPeriodicY) launch_wrap_cols(dt, dst, L0, lo[j], hi[j], stream);
+    if (bc & kBcInsulatedY) launch_ins_cols(dt, dst, L0, lo[j], hi[j], stream);
+  }
+  if (bc & kBcInsulatedX)  // (after the columns: the image row carries the frame columns' images)
+    for (int j = 0; j < n; ++j)
+      launch_ins_rows(dt, dst, L0, lo[j] <= 0 && hi[j] > 0, lo[j] < L0.nrows && hi[j] >= L0.nrows, stream);
+}
+
 // Launch `rects` (item counts from their nb and strip ranges) on `nwaves` waves.
 // partials != nullptr: the fused-statistics kernel (general, ring 4). Returns the waves launched.
-// bc: kernels.hpp kBcPeriodicX / kBcPeriodicY; L is the slab's own layout (the
-// kernels see bc_layout(L, bc)). Periodic y: the ghost columns of the rows
-// written are refreshed right behind the stencil launch, on the same stream,
-// so whatever orders a consumer after this launch orders it after the fill.
-int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
-                     const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
-                     double* partials = nullptr, uint32_t* queue = nullptr, int bc = 0, bool pipe = false) {
+// bc: kernels.hpp kBcPeriodicX / ... / kBcInsulatedY; L is the slab's own
+// layout (the kernels see bc_layout(L, bc)). Insulated edges: a general launch
+// runs tb_kernel_ins (ring 4, whatever `ring` says) with the insulated edges as
+// its extra argument. The frame entries are refreshed by the caller (launch_rects).
+int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
+                       const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
+                       double* partials, uint32_t* queue, int bc, bool pipe) {
   HEAT2D_REQUIRE(nrect >= 1 && nrect <= (main ? kMainRects : kMaxRects), "bad rect count");
   HEAT2D_REQUIRE(!pipe || (main && !partials && pipe_available(dt, k, arith)), "no wave-pair kernel for this launch");
-  HEAT2D_REQUIRE((bc & ~(kBcPeriodicX | kBcPeriodicY)) == 0, "bc must be a set of kBcPeriodicX | kBcPeriodicY");
+  const int ins = main ? 0 : ins_edges(bc);  // (interior launches: launch_rects keeps insulated edges out of them)
+  if (ins) {
+    HEAT2D_REQUIRE(!partials, "the fused-statistics kernel has no insulated boundaries");
+    HEAT2D_REQUIRE(arith != 3, "insulated boundaries have no arith 3 (fast) kernels");
+  }
   const SlabLayout L = bc_layout(L0, bc);
   check_layout(dt, L, k);  // (the shifted rows must still fit the march's 32-bit row index)
   if (bc & kBcPeriodicY) {
@@ -338,6 +397,18 @@ int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0,
       dispatch_pipe<decltype(ar)::value>(k, (unsigned)((a.nwaves + 1) / 2), static_cast<const double*>(src) + o,
                                          static_cast<double*>(dst) + o, a, r, status, stream);
     });
+  } else if (ins) {
+    with_ar(arith, [&](auto ar) {
+      constexpr int AR = decltype(ar)::value;
+      if constexpr (AR != 3) {
+        if (dt == DType::F32)
+          dispatch_ins<float, AR>(k, nblocks, static_cast<const float*>(src) + o, static_cast<float*>(dst) + o, a,
+                                  (float)r, ins, stream);
+        else
+          dispatch_ins<double, AR>(k, nblocks, static_cast<const double*>(src) + o, static_cast<double*>(dst) + o, a,
+                                   r, ins, stream);
+      }
+    });
   } else if (partials) {
     HEAT2D_REQUIRE(a.nwaves <= max_stats_waves(), "statistics partials buffer too small");
     const float* s32 = static_cast<const float*>(src) + o;
@@ -356,32 +427,68 @@ int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0,
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) fail(__FILE__, __LINE__, std::string("tb_kernel launch: ") + hipGetErrorString(e));
-  if (bc & kBcPeriodicY) {
-    // one fill per run of rows the rects cover (rects of one launch share rows
-    // strip by strip, or are disjoint bands): never a row another launch writes
-    int64_t lo[kMaxRects], hi[kMaxRects];
-    int n = 0;
-    for (int i = 0; i < a.nrect; ++i) {
-      int64_t b = a.rect[i].r0, t = a.rect[i].r1;
-      for (int j = 0; j < n;) {  // absorb every run [lo, hi) that touches [b, t)
-        if (lo[j] <= t && b <= hi[j]) {
-          b = std::min(b, lo[j]);
-          t = std::max(t, hi[j]);
-          lo[j] = lo[n - 1];
-          hi[j] = hi[n - 1];
-          --n;
-          j = 0;
-        } else {
-          ++j;
-        }
-      }
-      lo[n] = b;
-      hi[n] = t;
-      ++n;
-    }
-    for (int j = 0; j < n; ++j) launch_wrap_cols(dt, dst, L0, lo[j], hi[j], stream);
-  }
   return a.nwaves;
+}
+
+// Launch `rects` and refresh the frame entries behind them (periodic y: the
+// ghost columns; insulated axes: the frame images) right behind the stencil
+// launch, on the same stream, so whatever orders a consumer after this launch
+// orders it after the fills. Insulated y under
+// an interior (MAIN) launch: the interior kernel pins the frame columns, so
+// the first and the last strip of every rect are carved out of it and run as
+// rects of tb_kernel_ins, on the same stream right behind it (disjoint
+// columns of the same rows).
+int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
+                     const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
+                     double* partials = nullptr, uint32_t* queue = nullptr, int bc = 0, bool pipe = false) {
+  HEAT2D_REQUIRE((bc & ~kBcAll) == 0, "bc must be a set of kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY");
+  HEAT2D_REQUIRE(!((bc & kBcPeriodicX) && (bc & kBcInsulatedX)) && !((bc & kBcPeriodicY) && (bc & kBcInsulatedY)),
+                 "an axis is periodic or insulated, not both");
+  if (!(main && (bc & kBcInsulatedY))) {
+    const int64_t nw = launch_rects_1(dt, src, dst, L0, k, ring, main, rects, nrect, nwaves, r, stream, arith, partials,
+                                      queue, bc, pipe);
+    fill_frames(dt, dst, L0, rects, nrect, bc, stream);
+    return nw;
+  }
+  HEAT2D_REQUIRE(!pipe, "insulated y: the wave-pair kernel's wide strips are not carved (no pipe plans)");
+  HEAT2D_REQUIRE(nrect >= 1 && nrect <= kMainRects, "bad rect count");
+  const int64_t U = useful_width(dt, k);
+  const int64_t ns = (bc_layout(L0, bc).ncols + U - 1) / U;
+  // the strips whose loads reach a frame column (the kernels' edge-kind test:
+  // c0 < 0 is strip 0 alone; c0 + W > ncols the last strip, and the one before
+  // it when the last is narrower than the halo): [0, 1) and [sF, ns)
+  const int64_t KA = halo_cols(dt, k), ncols = bc_layout(L0, bc).ncols;
+  int64_t sF = ns;
+  while (sF > 1 && (sF - 1) * U + U + KA > ncols) --sF;
+  const int64_t slots = (int64_t)cu_count() * occupancy_ins(dt, k, arith) * 4;
+  TbRect in[kMainRects], fr[2 * kMainRects];
+  int ni = 0, nf = 0;
+  for (int i = 0; i < nrect; ++i) {
+    const TbRect& R = rects[i];
+    if (R.r1 <= R.r0 || R.s1 <= R.s0 || R.nb == 0) continue;
+    const int64_t rows = R.r1 - R.r0, w = R.s1 - R.s0;
+    const int64_t i0 = std::max<int64_t>(R.s0, 1), i1 = std::max(i0, std::min(R.s1, sF));  // interior strips [i0, i1)
+    const int64_t h0 = std::max(R.s0, sF);                                                 // high frame strips [h0, s1)
+    // the interior keeps its bands / its strips' share of the segments (q per
+    // strip); the frame strips get short bands of their own: a few items of
+    // the interior's length on tb_kernel_ins (1 wave/SIMD at deep fp64 depths,
+    // launched behind the interior) would be the launch's tail
+    const int64_t q = std::min<int64_t>(rows, std::max<int64_t>(1, (std::abs(R.nb) + w / 2) / w));
+    const int64_t nbf = std::min<int64_t>(rows, std::max<int64_t>(R.nb > 0 ? R.nb : q, choose_bands(rows, 2, slots, k)));
+    if (R.s0 < 1) fr[nf++] = TbRect{R.r0, R.r1, 0, 1, nbf};
+    if (R.s1 > h0) fr[nf++] = TbRect{R.r0, R.r1, h0, R.s1, nbf};
+    if (i1 > i0)
+      in[ni++] = TbRect{R.r0, R.r1, i0, i1,
+                        R.nb > 0 ? R.nb : -std::min<int64_t>(rows * (i1 - i0), std::max<int64_t>(1, -R.nb - q * (w - (i1 - i0))))};
+  }
+  int64_t nw = 0;
+  if (ni > 0)
+    nw = launch_rects_1(dt, src, dst, L0, k, ring, true, in, ni, nwaves, r, stream, arith, nullptr, queue, bc, false);
+  for (int i = 0; i < nf; i += kMaxRects)
+    launch_rects_1(dt, src, dst, L0, k, 4, false, fr + i, std::min(nf - i, kMaxRects), slots, r, stream, arith, nullptr,
+                   nullptr, bc, false);
+  fill_frames(dt, dst, L0, rects, nrect, bc, stream);
+  return nw;
 }
 
 }  // namespace

@@ -305,8 +305,30 @@ constexpr int chain_len() {
 #define HEAT2D_STORE_AUX 2
 #endif
 
-template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, int CL = K>
-struct March {
+// INS (tb_kernel_ins, items that touch an insulated edge): at a point next to
+// an insulated wall the operand that would come from beyond the wall is the
+// point's own value, at every level — the frame entry of an insulated axis is
+// the image of the adjacent owned point, so this is the reference sum with the
+// frame refreshed before every step, and K fused levels have the bits of K
+// single steps. (A mirrored ghost layer cannot: its points sum their operands
+// in the swapped order.) Frame rows and columns stay pinned; their in-march
+// values are never read by an owned point.
+// (The wall state lives in a base that is empty unless INS, so the plain
+// marches keep their layout — and their code — to the byte.)
+template <bool INS>
+struct WallState {};
+template <>
+struct WallState<true> {
+  // EK & 1: the first / last owned row when its wall is insulated (else a row
+  // no march reaches): there the north / south operand is the centre row
+  int32_t wall_lo, wall_hi;
+  // EK & 2: this lane's element 0 is the first owned column (strips start at
+  // whole lanes) / bit e: element e is the last owned column, wall insulated
+  bool wall_w;
+  uint32_t wall_e;
+};
+template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false>
+struct March : WallState<INS> {
   using S = TbShape<T, NV, K>;
   static constexpr int V = S::V;
   static constexpr int VM = S::VM;
@@ -383,10 +405,21 @@ struct March {
 
   // part = S + E(C): the first partial sum of the reference order, from the
   // level's oldest row S and the east neighbours of its centre row C.
-  __device__ __forceinline__ void partial(const T (&Sx)[V], const T (&C)[V], T (&part)[V]) const {
+  // (row: the row the sum belongs to — INS only)
+  __device__ __forceinline__ void partial(const T (&Sx)[V], const T (&C)[V], T (&part)[V], int32_t row = 0) const {
     const T eastL = from_upper(C[0]);
+    if constexpr (INS) {
+      const bool swall = (EK & 1) && row == this->wall_hi;  // wave-uniform
 #pragma unroll
-    for (int e = 0; e < V; ++e) part[e] = Sx[e] + (e < V - 1 ? C[e + 1] : eastL);
+      for (int e = 0; e < V; ++e) {
+        T east = e < V - 1 ? C[e + 1] : eastL;
+        if constexpr ((EK & 2) != 0) east = ((this->wall_e >> e) & 1u) ? C[e] : east;
+        part[e] = (swall ? C[e] : Sx[e]) + east;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < V; ++e) part[e] = Sx[e] + (e < V - 1 ? C[e + 1] : eastL);
+    }
   }
 
   // ((part + N) + W) then C + r*(sum - 4C), pinned columns / rows kept.
@@ -397,11 +430,16 @@ struct March {
     const T rs = frame_row ? T(0) : r;                                      // EK 1: scalar select
 #pragma unroll
     for (int e = 0; e < V; ++e) {
-      const T west = e > 0 ? C[e - 1] : west0;
+      T west = e > 0 ? C[e - 1] : west0;
+      T north = N[e];
+      if constexpr (INS) {
+        if ((EK & 2) && e == 0) west = this->wall_w ? C[0] : west;
+        if (EK & 1) north = row == this->wall_lo ? C[e] : north;  // wave-uniform
+      }
       // reference order: ((S + E) + N) + W - 4C; sum - 4C as fma(-4, C, sum)
       // is bitwise identical (4C is exact) and saves one op; C + r*(...)
       // stays unfused, as in the reference.
-      const T sum = (part[e] + N[e]) + west;
+      const T sum = (part[e] + north) + west;
       T re;
       if constexpr (EK == 0) re = r;
       else if constexpr (EK == 1) re = rs;
@@ -440,7 +478,7 @@ struct March {
       T S0[V];
       unpack(Lb[sS], S0);
       unpack(Lb[sC], C0);
-      partial(S0, C0, part);  // level 1's S+E
+      partial(S0, C0, part, m + Ch::off(1));  // level 1's S+E
     }
     {  // row m+2 is dead: refill its slot with row m+2-RING (clamped: a harmless re-read).
       // The scheduling fence keeps the load below the slot's last use: hoisted
@@ -473,7 +511,7 @@ struct March {
       }
       const int ps = Ch::slot(PH, 0, s < K ? s : 1);  // this level's slot of this iteration
       // level s+1's S+E from level s's S (the slot about to be overwritten) and C
-      if (s < K) partial(X[ps][s - 1], X[Ch::slot(PH, Ch::delta(s + 1), s)][s - 1], nxtpart);
+      if (s < K) partial(X[ps][s - 1], X[Ch::slot(PH, Ch::delta(s + 1), s)][s - 1], nxtpart, m + Ch::off(s + 1));
       update(part, C, N, m + Ch::off(s), out);
       if (s < K) {
 #pragma unroll
@@ -576,8 +614,8 @@ struct March {
 // ~2x the registers: 209 VGPRs at K = 10). Same operation order and rounding
 // per element as March (bitwise identical); the loads / stores / ring /
 // descriptors / edge kinds are March's.
-template <int K, int EK, int RING, int AR, bool ST = false, int CL = K>
-struct MarchF32 {
+template <int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false>
+struct MarchF32 : WallState<INS> {
   using F2 = float __attribute__((ext_vector_type(2)));
   using VT = float __attribute__((ext_vector_type(4)));
   using U4 = unsigned int __attribute__((ext_vector_type(4)));
@@ -629,13 +667,36 @@ struct MarchF32 {
   static __device__ __forceinline__ Row split(const Row& v) { return Row{F2{v.a.x, v.b.x}, F2{v.a.y, v.b.y}}; }
 
   // part = S + E(C) (first partial sum of the reference order)
-  static __device__ __forceinline__ Row partial(const Row& S, const Row& C) {
-    return Row{S.a + C.b, F2{sadd(S.b.x, C.a.y), sadd_from_upper(S.b.y, C.a.x)}};
+  // (row: the row the sum belongs to — INS only: the operands beyond an
+  // insulated wall become the centre's, see March)
+  __device__ __forceinline__ Row partial(const Row& S, const Row& C, int32_t row) const {
+    if constexpr (INS) {
+      const bool swall = (EK & 1) && row == this->wall_hi;  // wave-uniform
+      Row E{C.b, F2{C.a.y, from_upper(C.a.x)}};             // east of (c0, c2), (c1, c3)
+      if constexpr ((EK & 2) != 0) {  // (wall_e: bit e = column c_e, memory order)
+        E.a.x = (this->wall_e & 1u) ? C.a.x : E.a.x;
+        E.b.x = (this->wall_e & 2u) ? C.b.x : E.b.x;
+        E.a.y = (this->wall_e & 4u) ? C.a.y : E.a.y;
+        E.b.y = (this->wall_e & 8u) ? C.b.y : E.b.y;
+      }
+      const Row Sx = swall ? C : S;
+      return Row{Sx.a + E.a, Sx.b + E.b};
+    } else {
+      return Row{S.a + C.b, F2{sadd(S.b.x, C.a.y), sadd_from_upper(S.b.y, C.a.x)}};
+    }
   }
   // ((part + N) + W): the reference's sum
-  static __device__ __forceinline__ Row sum4(const Row& part, const Row& C, const Row& N) {
-    const F2 ta = part.a + N.a;
-    return Row{F2{sadd_from_lower(ta.x, C.b.y), sadd(ta.y, C.b.x)}, (part.b + N.b) + C.a};
+  __device__ __forceinline__ Row sum4(const Row& part, const Row& C, const Row& N, int32_t row) const {
+    if constexpr (INS) {
+      const bool nwall = (EK & 1) && row == this->wall_lo;  // wave-uniform
+      float w0 = from_lower(C.b.y);                          // west of c0
+      if constexpr ((EK & 2) != 0) w0 = this->wall_w ? C.a.x : w0;
+      const Row Nx = nwall ? C : N;
+      return Row{(part.a + Nx.a) + F2{w0, C.b.x}, (part.b + Nx.b) + C.a};
+    } else {
+      const F2 ta = part.a + N.a;
+      return Row{F2{sadd_from_lower(ta.x, C.b.y), sadd(ta.y, C.b.x)}, (part.b + N.b) + C.a};
+    }
   }
   // AR 2, pinned kinds: re * sum + (C - 4 re C) (see March::update)
   static __device__ __forceinline__ F2 pin2(F2 re, F2 sum, F2 c) {
@@ -648,7 +709,7 @@ struct MarchF32 {
   // sum - 4C (in) and the per-element r (re) of the update C + r*(sum - 4C)
   __device__ __forceinline__ void terms(const Row& part, const Row& C, const Row& N, int32_t row, Row& in,
                                         Row& re) const {
-    const Row sum = sum4(part, C, N);
+    const Row sum = sum4(part, C, N, row);
     const F2 m4 = {-4.f, -4.f};
     in = Row{__builtin_elementwise_fma(m4, C.a, sum.a), __builtin_elementwise_fma(m4, C.b, sum.b)};
     const bool frame_row = (EK & 1) && ((uint32_t)(row - fixed_lo) >= (uint32_t)(fixed_hi - fixed_lo));  // wave-uniform
@@ -666,12 +727,12 @@ struct MarchF32 {
   }
   __device__ __forceinline__ Row update(const Row& part, const Row& C, const Row& N, int32_t row) const {
     if constexpr (AR == 3 && EK == 0) {  // scaled: fma(b, C, sum) on packed pairs
-      const Row sum = sum4(part, C, N);
+      const Row sum = sum4(part, C, N, row);
       const F2 b2 = {fb, fb};
       return Row{__builtin_elementwise_fma(b2, C.a, sum.a), __builtin_elementwise_fma(b2, C.b, sum.b)};
     }
     if constexpr (AR == 2 || AR == 3) {  // (AR 3, kind 0: above)
-      const Row sum = sum4(part, C, N);
+      const Row sum = sum4(part, C, N, row);
       if constexpr (EK == 0) return sum;  // scaled: 4^s T
       const bool frame_row = (EK & 1) && ((uint32_t)(row - fixed_lo) >= (uint32_t)(fixed_hi - fixed_lo));  // wave-uniform
       if constexpr (EK == 1) {  // fma(ke, C, re * sum), scalar (re, ke) (see March::update)
@@ -699,12 +760,12 @@ struct MarchF32 {
   // the even/odd pairs and need a transpose before the 16-B store.
   __device__ __forceinline__ VT update_last(const Row& part, const Row& C, const Row& N, int32_t row) const {
     if constexpr (AR == 3 && EK == 0) {  // scaled level K, unscaled by r^K at the store
-      const Row sum = sum4(part, C, N);
+      const Row sum = sum4(part, C, N, row);
       return VT{__builtin_fmaf(fb, C.a.x, sum.a.x) * fu, __builtin_fmaf(fb, C.b.x, sum.b.x) * fu,
                 __builtin_fmaf(fb, C.a.y, sum.a.y) * fu, __builtin_fmaf(fb, C.b.y, sum.b.y) * fu};
     }
     if constexpr (AR == 2 || AR == 3) {  // (AR 3, kind 0: above)
-      const Row sum = sum4(part, C, N);
+      const Row sum = sum4(part, C, N, row);
       if constexpr (EK == 0) {
         // unscale 4^K T once, at the store (exact)
         constexpr float u = inv_pow4<float>(K);
@@ -732,7 +793,7 @@ struct MarchF32 {
     constexpr int P0 = PH % RING;
     constexpr int sN = P0, sC = (P0 + RING - 1) % RING, sS = (P0 + RING - 2) % RING;
     const Row C0 = Lb[sC];
-    Row part = partial(Lb[sS], C0);
+    Row part = partial(Lb[sS], C0, m + Ch::off(1));
     {
       const int32_t nxt = m + 2 - RING;
       __builtin_amdgcn_sched_barrier(0);
@@ -751,7 +812,7 @@ struct MarchF32 {
       if (s < K) {
         const int i = s < K ? s - 1 : 0;
         const int ps = Ch::slot(PH, 0, s < K ? s : 1);
-        const Row nxtpart = partial(X[ps][i], X[Ch::slot(PH, Ch::delta(s + 1), s < K ? s : 1)][i]);
+        const Row nxtpart = partial(X[ps][i], X[Ch::slot(PH, Ch::delta(s + 1), s < K ? s : 1)][i], m + Ch::off(s + 1));
         X[ps][i] = update(part, C, N, m + Ch::off(s));
         part = nxtpart;
       } else {
@@ -832,9 +893,13 @@ template <typename T, int NV>
 constexpr bool kPackedF32 = false;
 #endif
 
-template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, bool PS = false, int CLX = 0>
+// Insulated edges of the grid (tb_kernel_ins's extra argument; March INS)
+constexpr int kInsRowLo = 1, kInsRowHi = 2, kInsColLo = 4, kInsColHi = 8;
+
+template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, bool PS = false, int CLX = 0,
+          bool INS = false>
 __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r, int64_t strip, int64_t t0,
-                                      int64_t t1, int lane, StatAcc* acc = nullptr) {
+                                      int64_t t1, int lane, StatAcc* acc = nullptr, int ins = 0) {
   using S = TbShape<T, NV, K>;
   constexpr int V = S::V;
   constexpr int ES = (int)sizeof(T);
@@ -846,8 +911,8 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
   // the chains' extra rows spill at fp64 K >= 21
   // (CLX > 0: an explicit chain length — the boundary-band kernel)
   constexpr int CL = CLX > 0 ? (CLX < K ? CLX : K) : (ST ? K : chain_len<T, K>());
-  using W = typename std::conditional<kPackedF32<T, NV>, MarchF32<K, EK, RING, AR, ST, CL>,
-                                      March<T, NV, K, EK, RING, AR, ST, CL>>::type;
+  using W = typename std::conditional<kPackedF32<T, NV>, MarchF32<K, EK, RING, AR, ST, CL, INS>,
+                                      March<T, NV, K, EK, RING, AR, ST, CL, INS>>::type;
   W w;
   // row base = column col_lo (= -cpad) of row 0; offsets are relative to it
   w.srow = reinterpret_cast<const char*>(src + a.col_lo);
@@ -885,6 +950,17 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
 #pragma unroll
       for (int e = 0; e < V; ++e) w.rl[e] = rcol(e);
     }
+  }
+  if constexpr (INS) {
+    // rows no march reaches stand for "no insulated wall" (row indices are < 2^31 - kMaxTB)
+    constexpr int32_t kNoRow = (int32_t)0x80000000u;
+    w.wall_lo = (ins & kInsRowLo) ? w.fixed_lo : kNoRow;
+    w.wall_hi = (ins & kInsRowHi) ? w.fixed_hi - 1 : kNoRow;
+    w.wall_w = (ins & kInsColLo) && mycol == 0;
+    uint32_t me = 0;
+#pragma unroll
+    for (int e = 0; e < V; ++e) me |= ((ins & kInsColHi) && mycol + e == a.ncols - 1) ? (1u << e) : 0u;
+    w.wall_e = me;
   }
   if constexpr (ST) {
     uint32_t mask = 0;
@@ -1103,6 +1179,41 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VAR == kVar
   }
 }
 
+// The general kernel with insulated edges (`ins`: kInsRowLo | kInsRowHi |
+// kInsColLo | kInsColHi, an argument of this kernel only — TbArgs and every
+// tb_kernel instance stay as they are): the same items, kinds and march; an
+// item of kind 1 / 2 / 3 runs the march with the operand substitution (March
+// INS) at the insulated walls it touches, a kind-0 item the plain march.
+template <typename T, int NV, int K, int RING, int AR>
+__global__ __launch_bounds__(256) void tb_kernel_ins(const T* __restrict__ src, T* __restrict__ dst, TbArgs a, T r,
+                                                     int ins) {
+  using S = TbShape<T, NV, K>;
+  const int lane = threadIdx.x & 63;
+  const int64_t wid = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (wid >= a.nwaves) return;  // whole wave exits; no barriers in this kernel
+  int64_t it = wid;
+  int32_t lin = tb_span<kMaxRects>(a, it).lin;
+  while (it < a.nitems) {
+    int64_t strip, t0, t1;
+    if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {
+      it = next_item(a, it);
+      if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;
+      continue;
+    }
+    lin += (int32_t)(t1 - t0);
+    const int64_t c0 = strip * S::U - S::KA;
+    const int ek = (((t0 - K < a.fixed_lo) || (t1 + K > a.fixed_hi)) ? 1 : 0) |
+                   (((c0 < 0) || (c0 + S::W > a.ncols)) ? 2 : 0);
+    switch (ek) {
+      case 0: march<T, NV, K, 0, RING, AR>(src, dst, a, r, strip, t0, t1, lane); break;
+      case 1: march<T, NV, K, 1, RING, AR, false, false, 0, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, ins); break;
+      case 2: march<T, NV, K, 2, RING, AR, false, false, 0, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, ins); break;
+      default: march<T, NV, K, 3, RING, AR, false, false, 0, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, ins); break;
+    }
+  }
+  queue_exit(a);
+}
+
 template <typename T, int NV, int K, int RING, bool MAIN, int AR, int VAR = kVarPlain>
 constexpr auto kernel_ptr() {
   return &tb_kernel<T, NV, K, RING, MAIN, AR, VAR>;
@@ -1138,6 +1249,11 @@ template <typename T, int AR>
 void dispatch_stats(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, hipStream_t s);
 template <typename T, int AR>
 int occupancy_blocks_stats(int k);
+// insulated-edge kernels: general kernel, ring 4 (tb_<dtype>_ins[_fma|_jac].hip)
+template <typename T, int AR>
+void dispatch_ins(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, int ins, hipStream_t s);
+template <typename T, int AR>
+int occupancy_blocks_ins(int k);
 #define H2D_TB_CASE(T, RING, MAIN, AR, KK)                                                                    \
   case KK:                                                                                                    \
     hipLaunchKernelGGL((tb_kernel<T, 1, KK, RING, MAIN, AR>), dim3(nblocks), dim3(256), 0, s, src, dst, a, r); \
@@ -1218,6 +1334,52 @@ int occupancy_blocks_stats(int k);
     return 1;                                                                                                 \
   }
 
+template <typename T, int K, int AR>
+int blocks_per_cu_ins() {
+  static std::mutex mu;
+  static std::map<int, int> cache;  // device -> blocks/CU
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> g(mu);
+  auto it = cache.find(dev);
+  if (it != cache.end()) return it->second;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tb_kernel_ins<T, 1, K, 4, AR>),
+                                                   256, 0) != hipSuccess ||
+      nb <= 0)
+    nb = 1;
+  cache[dev] = nb;
+  return nb;
+}
+#define H2D_INS_CASE(T, RING, MAIN, AR, KK)                                                                      \
+  case KK:                                                                                                       \
+    hipLaunchKernelGGL((tb_kernel_ins<T, 1, KK, 4, AR>), dim3(nblocks), dim3(256), 0, s, src, dst, a, r, ins); \
+    return;
+#define H2D_INS_OCC_CASE(T, RING, MAIN, AR, KK) \
+  case KK:                                      \
+    return blocks_per_cu_ins<T, KK, AR>();
+#define H2D_INS_UNIT(T, AR, DEEP)                                                                             \
+  template <>                                                                                                 \
+  void dispatch_ins<T, AR>(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, int ins,      \
+                           hipStream_t s) {                                                                   \
+    switch (k) {                                                                                              \
+      H2D_TB_CASES(H2D_INS_CASE, T, 4, false, AR)                                                             \
+      DEEP(H2D_INS_CASE, T, 4, false, AR)                                                                     \
+      default:                                                                                                \
+        break;                                                                                                \
+    }                                                                                                         \
+    HEAT2D_REQUIRE(false, "temporal depth not instantiated for the insulated-edge kernel");                   \
+  }                                                                                                           \
+  template <>                                                                                                 \
+  int occupancy_blocks_ins<T, AR>(int k) {                                                                    \
+    switch (k) {                                                                                              \
+      H2D_TB_CASES(H2D_INS_OCC_CASE, T, 4, false, AR)                                                         \
+      DEEP(H2D_INS_OCC_CASE, T, 4, false, AR)                                                                 \
+      default:                                                                                                \
+        break;                                                                                                \
+    }                                                                                                         \
+    return 1;                                                                                                 \
+  }
 
 }  // namespace tbimpl
 }  // namespace kern

@@ -283,8 +283,8 @@ Meta read_meta(const std::string& dir) {
   if (js.find("\"edge_shift\"") != std::string::npos) m.edge_shift = std::atoll(json_value(js, "edge_shift").c_str());
   if (js.find("\"bc_x\"") != std::string::npos) m.bc_x = json_value(js, "bc_x");
   if (js.find("\"bc_y\"") != std::string::npos) m.bc_y = json_value(js, "bc_y");
-  HEAT2D_REQUIRE((m.bc_x == "dirichlet" || m.bc_x == "periodic") && (m.bc_y == "dirichlet" || m.bc_y == "periodic"),
-                 dir + ": meta.json: bc_x / bc_y must be dirichlet or periodic");
+  auto bc_ok = [](const std::string& v) { return v == "dirichlet" || v == "periodic" || v == "insulated"; };
+  HEAT2D_REQUIRE(bc_ok(m.bc_x) && bc_ok(m.bc_y), dir + ": meta.json: bc_x / bc_y must be dirichlet, periodic or insulated");
   HEAT2D_REQUIRE(m.nranks >= 1 && m.step >= 0 && m.n_owned >= 1, dir + ": inconsistent meta.json");
   return m;
 }

@@ -67,7 +67,7 @@ SlabLayout solver_layout(const SolverConfig& cfg, int rank, int nranks) {
     return make_layout(cfg.n_rows, cfg.n_cols, halo, cfg.slab_row0, cfg.slab_rows_global);
   }
   // (periodic x: no slab is an edge slab, nothing to shift)
-  const SlabRange sr = decompose(cfg.n_rows, nranks, rank, cfg.bc_x ? 0 : cfg.edge_shift);
+  const SlabRange sr = decompose(cfg.n_rows, nranks, rank, cfg.bc_x == kBcPeriodic ? 0 : cfg.edge_shift);
   return make_layout(sr.nrows, cfg.n_cols, halo, sr.row0, cfg.n_rows);
 }
 
@@ -136,19 +136,24 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
                  "arith must be 0 (reference rounding), 1 (fma), 2 (jacobi, r = 1/4), 3 (fast) or -1 (auto)");
   HEAT2D_REQUIRE(cfg_.arith != 2 || cfg_.r == 0.25, "arith 2 (jacobi) needs r == 1/4 exactly (sigma = 0.25)");
   HEAT2D_REQUIRE(cfg_.arith != 3 || cfg_.r > 0, "arith 3 (fast) needs r > 0");
-  HEAT2D_REQUIRE((cfg_.bc_x == 0 || cfg_.bc_x == 1) && (cfg_.bc_y == 0 || cfg_.bc_y == 1),
-                 "bc_x / bc_y must be 0 (dirichlet) or 1 (periodic)");
+  HEAT2D_REQUIRE(cfg_.bc_x >= 0 && cfg_.bc_x <= 2 && cfg_.bc_y >= 0 && cfg_.bc_y <= 2,
+                 "bc_x / bc_y must be 0 (dirichlet), 1 (periodic) or 2 (insulated)");
   bc_ = config_bc(cfg_);
   if (bc_) {
-    HEAT2D_REQUIRE(cfg_.engine == 0, "periodic boundaries need the temporal-blocked engine (engine \"jit\" is Dirichlet only)");
-    HEAT2D_REQUIRE(!cfg_.copy_swap, "periodic boundaries have no copy-swap mode (Dirichlet only)");
-    HEAT2D_REQUIRE(cfg_.slab_rows_global == 0, "periodic boundaries: no middle-slab rehearsal (slab_rows_global)");
+    const bool ins = (bc_ & (kern::kBcInsulatedX | kern::kBcInsulatedY)) != 0;
+    const std::string what = ins ? "insulated boundaries" : "periodic boundaries";
+    HEAT2D_REQUIRE(cfg_.engine == 0, what + " need the temporal-blocked engine (engine \"jit\" is Dirichlet only)");
+    HEAT2D_REQUIRE(!cfg_.copy_swap, what + " have no copy-swap mode (Dirichlet only)");
+    HEAT2D_REQUIRE(cfg_.slab_rows_global == 0, what + ": no middle-slab rehearsal (slab_rows_global)");
+    HEAT2D_REQUIRE(!ins || cfg_.arith != 3,
+                   "arith 3 (fast) has no insulated boundaries: the scaled levels have no insulated kernels (use "
+                   "exact, fma, jacobi or auto)");
   }
-  if (cfg_.bc_y)
+  if (cfg_.bc_y == kBcPeriodic)
     HEAT2D_REQUIRE(cfg_.n_cols >= kern::kWrapCols,
                    "grid too small for periodic y: " + std::to_string(cfg_.n_cols) + " owned columns, the ghost depth is " +
                        std::to_string(kern::kWrapCols));
-  if (cfg_.bc_x) {
+  if (cfg_.bc_x == kBcPeriodic) {
     // the wrap images of a slab's ghost rows must come from ONE rank's owned rows
     const int64_t need = tb_given ? std::min<int64_t>(cfg_.tb, max_tb(dtype())) : 1;
     HEAT2D_REQUIRE(cfg_.n_rows / P >= need, "grid too small for periodic x: " + std::to_string(cfg_.n_rows / P) +
@@ -298,12 +303,12 @@ void Solver::init(const kern::IcParams& ic, const double* xg, const double* yg) 
   // ghost rows are filled from the global IC directly: no exchange needed
   cur_ = 0;
   steps_ = 0;
-  ghost_ = cfg_.bc_x ? 0 : (int)band_;
+  ghost_ = cfg_.bc_x == kBcPeriodic ? 0 : (int)band_;
   last_x_[0] = last_x_[1] = 0;
   last_k_ = 0;
   // ... except with periodic x, where they are wrap images: one exchange, as
   // after upload() (init is collective; a loopback group runs it for its members)
-  if (cfg_.bc_x && tr_->collective()) {
+  if (cfg_.bc_x == kBcPeriodic && tr_->collective()) {
     exchange_post();
     exchange_now();
     synchronize();
@@ -311,9 +316,22 @@ void Solver::init(const kern::IcParams& ic, const double* xg, const double* yg) 
 }
 
 void Solver::wrap_cols_all(void* field) {
-  if (!cfg_.bc_y) return;
-  if (hip_) kern::launch_wrap_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo, s_compute_);
-  else cpu::wrap_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo);
+  if (cfg_.bc_y == kBcPeriodic) {
+    if (hip_) kern::launch_wrap_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo, s_compute_);
+    else cpu::wrap_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo);
+  }
+  if (cfg_.bc_y == kBcInsulated) {
+    if (hip_) kern::launch_ins_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo, s_compute_);
+    else cpu::ins_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo);
+  }
+  if (cfg_.bc_x == kBcInsulated) {  // (after the columns: the image rows carry their images)
+    if (hip_) kern::launch_ins_rows(dtype(), field, L_, true, true, s_compute_);
+    else cpu::ins_rows(dtype(), field, L_, true, true);
+  }
+}
+
+bool Solver::pipe_ok(int k) const {
+  return kern::pipe_available(dtype(), k, cfg_.arith) && !(bc_ & kern::kBcInsulatedY);
 }
 
 void Solver::launch_tb(const void* src, void* dst, int64_t rb, int64_t re, int k) {
@@ -328,10 +346,16 @@ void Solver::exchange_on(void* field, int64_t k, hipStream_t s) {
   if (!tr_->exchanges()) return;
   HEAT2D_REQUIRE(k >= 1 && k <= band_, "halo exchange depth outside [1, band]");
   tr_->exchange(field, L_, dtype(), k, s, hip_);
-  if (cfg_.bc_y && !tr_->whole_rows()) {  // the ghost rows arrived without their ghost columns
+  if (cfg_.bc_y == kBcPeriodic && !tr_->whole_rows()) {  // the ghost rows arrived without their ghost columns
     for (int64_t r0 : {-k, L_.nrows}) {
       if (hip_) kern::launch_wrap_cols(dtype(), field, L_, r0, r0 + k, s);
       else cpu::wrap_cols(dtype(), field, L_, r0, r0 + k);
+    }
+  }
+  if (cfg_.bc_y == kBcInsulated && !tr_->whole_rows()) {  // ... nor their frame columns' images
+    for (int64_t r0 : {-k, L_.nrows}) {
+      if (hip_) kern::launch_ins_cols(dtype(), field, L_, r0, r0 + k, s);
+      else cpu::ins_cols(dtype(), field, L_, r0, r0 + k);
     }
   }
   halo_rows_ += k;
@@ -565,7 +589,7 @@ const kern::SplitPlan& Solver::split_plan(int k) {
     }
     // HEAT2D_PIPE=1: the interior on the wave-pair kernel wherever it exists
     if (pipe_mode() == 1 && p.valid && !(p.flags & kern::kPlanPipe) && hip_ &&
-        kern::pipe_available(dtype(), k, cfg_.arith) && !(p.valid == 2 && tr_->exchanges())) {
+        pipe_ok(k) && !(p.valid == 2 && tr_->exchanges())) {
       kern::SplitPlan q = kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, p.valid == 2 ? 0 : p.ring, 0,
                                            cfg_.arith, true);
       if (q.valid) {
@@ -798,7 +822,7 @@ bool Solver::cached_split(int k) {
   if (!plancache::get_plan(cache_ctx(), k, k, &c, &ms) || ms <= 0.f) return false;
   // geometry must match this slab (defensive: the key already pins it)
   if ((c.flags & kern::kPlanPipe) &&
-      (pipe_mode() == 0 || c.valid == 2 || !kern::pipe_available(dtype(), k, cfg_.arith)))
+      (pipe_mode() == 0 || c.valid == 2 || !pipe_ok(k)))
     return false;
   const kern::SplitPlan fresh = kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare_waves(), c.ring,
                                                  c.main.nb, cfg_.arith, (c.flags & kern::kPlanPipe) != 0);
@@ -898,7 +922,7 @@ void Solver::autotune_split(int k) {
       if (nk < 1 || nk > kMaxTB || (plan_origin_[nk] != 1 && plan_origin_[nk] != 2)) continue;
       const kern::SplitPlan& q = split_[nk];
       if (q.k != nk || !q.valid) continue;
-      const bool qpipe = (q.flags & kern::kPlanPipe) && kern::pipe_available(dtype(), k, cfg_.arith);
+      const bool qpipe = (q.flags & kern::kPlanPipe) && pipe_ok(k);
       kern::SplitPlan c = q.valid == 2
                               ? kern::plan_single(dtype(), Lk_, k, compute_cus_, q.ring, q.main.nb, cfg_.arith)
                               : kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, q.ring, q.main.nb, cfg_.arith,
@@ -1008,7 +1032,7 @@ void Solver::autotune_split(int k) {
   // The wave-pair interior kernel (fp64 depths with an instance): the same
   // band / segment families over its wide strips, items per PAIR of waves,
   // in the split orders (the boundary bands keep the one-wave strips).
-  if (pipe_mode() != 0 && best.valid != 2 && kern::pipe_available(dtype(), k, cfg_.arith)) {
+  if (pipe_mode() != 0 && best.valid != 2 && pipe_ok(k)) {
     const kern::SplitPlan p0 = kern::plan_split(dtype(), Lk_, k, k, compute_cus_, spare, best.ring, 0, cfg_.arith, true);
     if (p0.valid) {
       for (int mode : {1, 3}) {
@@ -1866,8 +1890,9 @@ void Solver::synchronize() {
 void Solver::step_stats(int64_t n, double out[6]) {
   HEAT2D_REQUIRE(n >= 1, "step_stats needs n >= 1");
   if (hip_) H2D_HIP(hipSetDevice(cfg_.device));
-  // (periodic y: the fused-statistics march would count its ghost columns)
-  if (!hip_ || jit_ || cfg_.copy_swap || cfg_.bc_y) {
+  // (periodic y: the fused-statistics march would count its ghost columns;
+  // insulated axes: the fused-statistics kernel has no insulated edges)
+  if (!hip_ || jit_ || cfg_.copy_swap || cfg_.bc_y || cfg_.bc_x == kBcInsulated) {
     step(n - 1);
     step(1);
     stats(out, true);
@@ -2061,7 +2086,7 @@ LoopbackGroup::~LoopbackGroup() {
 
 void LoopbackGroup::init(const kern::IcParams& ic, const double* xg, const double* yg) {
   for (auto& m : members_) m->init(ic, xg, yg);
-  if (members_[0]->config().bc_x) {  // periodic x: the ghost rows are wrap images (Solver::init)
+  if (members_[0]->config().bc_x == kBcPeriodic) {  // periodic x: the ghost rows are wrap images (Solver::init)
     for (auto& m : members_) m->synchronize();
     for (auto& m : members_) m->exchange_post();
     for (auto& m : members_) m->exchange_now();

@@ -125,12 +125,15 @@ class HeatSolver:
             more per row, and a step lasts as long as the slowest rank;
             bench.py measures the excess and picks the shift. Same on every rank.
         bc_x, bc_y: boundary condition of the row (x, decomposed over ranks) and
-            column (y) axis: "dirichlet" (the frame keeps its values) or
-            "periodic" (the n owned points are the period). Periodic results
-            are bitwise equal to models.reference.ftcs(bc_x=, bc_y=) at any
-            depth, plan and rank count; engine "tb" only, no copy_swap; on more
-            than one rank periodic x runs on the loopback, host-thread and
-            torch.distributed (host-staged) transports.
+            column (y) axis: "dirichlet" (the frame keeps its values),
+            "periodic" (the n owned points are the period) or "insulated" (a
+            zero-flux wall half a cell outside the first and last owned point;
+            the frame entries are images of the adjacent owned point). The
+            results are bitwise equal to models.reference.ftcs(bc_x=, bc_y=)
+            at any depth, plan and rank count; engine "tb" only, no copy_swap;
+            on more than one rank periodic x runs on the loopback, host-thread
+            and torch.distributed (host-staged) transports (insulated x: every
+            transport); "insulated" not with arith "fast".
     """
 
     def __init__(self, problem: Problem, *, dtype: str = "fp64", backend: str = "auto", tb: int = 0,
@@ -222,7 +225,7 @@ class HeatSolver:
         return {"tb": tb.value, "band": band.value, "steps": steps.value, "field": field.value,
                 "stream": stream.value, "backend": self.backend, "transport": self.transport.name,
                 "arith": _arith(self._h),  # the resolved code: 0 exact, 1 fma, 2 jacobi, 3 fast
-                "bc_x": self._bc()[0], "bc_y": self._bc()[1],  # "dirichlet" | "periodic", as the native solver runs
+                "bc_x": self._bc()[0], "bc_y": self._bc()[1],  # "dirichlet" | "periodic" | "insulated", as the native solver runs
                 "rank": self.rank, "size": self.size, "layout": self.layout.as_dict()}
 
     def _bc(self) -> tuple:
@@ -382,7 +385,8 @@ class HeatSolver:
         """This rank's rows with their frame, (nrows + 2) x (ncols + 2): local
         rows -1 .. nrows (the global frame rows on the first / last rank, else
         the neighbours' rows) and columns -1 .. ncols. On a periodic axis the
-        frame entries are wrap images of the owned points."""
+        frame entries are wrap images of the owned points, on an insulated one
+        images of the adjacent owned point."""
         out = np.empty((self.nrows + 2, self.ncols + 2), dtype=self.np_dtype)
         N.call("heat2d_solver_download_region", self._h, -1, self.nrows + 1, -1, self.ncols + 1,
                out.ctypes.data_as(C.c_void_p), self.ncols + 2)
@@ -392,8 +396,8 @@ class HeatSolver:
         """Set this rank's owned rows (collective: followed by a halo exchange).
         ``arr``: the owned points (nrows, ncols), or the frame-inclusive local
         field (nrows + 2, ncols + 2) — then the frame lines of a Dirichlet axis
-        are set too, and the entries on a periodic axis are ignored (they become
-        wrap images of the owned points)."""
+        are set too, and the entries on a periodic or insulated axis are ignored
+        (they become wrap / edge images of the owned points)."""
         a = np.ascontiguousarray(arr, dtype=self.np_dtype)
         if a.shape == (self.nrows + 2, self.ncols + 2):
             N.call("heat2d_solver_upload_field", self._h, a.ctypes.data_as(C.c_void_p), self.ncols + 2)

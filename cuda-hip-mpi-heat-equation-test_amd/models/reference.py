@@ -46,26 +46,38 @@ def initial_field(problem: Problem, dtype=np.float64) -> np.ndarray:
     return np.ascontiguousarray(T, dtype=np.float64).astype(dtype)
 
 
+_PAD_MODE = {"periodic": "wrap", "insulated": "edge"}
+
+
 def wrap_frame(T: np.ndarray, bc_x: str = "dirichlet", bc_y: str = "dirichlet") -> np.ndarray:
     """The frame-inclusive field with its frame entries on periodic axes
-    replaced by wrap images of the owned points (``np.pad(mode="wrap")``). With
-    only y periodic the Dirichlet frame rows wrap too: the point (0, -1) reads
-    (-1, -1). Dirichlet on both axes: T itself."""
+    replaced by wrap images of the owned points (``np.pad(mode="wrap")``) and on
+    insulated axes by images of the adjacent owned point (``mode="edge"``: the
+    wall sits half a cell outside the first and last owned point, T[0] = T[1],
+    T[n+1] = T[n]). With only y periodic / insulated the Dirichlet frame rows
+    get images at their ends too: the point (0, -1) reads (-1, -1) / (0, 0).
+    x is padded first, then y over the padded rows. Dirichlet on both axes: T
+    itself."""
     for name, bc in (("bc_x", bc_x), ("bc_y", bc_y)):
-        if bc not in ("dirichlet", "periodic"):
-            raise ValueError(f"{name} must be 'dirichlet' or 'periodic', got {bc!r}")
-    px, py = bc_x == "periodic", bc_y == "periodic"
+        if bc not in ("dirichlet", "periodic", "insulated"):
+            raise ValueError(f"{name} must be 'dirichlet', 'periodic' or 'insulated', got {bc!r}")
+    px, py = bc_x != "dirichlet", bc_y != "dirichlet"
     if not (px or py):
         return T
-    core = T[(1 if px else 0):(-1 if px else None), (1 if py else 0):(-1 if py else None)]
-    return np.pad(core, ((1, 1) if px else (0, 0), (1, 1) if py else (0, 0)), mode="wrap")
+    out = T[(1 if px else 0):(-1 if px else None), (1 if py else 0):(-1 if py else None)]
+    if px:
+        out = np.pad(out, ((1, 1), (0, 0)), mode=_PAD_MODE[bc_x])
+    if py:
+        out = np.pad(out, ((0, 0), (1, 1)), mode=_PAD_MODE[bc_y])
+    return out
 
 
 def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet") -> np.ndarray:
     """One FTCS step of a frame-inclusive field. On a Dirichlet axis the frame
-    is kept fixed; on a periodic one it is refreshed from the owned points
-    before the step (:func:`wrap_frame`) — the update and its operation order
-    are the same — and holds the wrap images of T at time t on return.
+    is kept fixed; on a periodic or insulated one it is refreshed from the
+    owned points before the step (:func:`wrap_frame`) — the update and its
+    operation order are the same — and holds the images of T at time t on
+    return.
     arith "jacobi" (r == 1/4 only): r * sum, the zero centre weight folded
     away — the engine's arith 2."""
     T = wrap_frame(T, bc_x, bc_y)
@@ -89,7 +101,7 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
 def ftcs(problem: Problem, nsteps: int | None = None, dtype=np.float64, T0: np.ndarray | None = None,
          arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet") -> np.ndarray:
     """Run FTCS; returns the frame-inclusive field (frame entries on periodic
-    axes: wrap images of the returned owned points)."""
+    / insulated axes: wrap / edge images of the returned owned points)."""
     T = initial_field(problem, dtype) if T0 is None else T0.astype(dtype)
     n = problem.ntime if nsteps is None else nsteps
     for _ in range(n):
@@ -154,6 +166,19 @@ def periodic_eigenmode(r: float, n: int, nsteps: int, k: int = 1, l: int = 1) ->
     i = np.arange(n)
     T0 = np.cos(2 * np.pi * k * i / n)[:, None] * np.cos(2 * np.pi * l * i / n)[None, :]
     return T0 * periodic_eigen_factor(r, n, k, l) ** nsteps
+
+
+def insulated_eigen_factor(r: float, n: int, p: int = 1, q: int = 1) -> float:
+    """Per-step amplification of the mode cos(p pi (i + 1/2) / n) cos(q pi (j + 1/2) / n)
+    on the fully insulated n x n grid: g = 1 - 4r (sin^2(p pi / 2n) + sin^2(q pi / 2n))."""
+    return 1.0 - 4.0 * r * (np.sin(np.pi * p / (2 * n)) ** 2 + np.sin(np.pi * q / (2 * n)) ** 2)
+
+
+def insulated_eigenmode(r: float, n: int, nsteps: int, p: int = 1, q: int = 1) -> np.ndarray:
+    """Closed-form FTCS solution (owned n x n points) from that mode: g^nsteps T_0."""
+    i = np.arange(n) + 0.5
+    T0 = np.cos(np.pi * p * i / n)[:, None] * np.cos(np.pi * q * i / n)[None, :]
+    return T0 * insulated_eigen_factor(r, n, p, q) ** nsteps
 
 
 def eigenmode(problem: Problem, nsteps: int) -> np.ndarray:

@@ -42,10 +42,16 @@ def arith_code(arith: str, r: float) -> int:
     return ARITH[arith]
 BACKEND_HIP, BACKEND_CPU = 0, 1
 # boundary condition of an axis (Config.bc_x / bc_y); the raw ops take the bit
-# set BC_PERIODIC_X | BC_PERIODIC_Y (kernels.hpp)
-BC = {"dirichlet": 0, "periodic": 1}
+# set BC_PERIODIC_X | BC_PERIODIC_Y | BC_INSULATED_X | BC_INSULATED_Y (kernels.hpp)
+BC = {"dirichlet": 0, "periodic": 1, "insulated": 2}
 BC_NAMES = {v: k for k, v in BC.items()}
-BC_PERIODIC_X, BC_PERIODIC_Y = 1, 2
+BC_PERIODIC_X, BC_PERIODIC_Y, BC_INSULATED_X, BC_INSULATED_Y = 1, 2, 4, 8
+
+
+def bc_bits(bc_x: str, bc_y: str) -> int:
+    """The raw ops' bit set of a pair of axis names."""
+    x, y = bc_code(bc_x, "bc_x"), bc_code(bc_y, "bc_y")
+    return ((BC_PERIODIC_X, BC_INSULATED_X)[x - 1] if x else 0) | ((BC_PERIODIC_Y, BC_INSULATED_Y)[y - 1] if y else 0)
 
 
 def bc_code(name: str, what: str = "bc") -> int:

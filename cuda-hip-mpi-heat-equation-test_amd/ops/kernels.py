@@ -94,7 +94,11 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
     ``bc_y="periodic"``: no column is pinned — ``src`` must hold wrap images in
     its ghost columns (:func:`wrap_cols`), and the ghost columns of the rows
     written are refreshed in ``dst``. ``bc_x="periodic"``: no row is pinned
-    (the ghost rows hold wrap images: :func:`wrap_rows`)."""
+    (the ghost rows hold wrap images: :func:`wrap_rows`). ``"insulated"`` on
+    either axis: a point next to the wall takes its own value for the operand
+    beyond it, at every level (``src``'s frame entries on that axis are not
+    read by an owned point), and the frame images of the rows written are
+    refreshed in ``dst``; not with arith "fast"."""
     _check_field(src, layout)
     _check_field(dst, layout)
     if src.dtype != dst.dtype or src.device != dst.device:
@@ -103,7 +107,7 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
         raise ValueError("tb_step is out-of-place (ping-pong fields)")
     rb, re = (0, layout.nrows) if rows is None else rows
     ar = N.arith_code(arith, r)
-    bc = (N.BC_PERIODIC_X if N.bc_code(bc_x, "bc_x") else 0) | (N.BC_PERIODIC_Y if N.bc_code(bc_y, "bc_y") else 0)
+    bc = N.bc_bits(bc_x, bc_y)
     if src.is_cuda:
         N.call("heat2d_tb_bc", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
                C.byref(layout), rb, re, k, r, _stream(src), tile_rows, ar, bc)

@@ -52,11 +52,12 @@ def build_parser():
                          "number, auto (GPU ranks: measured before the run — every rank times its own slab on a "
                          "1-rank loop exchange, uniform and shifted, parallel/select.balance_edges, as bench.py "
                          "does) or measure (the same on any backend)")
-    ap.add_argument("--bc-x", default=None, choices=["dirichlet", "periodic"],
+    ap.add_argument("--bc-x", default=None, choices=["dirichlet", "periodic", "insulated"],
                     help="boundary condition of the x (row) axis, the one decomposed over ranks (default: "
                          "dirichlet, or a restart's checkpointed setting; a flag that contradicts the checkpoint "
-                         "fails). periodic on more than one rank: host-staged halos (--transport auto picks them)")
-    ap.add_argument("--bc-y", default=None, choices=["dirichlet", "periodic"],
+                         "fails). periodic on more than one rank: host-staged halos (--transport auto picks them); "
+                         "insulated: a zero-flux wall, any transport")
+    ap.add_argument("--bc-y", default=None, choices=["dirichlet", "periodic", "insulated"],
                     help="boundary condition of the y (column) axis")
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--ntime", type=int, default=None)
@@ -384,7 +385,7 @@ def _write_inclusive(s, prob, path, world):
     T = np.empty((m + 2, m + 2), dtype=full.dtype)
     T[1:-1, 1:-1] = full
     # frame values: the IC on the frame (kept fixed by the solver); on a
-    # periodic axis the wrap images of the owned points
+    # periodic / insulated axis the wrap / edge images of the owned points
     from heat2d.models.reference import initial_field, wrap_frame
     frame = initial_field(prob, full.dtype)
     T[0, :], T[-1, :], T[:, 0], T[:, -1] = frame[0, :], frame[-1, :], frame[:, 0], frame[:, -1]
