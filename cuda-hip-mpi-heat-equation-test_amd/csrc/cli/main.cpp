@@ -82,6 +82,9 @@ struct Args {
   // --bc-x / --bc-y dirichlet|periodic|insulated (SolverConfig::bc_x / bc_y; x = rows, decomposed over ranks).
   // Empty: not given — dirichlet, or a restart's checkpointed setting
   std::string bc_x, bc_y;
+  // --source FILE.npy: heat source, the frame-inclusive (n+2) x (n+2) per-step increment dt * f
+  // (SolverConfig::source; converted to the run's dtype, a wrong shape fails)
+  std::string source;
 };
 
 void usage() {
@@ -93,7 +96,8 @@ void usage() {
       "              [--time-transfers]\n"
       "              [--checkpoint DIR [--checkpoint-every N]] [--restart DIR]\n"
       "              [--transport auto|rccl|peer] [--share-gpu] [--autotune auto|on|off] [--edge-shift N]\n"
-      "              [--bc-x dirichlet|periodic|insulated] [--bc-y dirichlet|periodic|insulated]\n");
+      "              [--bc-x dirichlet|periodic|insulated] [--bc-y dirichlet|periodic|insulated]\n"
+      "              [--source FILE.npy]\n");
 }
 
 Args parse_args(int argc, char** argv) {
@@ -138,6 +142,7 @@ Args parse_args(int argc, char** argv) {
     else if (s == "--restart") a.restart = need("--restart");
     else if (s == "--transport") a.transport = need("--transport");
     else if (s == "--share-gpu") a.share_gpu = true;
+    else if (s == "--source") a.source = need("--source");
     else if (s == "--bc-x" || s == "--bc-y") {
       const std::string v = need(s.c_str());
       if (v != "dirichlet" && v != "periodic" && v != "insulated") {
@@ -192,6 +197,9 @@ struct Shared {
   int64_t start_step = 0;  // > 0 after --restart
   std::string arith_used;  // the arithmetic the run used (auto resolved)
   double t_h2d = 0, t_d2h = 0;  // --time-transfers: rank 0's whole-field copies inside the timed region
+  // --source: the global array in the run's dtype (read by the first rank to need it, under mu) and its digest
+  std::vector<char> source;
+  std::string source_sha256;
 };
 
 // Collective checkpoint (every rank its slab, then rank 0 publishes meta.json).
@@ -219,6 +227,7 @@ void save_checkpoint(Shared& sh, Solver& s, Transport& tr, int rank, int64_t ste
     const char* const bc_names[3] = {"dirichlet", "periodic", "insulated"};
     m.bc_x = bc_names[s.config().bc_x];
     m.bc_y = bc_names[s.config().bc_y];
+    m.source_sha256 = sh.source_sha256;  // (empty: no source, written as null)
     ckpt::write_meta(a.checkpoint, name, m);
   }
   tr.barrier();
@@ -291,6 +300,12 @@ void run_rank(Shared& sh, int rank) {
     // (auto: slabs of >= 2^24 points — decided from the thinnest slab, the same on every rank)
     cfg.autotune = a.autotune;
     cfg.edge_shift = a.edge_shift;
+    if (!a.source.empty()) {
+      cfg.source = 1;
+      std::lock_guard<std::mutex> g(sh.mu);
+      if (sh.source.empty())
+        sh.source = ckpt::read_source(a.source, sh.prob.n_owned + 2, sh.prob.n_owned + 2, cfg.dtype, &sh.source_sha256);
+    }
     // boundary conditions: the flags, or a restart's checkpointed settings (a
     // flag that says otherwise fails: the resumed run would not be the saved one)
     std::string bc_x = a.bc_x.empty() ? "dirichlet" : a.bc_x, bc_y = a.bc_y.empty() ? "dirichlet" : a.bc_y;
@@ -302,6 +317,14 @@ void run_rank(Shared& sh, int rank) {
                      "--bc-y " + a.bc_y + " conflicts with the checkpoint's bc_y = " + m0.bc_y);
       bc_x = m0.bc_x;
       bc_y = m0.bc_y;
+      // a restart must be given the source the checkpointed run had (it is not saved), and no other
+      if (m0.source_sha256 != sh.source_sha256) {
+        HEAT2D_REQUIRE(!m0.source_sha256.empty(), "the checkpoint was written without a heat source, this run has one (--source)");
+        HEAT2D_REQUIRE(!sh.source_sha256.empty(), "the checkpoint was written with a heat source: give the restart the same "
+                                                  "--source (sha256 " + m0.source_sha256 + ")");
+        fail(__FILE__, __LINE__, "the restart's heat source differs from the checkpoint's (sha256 " + sh.source_sha256 +
+                                     " != " + m0.source_sha256 + ")");
+      }
     }
     auto bc_code = [](const std::string& v) { return v == "periodic" ? kBcPeriodic : v == "insulated" ? kBcInsulated : kBcDirichlet; };
     cfg.bc_x = bc_code(bc_x);
@@ -316,7 +339,8 @@ void run_rank(Shared& sh, int rank) {
       // auto: the r = 1/4 form when it rounds exactly like the reference for
       // the whole run — the IC in [m, 2m] (the reference's: 1 and 2) keeps
       // every sum - 4c exact; a restart's data is not known to be
-      if (sh.prob.r == 0.25 && ic_sterbenz_safe(sh.prob.ic) && a.restart.empty() && cfg.engine == 0) {
+      // (with a source auto stays with the solver: fma or exact, never jacobi)
+      if (sh.prob.r == 0.25 && ic_sterbenz_safe(sh.prob.ic) && a.restart.empty() && cfg.engine == 0 && !cfg.source) {
         cfg.arith = 2;
         arith_used = "jacobi (auto)";
       } else {
@@ -327,6 +351,7 @@ void run_rank(Shared& sh, int rank) {
     }
     if (root) sh.arith_used = arith_used;
     Solver s(cfg, tr);
+    if (cfg.source) s.set_source(sh.source.data(), sh.prob.n_owned + 2);
     s.init(sh.prob.ic, sh.prob.x.data(), sh.prob.x.data());
     const bool inclusive = sh.prob.conv == Convention::Inclusive;
     int64_t start = 0;

@@ -107,8 +107,12 @@ void ins_cols_impl(T* f, const SlabLayout& L, int64_t r0, int64_t r1) {
 // device march's substitution, tb_impl.hpp March INS) — here by giving the
 // frame entry beside it that value before each level reads it; the frame
 // images of the rows written are refreshed.
+// q (a heat source in the field's layout, Dirichlet axes only): every level adds
+// its row of q to the updated owned points, T' = update + q, as an add of its
+// own (the device march's tb_impl.hpp March SRC); pinned points are copied.
 template <typename T>
-void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re, int k, T r, int arith, int bc) {
+void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re, int k, T r, int arith, int bc,
+             const T* q = nullptr) {
   const SlabLayout L = kern::bc_layout(L0, bc & kern::kBcPeriodicX);  // (the columns: free_cols below)
   const bool free_cols = (bc & kern::kBcPeriodicY) != 0;
   const bool ins_x = (bc & kern::kBcInsulatedX) != 0, ins_y = (bc & kern::kBcInsulatedY) != 0;
@@ -151,6 +155,10 @@ void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re,
           continue;
         }
         row_update(up, mid, dn, out, L.ncols + 2 * g, r);
+        if (q) {
+          const T* qr = q + L.offset(row, 0);
+          for (int64_t j = 0; j < L.ncols; ++j) out[j] = out[j] + qr[j];
+        }
       }
     }, L.ncols);
     std::swap(a, b);
@@ -243,7 +251,7 @@ int num_threads() {
 }
 
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end,
-        int k, double r, int arith, int bc) {
+        int k, double r, int arith, int bc, const void* source) {
   HEAT2D_REQUIRE(k >= 1 && k <= L.halo, "k out of range");
   HEAT2D_REQUIRE(arith >= 0 && arith <= 3, "arith must be 0, 1, 2 or 3");
   HEAT2D_REQUIRE(arith != 2 || r == 0.25, "arith 2 (jacobi) needs r == 1/4 exactly");
@@ -252,12 +260,16 @@ void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_b
   // contracted form (arith 1), within the same stated bound of exact
   HEAT2D_REQUIRE(arith != 3 || !(bc & (kern::kBcInsulatedX | kern::kBcInsulatedY)),
                  "insulated boundaries have no arith 3 (fast) kernels");
+  HEAT2D_REQUIRE(!source || ((arith == 0 || arith == 1) && bc == 0),
+                 "a heat source needs arith 0 (exact) or 1 (fma) and Dirichlet boundaries on both axes");
   if (arith == 3) arith = 1;
   if (row_end <= row_begin) return;
   if (dt == DType::F32)
-    tb_impl<float>(static_cast<const float*>(src), static_cast<float*>(dst), L, row_begin, row_end, k, (float)r, arith, bc);
+    tb_impl<float>(static_cast<const float*>(src), static_cast<float*>(dst), L, row_begin, row_end, k, (float)r, arith, bc,
+                   static_cast<const float*>(source));
   else
-    tb_impl<double>(static_cast<const double*>(src), static_cast<double*>(dst), L, row_begin, row_end, k, r, arith, bc);
+    tb_impl<double>(static_cast<const double*>(src), static_cast<double*>(dst), L, row_begin, row_end, k, r, arith, bc,
+                    static_cast<const double*>(source));
 }
 
 void init(DType dt, void* field, const SlabLayout& L, const kern::IcParams& ic, const double* xc,

@@ -4,6 +4,7 @@
 #pragma once
 
 #include <string>
+#include <vector>
 
 #include "heat2d/runtime.hpp"
 
@@ -19,8 +20,17 @@ struct Meta {
   double sigma = 0, nu = 0, dom_len = 0, r = 0;
   int64_t edge_shift = 0;  // the writer's decomposition (common.hpp decompose); absent in older saves: 0
   std::string bc_x = "dirichlet", bc_y = "dirichlet";  // dirichlet | periodic | insulated; absent in older saves: dirichlet
+  // the run's heat source: SHA-256 (hex) of the global frame-inclusive array's bytes in the run's
+  // dtype, as utils/checkpoint.py records it; empty: none (null, or absent in older saves)
+  std::string source_sha256;
   std::string dir;  // read_meta: the directory holding this step's files
 };
+// A heat source file (--source FILE.npy): a 2-D little-endian f4 / f8 array of exactly rows x cols
+// (the frame-inclusive grid; another shape fails), converted to `dtype` (0 fp32, 1 fp64). *sha256
+// receives the digest of the converted bytes (Meta::source_sha256).
+std::vector<char> read_source(const std::string& path, int64_t rows, int64_t cols, int dtype, std::string* sha256);
+// SHA-256 of a byte range, lower-case hex
+std::string sha256_hex(const void* data, size_t bytes);
 
 // Layout (v2): DIR/step-NNNNNNNNNNNN[-G]/{rankNNNNN.npy, meta.json} +
 // DIR/latest, a one-line pointer to the newest COMPLETE step directory.

@@ -54,6 +54,9 @@ constexpr int64_t kColPad = 32;
 constexpr int kMaxTB = 24;
 constexpr int kMaxTBF32 = 24;
 inline int max_tb(DType dt) { return dt == DType::F64 ? kMaxTB : kMaxTBF32; }
+// Deepest pass with a heat source (tb_kernel_src is instantiated for depths
+// 1..kMaxTBSrc, both dtypes; a solver with a source clamps its depth to it).
+constexpr int kMaxTBSrc = 16;
 // Default halo depth (ghost rows per side). Must be >= temporal depth used.
 constexpr int64_t kDefaultHalo = kMaxTB;
 

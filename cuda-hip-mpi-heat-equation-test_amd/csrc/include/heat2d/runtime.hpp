@@ -62,6 +62,14 @@ struct SolverConfig {
   // x is the row axis (decomposed over ranks), y the column axis.
   int32_t bc_x;
   int32_t bc_y;
+  // 1: the solver carries a heat source (u_t = nu lap(u) + f): a third buffer
+  // in the field's layout, filled by Solver::set_source with the per-step
+  // increment S = dt * f and added at every fused level (kernels.hpp
+  // launch_tb `source`). Dirichlet on both axes, arith exact / fma (auto never
+  // picks another), engine "tb", no copy_swap; the depth is clamped to
+  // kMaxTBSrc. 0: no source, today's solver.
+  int32_t source;
+  int32_t pad0;
 };
 constexpr int32_t kBcDirichlet = 0, kBcPeriodic = 1, kBcInsulated = 2;
 // the kernels' bit set (kernels.hpp kBcPeriodicX / ... / kBcInsulatedY) of a config
@@ -245,7 +253,7 @@ std::shared_ptr<Transport> make_ipc_loop_transport(int device);
 
 namespace cpu {
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
-        int64_t row_end, int k, double r, int arith = 0, int bc = 0);
+        int64_t row_end, int k, double r, int arith = 0, int bc = 0, const void* source = nullptr);
 void wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1);
 void wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k);
 // insulated frame images (kern::launch_ins_cols / launch_ins_rows)
@@ -325,8 +333,9 @@ Footprint solver_footprint(const SolverConfig& cfg, int rank, int nranks);
 // `nranks` ranks fits budget_bytes per GPU (the largest slab, rank 0's,
 // decides). The reference sizes nothing: its grid is input.dat's n, with a
 // whole-field host mirror (fortran/hip/heat.F90:161-176); here the IC is made
-// on the device, so only the two device fields count.
-int64_t plan_max_grid(int dtype, int nranks, int64_t budget_bytes, int64_t halo = 0);
+// on the device, so only the two device fields count (three with a heat
+// source: SolverConfig::source).
+int64_t plan_max_grid(int dtype, int nranks, int64_t budget_bytes, int64_t halo = 0, bool source = false);
 
 class Solver {
  public:
@@ -415,6 +424,15 @@ class Solver {
   // lines included (both buffers); no halo exchange (exchange_post / exchange_now follow)
   void upload_framed(const void* host, int64_t ld);
   void upload_field(const void* host, int64_t ld);  // upload_framed, then the halo exchange (collective, as upload)
+  // The heat source (SolverConfig::source = 1): `host` is the GLOBAL
+  // frame-inclusive array, (nrows_global + 2) x (ncols + 2) in the field's
+  // dtype, leading dimension ld; this rank copies its rows, ghost rows
+  // included (the source does not change in time: never exchanged). Frame
+  // entries are ignored: the solver's copy holds -0.0 in every frame row /
+  // column and pad entry. nullptr clears the source: the solver runs as one
+  // without. Between step() calls; invalidates nothing but the captured graphs.
+  void set_source(const void* host, int64_t ld);
+  bool has_source() const { return src_on_; }
   // Cycles launched by step() since the last reset, by depth: hist[k] for
   // k = 0..kMaxTB (graph replays count their two cycles each).
   void cycle_hist(int64_t out[kMaxTB + 1], bool reset);
@@ -512,6 +530,9 @@ class Solver {
   bool pipe_ok(int k) const;
   bool hip_ = true;
   void* buf_[2] = {nullptr, nullptr};
+  void* src_buf_ = nullptr;  // the heat source (cfg_.source), in L_'s layout
+  bool src_on_ = false;      // set_source has filled it
+  const void* source() const { return src_on_ ? src_buf_ : nullptr; }
   int cur_ = 0;
   int64_t steps_ = 0;
   int64_t band_ = 0;     // largest boundary band / halo exchange depth (= K)
@@ -593,6 +614,7 @@ class LoopbackGroup {
   void upload(const void* host, int64_t ld);  // whole global owned region, then a halo exchange
   // the whole frame-inclusive field (n + 2) x (n_cols + 2) (Solver::upload_framed per member), then a halo exchange
   void upload_field(const void* host, int64_t ld);
+  void set_source(const void* host, int64_t ld);  // Solver::set_source on every member (the global array)
   int nranks() const { return (int)members_.size(); }
   Solver& member(int i) { return *members_[i]; }
 

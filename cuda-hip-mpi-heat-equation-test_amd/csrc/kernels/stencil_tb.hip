@@ -291,6 +291,13 @@ int occupancy_ins(DType dt, int k, int arith) {
   });
 }
 
+// Heat source (tb_kernel_src): resident waves per CU (one-wave workgroups)
+int occupancy_src(DType dt, int k, int arith) {
+  HEAT2D_REQUIRE(arith == 0 || arith == 1, "a heat source needs arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 have no source kernels");
+  if (arith == 1) return dt == DType::F32 ? occupancy_waves_src<float, 1>(k) : occupancy_waves_src<double, 1>(k);
+  return dt == DType::F32 ? occupancy_waves_src<float, 0>(k) : occupancy_waves_src<double, 0>(k);
+}
+
 // The frame entries the launchers keep behind a stencil launch over `rects`:
 // periodic y the ghost columns, insulated y the frame columns, insulated x the
 // frame row of a slab at the wall — one fill per run of rows the rects cover
@@ -335,9 +342,19 @@ void fill_frames(DType dt, void* dst, const SlabLayout& L0, const TbRect* rects,
 // layout (the kernels see bc_layout(L, bc)). Insulated edges: a general launch
 // runs tb_kernel_ins (ring 4, whatever `ring` says) with the insulated edges as
 // its extra argument. The frame entries are refreshed by the caller (launch_rects).
+// source != nullptr (a buffer in the field's layout, Dirichlet axes only):
+// every launch, interior ones too, runs tb_kernel_src (general, ring 4) on at
+// most as many waves as that kernel keeps resident.
 int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
                        const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
-                       double* partials, uint32_t* queue, int bc, bool pipe) {
+                       double* partials, uint32_t* queue, int bc, bool pipe, const void* source = nullptr) {
+  if (source) {
+    HEAT2D_REQUIRE(bc == 0, "a heat source needs Dirichlet boundaries on both axes");
+    HEAT2D_REQUIRE(!partials && !pipe, "a heat source has no fused-statistics and no wave-pair kernel");
+    HEAT2D_REQUIRE(k <= kMaxTBSrc, "temporal depth exceeds the heat-source kernels' deepest pass (kMaxTBSrc)");
+    nwaves = std::min<int64_t>(nwaves, (int64_t)cu_count() * occupancy_src(dt, k, arith));
+    main = false;
+  }
   HEAT2D_REQUIRE(nrect >= 1 && nrect <= (main ? kMainRects : kMaxRects), "bad rect count");
   HEAT2D_REQUIRE(!pipe || (main && !partials && pipe_available(dt, k, arith)), "no wave-pair kernel for this launch");
   const int ins = main ? 0 : ins_edges(bc);  // (interior launches: launch_rects keeps insulated edges out of them)
@@ -378,7 +395,9 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
   a.nitems = items;
   a.nwaves = std::max<int64_t>(1, std::min<int64_t>(nwaves, items));
   a.partials = partials;
-  a.wtimes = pipe ? nullptr : wave_times_buf(a.nwaves);  // (the pair kernel records no wave times)
+  // (the pair kernel and the heat-source kernel record no wave times: HEAT2D_WAVE_TIMES keeps
+  // the last other launch's)
+  a.wtimes = (pipe || source) ? nullptr : wave_times_buf(a.nwaves);
   if (arith == 3) {  // scaled levels (tb_impl.hpp AR 3): coefficients of this depth, in double
     HEAT2D_REQUIRE(r > 0.0, "arith 3 (fast) needs r > 0");
     a.fb = (1.0 - 4.0 * r) / r;
@@ -397,6 +416,16 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
       dispatch_pipe<decltype(ar)::value>(k, (unsigned)((a.nwaves + 1) / 2), static_cast<const double*>(src) + o,
                                          static_cast<double*>(dst) + o, a, r, status, stream);
     });
+  } else if (source) {
+    if (dt == DType::F32) {
+      const float *s32 = static_cast<const float*>(src) + o, *q32 = static_cast<const float*>(source) + o;
+      if (arith == 1) dispatch_src<float, 1>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, (float)r, q32, stream);
+      else dispatch_src<float, 0>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, (float)r, q32, stream);
+    } else {
+      const double *s64 = static_cast<const double*>(src) + o, *q64 = static_cast<const double*>(source) + o;
+      if (arith == 1) dispatch_src<double, 1>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, r, q64, stream);
+      else dispatch_src<double, 0>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, r, q64, stream);
+    }
   } else if (ins) {
     with_ar(arith, [&](auto ar) {
       constexpr int AR = decltype(ar)::value;
@@ -440,16 +469,18 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
 // columns of the same rows).
 int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
                      const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
-                     double* partials = nullptr, uint32_t* queue = nullptr, int bc = 0, bool pipe = false) {
+                     double* partials = nullptr, uint32_t* queue = nullptr, int bc = 0, bool pipe = false,
+                     const void* source = nullptr) {
   HEAT2D_REQUIRE((bc & ~kBcAll) == 0, "bc must be a set of kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY");
   HEAT2D_REQUIRE(!((bc & kBcPeriodicX) && (bc & kBcInsulatedX)) && !((bc & kBcPeriodicY) && (bc & kBcInsulatedY)),
                  "an axis is periodic or insulated, not both");
   if (!(main && (bc & kBcInsulatedY))) {
     const int64_t nw = launch_rects_1(dt, src, dst, L0, k, ring, main, rects, nrect, nwaves, r, stream, arith, partials,
-                                      queue, bc, pipe);
+                                      queue, bc, pipe, source);
     fill_frames(dt, dst, L0, rects, nrect, bc, stream);
     return nw;
   }
+  HEAT2D_REQUIRE(!source, "a heat source needs Dirichlet boundaries on both axes");
   HEAT2D_REQUIRE(!pipe, "insulated y: the wave-pair kernel's wide strips are not carved (no pipe plans)");
   HEAT2D_REQUIRE(nrect >= 1 && nrect <= kMainRects, "bad rect count");
   const int64_t U = useful_width(dt, k);
@@ -534,12 +565,13 @@ TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end
 }
 
 void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end, int k,
-               double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc) {
-  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith, bc);
+               double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc, const void* source) {
+  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith, bc, source);
 }
 
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
-                int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc) {
+                int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc,
+                const void* source) {
   check_layout(dt, L, k);
   const int64_t n0 = std::max<int64_t>(0, re0 - rb0), n1 = std::max<int64_t>(0, re1 - rb1);
   if (n0 + n1 == 0) return;
@@ -553,7 +585,8 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
     const int64_t s0 = n1 == 0 ? ns : (n0 == 0 ? 0 : std::max<int64_t>(1, (ns * n0 + (n0 + n1) / 2) / (n0 + n1)));
     if (n0 > 0) rects[nr++] = TbRect{rb0, re0, 0, p.nstrips, -std::min<int64_t>(s0, n0 * p.nstrips)};
     if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, -std::min<int64_t>(std::max<int64_t>(1, ns - s0), n1 * p.nstrips)};
-    launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, p.nwaves, r, stream, arith, nullptr, nullptr, bc);
+    launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, p.nwaves, r, stream, arith, nullptr, nullptr, bc,
+                 false, source);
     return;
   }
   const int64_t nb = std::max<int64_t>(p.ntiles, (n0 > 0) + (n1 > 0));
@@ -561,7 +594,8 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
   if (n0 > 0) rects[nr++] = TbRect{rb0, re0, 0, p.nstrips, std::min<int64_t>(nb0, n0)};
   if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, std::min<int64_t>(nb - nb0, n1)};
   const int64_t slots = (int64_t)(cus > 0 ? cus : cu_count()) * p.blocks_per_cu * 4;
-  launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, slots, r, stream, arith, nullptr, nullptr, bc);
+  launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, slots, r, stream, arith, nullptr, nullptr, bc, false,
+               source);
 }
 
 // r = 1/4 kernels (arith 2): an interior item costs 3 adds + 2 DPP moves per
@@ -835,18 +869,19 @@ bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i) {
 }
 
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
-                      hipStream_t stream, int arith, int bc) {
+                      hipStream_t stream, int arith, int bc, const void* source) {
   HEAT2D_REQUIRE(i >= 0 && i < p.nedge, "edge rect index");
   const TbRect& R = p.edge[i];
   const bool on_main = edges_on_main(bc_layout(L, bc), p.k, &R, 1);
   const int64_t items = R.nb > 0 ? R.nb * (R.s1 - R.s0) : -R.nb;
   const int64_t slots = (int64_t)cu_count() * occupancy(dt, p.ring, on_main, p.k, arith) * 4;
   launch_rects(dt, src, dst, L, p.k, p.ring, on_main, &R, 1, std::min<int64_t>(items, slots), r, stream, arith,
-               nullptr, nullptr, bc);
+               nullptr, nullptr, bc, false, source);
 }
 
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
-                  double r, hipStream_t stream, int arith, uint32_t* queue, int bc) {
+                  double r, hipStream_t stream, int arith, uint32_t* queue, int bc, const void* source) {
+  HEAT2D_REQUIRE(!source || !(p.flags & kPlanPipe), "a heat source has no wave-pair kernel (no pipe plans)");
   // (SplitPlan::flags & kPlanDynamic: the main part takes its items from the dynamic queue)
   uint32_t* q = (p.flags & kPlanDynamic) ? queue : nullptr;
   HEAT2D_REQUIRE(p.valid, "invalid split plan");
@@ -855,15 +890,16 @@ void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, con
   const int nm = p.nrects > 0 ? p.nrects : 1;
   if (p.valid == 2) {  // single general launch over the whole slab (no edge part)
     if (main_part)
-      launch_rects(dt, src, dst, L, p.k, p.ring, false, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc);
+      launch_rects(dt, src, dst, L, p.k, p.ring, false, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc, false,
+                   source);
     return;
   }
   if (main_part)
     launch_rects(dt, src, dst, L, p.k, p.ring, true, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc,
-                 (p.flags & kPlanPipe) != 0);
+                 (p.flags & kPlanPipe) != 0, source);
   else
     launch_rects(dt, src, dst, L, p.k, p.ring, edges_on_main(bc_layout(L, bc), p.k, p.edge, p.nedge), p.edge, p.nedge,
-                 p.edge_waves, r, stream, arith, nullptr, nullptr, bc);
+                 p.edge_waves, r, stream, arith, nullptr, nullptr, bc, false, source);
 }
 
 }  // namespace kern

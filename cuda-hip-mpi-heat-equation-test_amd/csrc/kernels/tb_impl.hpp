@@ -327,8 +327,62 @@ struct WallState<true> {
   bool wall_w;
   uint32_t wall_e;
 };
-template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false>
-struct March : WallState<INS> {
+// SRC (tb_kernel_src, a heat source S added at every level: T' = update + S,
+// one separately rounded add per point and level): at march row m level s
+// works on row m + off(s), so K source rows are live at once and every row is
+// needed by K march rows in a row. The source rows travel beside the level-0
+// rows: each refill of a level-0 ring slot also loads that row of the source
+// buffer (same lanes, same descriptor, one more 16-B load per march row at the
+// same fixed place in the body, so the ring keeps its counted vmcnt) into the
+// slot's twin register Qb. When the row becomes the centre row (row m + 1, the
+// first a level needs: level 1) its 16 B per lane go into a ring of K rows in
+// LDS (1 KiB per row), and level s reads row m + s back with one 16-B LDS
+// read. A lane only ever reads what it wrote itself and the kernel runs one
+// wave per workgroup, so the ring is private to the wave: no barrier, no
+// counters, the wave's own LDS wait count is all the ordering there is. Row
+// m + K is read last at march row m and its slot is overwritten at row m - 1.
+// Pinned points need no masking: the solver's copy of the source holds -0.0 in
+// every frame row / column and pad entry, and x + (-0.0) keeps the bits of
+// every x. (The state lives in a base that is empty unless SRC, as WallState.)
+template <int K>
+__device__ __forceinline__ char* src_ring() {
+  __shared__ unsigned int __attribute__((ext_vector_type(4))) ring[(K > 1 ? K : 1) * 64];
+  return reinterpret_cast<char*>(ring);
+}
+template <int K, int RING, bool SRC>
+struct SrcState {};
+template <int K, int RING>
+struct SrcState<K, RING, true> {
+  using Q4 = unsigned int __attribute__((ext_vector_type(4)));
+  static constexpr int NR = K > 1 ? K : 1;  // LDS ring rows
+  const char* qrow;  // byte address of (row 0, column -cpad) in the source buffer [wave-uniform]
+  int64_t qdelta;    // qrow - srow: the source row of a level-0 row pointer
+  Q4 Qb[RING];       // source rows of the level-0 ring's rows (same slots)
+  int32_t qlane;     // this lane's byte offset in an LDS row
+  int32_t qw;        // ring slot of the newest row (m + 1), in bytes       [wave-uniform]
+  __device__ __forceinline__ void q_reset(int lane) {
+    qlane = lane * 16;
+    qw = 0;
+#pragma unroll
+    for (int q = 0; q < RING; ++q) Qb[q] = Q4{0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < NR; ++i) *reinterpret_cast<Q4*>(src_ring<K>() + i * 1024 + qlane) = Q4{0u, 0u, 0u, 0u};
+  }
+  // row m + 1 enters the ring (the slot of row m + K + 1, read last one march row ago)
+  __device__ __forceinline__ void q_push(const Q4& v) {
+    qw = (qw == 0 ? NR * 1024 : qw) - 1024;
+    *reinterpret_cast<Q4*>(src_ring<K>() + qw + qlane) = v;
+  }
+  // row m + s: pushed s - 1 march rows ago
+  __device__ __forceinline__ Q4 q_level(int s) const {
+    int32_t o = qw + (s - 1) * 1024;
+    o = o >= NR * 1024 ? o - NR * 1024 : o;
+    return *reinterpret_cast<const Q4*>(src_ring<K>() + o + qlane);
+  }
+};
+template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false,
+          bool SRC = false>
+struct March : WallState<INS>, SrcState<K, RING, SRC> {
   using S = TbShape<T, NV, K>;
   static constexpr int V = S::V;
   static constexpr int VM = S::VM;
@@ -336,6 +390,8 @@ struct March : WallState<INS> {
   using VT = typename Vec16<T>::type;
   using U4 = unsigned int __attribute__((ext_vector_type(4)));
   static_assert(RING % 2 == 0 && RING >= 4, "ring must be even (parity-indexed level rings) and >= 4");
+  static_assert(!SRC || (NV == 1 && CL == K && (AR == 0 || AR == 1) && !ST),
+                "source term: 16 B per lane, one chain, unscaled arithmetic, no fused statistics");
 
   const char* srow;  // byte address of (row 0, column -cpad) in src   [wave-uniform]
   char* drow;        // same in dst                                      [wave-uniform]
@@ -394,6 +450,11 @@ struct March : WallState<INS> {
       for (int e = 0; e < VM; ++e) w[e] = out[v * VM + e];
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(U4, w), rs, st_off + v * 16, 0, HEAT2D_STORE_AUX);
     }
+  }
+
+  // SRC: the source row of the level-0 row at p (same lanes; see SrcState)
+  __device__ __forceinline__ U4 load_q(const char* p, bool live) const {
+    return __builtin_amdgcn_raw_buffer_load_b128(row_rsrc(p + this->qdelta, live ? nrec : 0u), ld_off, 0, 0);
   }
 
   __device__ __forceinline__ void unpack(const VT (&x)[NV], T (&out)[V]) const {
@@ -474,6 +535,7 @@ struct March : WallState<INS> {
     constexpr int sN = P0, sC = (P0 + RING - 1) % RING, sS = (P0 + RING - 2) % RING;  // level-0 slots
     T part[V];
     T C0[V], N0[V];
+    if constexpr (SRC) this->q_push(this->Qb[sC]);  // source row m + 1 (loaded beside the centre row)
     {
       T S0[V];
       unpack(Lb[sS], S0);
@@ -488,9 +550,11 @@ struct March : WallState<INS> {
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (kIncPtr) {
         load_row_p(lp, nxt >= mload, Lb[sS]);
+        if constexpr (SRC) this->Qb[sS] = load_q(lp, nxt >= mload);
         lp -= pitch_b;
       } else {
         load_row(nxt >= mload ? nxt : mload, Lb[sS]);
+        if constexpr (SRC) this->Qb[sS] = load_q(srow + (int64_t)(nxt >= mload ? nxt : mload) * pitch_b, true);
       }
     }
     unpack(Lb[sN], N0);
@@ -513,6 +577,11 @@ struct March : WallState<INS> {
       // level s+1's S+E from level s's S (the slot about to be overwritten) and C
       if (s < K) partial(X[ps][s - 1], X[Ch::slot(PH, Ch::delta(s + 1), s)][s - 1], nxtpart, m + Ch::off(s + 1));
       update(part, C, N, m + Ch::off(s), out);
+      if constexpr (SRC) {  // + S(row m + off(s)): its own rounded add (-ffp-contract=off)
+        const VT q = __builtin_bit_cast(VT, this->q_level(s));
+#pragma unroll
+        for (int e = 0; e < V; ++e) out[e] = out[e] + q[e];
+      }
       if (s < K) {
 #pragma unroll
         for (int e = 0; e < V; ++e) X[ps][s - 1][e] = out[e];
@@ -575,6 +644,11 @@ struct March : WallState<INS> {
     for (int q = RING - 2; q < RING; ++q)
 #pragma unroll
       for (int v = 0; v < NV; ++v) Lb[q][v] = VT{};
+    if constexpr (SRC) {
+#pragma unroll
+      for (int q = 0; q < RING - 2; ++q)
+        this->Qb[q] = load_q(srow + (int64_t)(mtop - q >= mload ? mtop - q : mload) * pitch_b, true);
+    }
 #pragma unroll
     for (int p = 0; p < 3; ++p)
 #pragma unroll
@@ -614,13 +688,17 @@ struct March : WallState<INS> {
 // ~2x the registers: 209 VGPRs at K = 10). Same operation order and rounding
 // per element as March (bitwise identical); the loads / stores / ring /
 // descriptors / edge kinds are March's.
-template <int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false>
-struct MarchF32 : WallState<INS> {
+// SRC: a source row sits in LDS in the even/odd order (c0, c2, c1, c3), so a
+// level adds it with two packed adds (see SrcState).
+template <int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false, bool SRC = false>
+struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
   using F2 = float __attribute__((ext_vector_type(2)));
   using VT = float __attribute__((ext_vector_type(4)));
   using U4 = unsigned int __attribute__((ext_vector_type(4)));
   static constexpr int KX = K > 1 ? K - 1 : 1;
   static_assert(RING % 2 == 0 && RING >= 4, "ring must be even and >= 4");
+  static_assert(!SRC || (CL == K && (AR == 0 || AR == 1) && !ST),
+                "source term: one chain, unscaled arithmetic, no fused statistics");
   struct Row {
     F2 a, b;  // a = (c0, c2), b = (c1, c3)
   };
@@ -659,6 +737,11 @@ struct MarchF32 : WallState<INS> {
     const __amdgpu_buffer_rsrc_t rs = row_rsrc(p, live ? nrec : 0u);
     const VT v = __builtin_bit_cast(VT, __builtin_amdgcn_raw_buffer_load_b128(rs, ld_off, 0, 0));
     out = Row{F2{v.x, v.y}, F2{v.z, v.w}};
+  }
+  // SRC: the source row of the level-0 row at p (memory order; reordered when
+  // it enters the LDS ring, long after the load has landed: see SrcState)
+  __device__ __forceinline__ U4 load_q(const char* p, bool live) const {
+    return __builtin_amdgcn_raw_buffer_load_b128(row_rsrc(p + this->qdelta, live ? nrec : 0u), ld_off, 0, 0);
   }
   __device__ __forceinline__ void store_row(bool live, const VT& w) const {
     const __amdgpu_buffer_rsrc_t rs = row_rsrc(sp, live ? nrec : 0u);
@@ -793,11 +876,16 @@ struct MarchF32 : WallState<INS> {
     constexpr int P0 = PH % RING;
     constexpr int sN = P0, sC = (P0 + RING - 1) % RING, sS = (P0 + RING - 2) % RING;
     const Row C0 = Lb[sC];
+    if constexpr (SRC) {  // source row m + 1 (loaded beside the centre row), as (c0, c2, c1, c3)
+      const U4 q = this->Qb[sC];
+      this->q_push(U4{q.x, q.z, q.y, q.w});
+    }
     Row part = partial(Lb[sS], C0, m + Ch::off(1));
     {
       const int32_t nxt = m + 2 - RING;
       __builtin_amdgcn_sched_barrier(0);
       load_row_p(lp, nxt >= mload, Lb[sS]);
+      if constexpr (SRC) this->Qb[sS] = load_q(lp, nxt >= mload);
       lp -= pitch_b;
     }
     Lb[sN] = split(Lb[sN]);  // first use of this row: to even/odd form, in place
@@ -814,11 +902,19 @@ struct MarchF32 : WallState<INS> {
         const int ps = Ch::slot(PH, 0, s < K ? s : 1);
         const Row nxtpart = partial(X[ps][i], X[Ch::slot(PH, Ch::delta(s + 1), s < K ? s : 1)][i], m + Ch::off(s + 1));
         X[ps][i] = update(part, C, N, m + Ch::off(s));
+        if constexpr (SRC) {  // + S(row m + off(s)): its own rounded add (-ffp-contract=off)
+          const VT q = __builtin_bit_cast(VT, this->q_level(s));
+          X[ps][i] = Row{X[ps][i].a + F2{q.x, q.y}, X[ps][i].b + F2{q.z, q.w}};
+        }
         part = nxtpart;
       } else {
         const int32_t row = m + Ch::off(K);
         const bool live = (uint32_t)(row - t0) < (uint32_t)(t1 - t0);  // row in [t0, t1), wave-uniform
-        const VT w = update_last(part, C, N, row);
+        VT w = update_last(part, C, N, row);
+        if constexpr (SRC) {  // (w in memory order, the ring row as (c0, c2, c1, c3))
+          const VT q = __builtin_bit_cast(VT, this->q_level(K));
+          w = VT{w.x + q.x, w.y + q.z, w.z + q.y, w.w + q.w};
+        }
         store_row(live, w);
         if constexpr (ST) {
           if (live) {  // C in even/odd form: a = (c0, c2), b = (c1, c3)
@@ -859,6 +955,11 @@ struct MarchF32 : WallState<INS> {
     for (int q = 0; q < RING - 2; ++q) load_row(mtop - q >= mload ? mtop - q : mload, Lb[q]);
 #pragma unroll
     for (int q = RING - 2; q < RING; ++q) Lb[q] = Row{F2{0.f, 0.f}, F2{0.f, 0.f}};
+    if constexpr (SRC) {
+#pragma unroll
+      for (int q = 0; q < RING - 2; ++q)
+        this->Qb[q] = load_q(srow + (int64_t)(mtop - q >= mload ? mtop - q : mload) * pitch_b, true);
+    }
 #pragma unroll
     for (int p = 0; p < 3; ++p)
 #pragma unroll
@@ -897,9 +998,10 @@ constexpr bool kPackedF32 = false;
 constexpr int kInsRowLo = 1, kInsRowHi = 2, kInsColLo = 4, kInsColHi = 8;
 
 template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, bool PS = false, int CLX = 0,
-          bool INS = false>
+          bool INS = false, bool SRC = false>
 __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r, int64_t strip, int64_t t0,
-                                      int64_t t1, int lane, StatAcc* acc = nullptr, int ins = 0) {
+                                      int64_t t1, int lane, StatAcc* acc = nullptr, int ins = 0,
+                                      const T* qsrc = nullptr) {
   using S = TbShape<T, NV, K>;
   constexpr int V = S::V;
   constexpr int ES = (int)sizeof(T);
@@ -911,8 +1013,8 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
   // the chains' extra rows spill at fp64 K >= 21
   // (CLX > 0: an explicit chain length — the boundary-band kernel)
   constexpr int CL = CLX > 0 ? (CLX < K ? CLX : K) : (ST ? K : chain_len<T, K>());
-  using W = typename std::conditional<kPackedF32<T, NV>, MarchF32<K, EK, RING, AR, ST, CL, INS>,
-                                      March<T, NV, K, EK, RING, AR, ST, CL, INS>>::type;
+  using W = typename std::conditional<kPackedF32<T, NV>, MarchF32<K, EK, RING, AR, ST, CL, INS, SRC>,
+                                      March<T, NV, K, EK, RING, AR, ST, CL, INS, SRC>>::type;
   W w;
   // row base = column col_lo (= -cpad) of row 0; offsets are relative to it
   w.srow = reinterpret_cast<const char*>(src + a.col_lo);
@@ -961,6 +1063,11 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
 #pragma unroll
     for (int e = 0; e < V; ++e) me |= ((ins & kInsColHi) && mycol + e == a.ncols - 1) ? (1u << e) : 0u;
     w.wall_e = me;
+  }
+  if constexpr (SRC) {  // the source buffer has the field's layout
+    w.qrow = reinterpret_cast<const char*>(qsrc + a.col_lo);
+    w.qdelta = w.qrow - w.srow;
+    w.q_reset(lane);
   }
   if constexpr (ST) {
     uint32_t mask = 0;
@@ -1214,6 +1321,41 @@ __global__ __launch_bounds__(256) void tb_kernel_ins(const T* __restrict__ src, 
   queue_exit(a);
 }
 
+// The general kernel with a heat source (`q`: the source buffer, in the field's
+// layout, an argument of this kernel only — TbArgs and every other kernel stay
+// as they are): the same items and kinds; every item runs the march with the
+// source added at every level (March SRC). One wave per workgroup: the wave's
+// ring of K source rows in LDS (K KiB) is the workgroup's whole allocation.
+template <typename T, int NV, int K, int RING, int AR>
+__global__ __launch_bounds__(64) void tb_kernel_src(const T* __restrict__ src, T* __restrict__ dst, TbArgs a, T r,
+                                                    const T* __restrict__ q) {
+  using S = TbShape<T, NV, K>;
+  const int lane = threadIdx.x;
+  const int64_t wid = (int64_t)blockIdx.x;
+  if (wid >= a.nwaves) return;
+  int64_t it = wid;
+  int32_t lin = tb_span<kMaxRects>(a, it).lin;
+  while (it < a.nitems) {
+    int64_t strip, t0, t1;
+    if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {
+      it = next_item(a, it);
+      if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;
+      continue;
+    }
+    lin += (int32_t)(t1 - t0);
+    const int64_t c0 = strip * S::U - S::KA;
+    const int ek = (((t0 - K < a.fixed_lo) || (t1 + K > a.fixed_hi)) ? 1 : 0) |
+                   (((c0 < 0) || (c0 + S::W > a.ncols)) ? 2 : 0);
+    switch (ek) {
+      case 0: march<T, NV, K, 0, RING, AR, false, false, K, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q); break;
+      case 1: march<T, NV, K, 1, RING, AR, false, false, K, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q); break;
+      case 2: march<T, NV, K, 2, RING, AR, false, false, K, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q); break;
+      default: march<T, NV, K, 3, RING, AR, false, false, K, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q); break;
+    }
+  }
+  queue_exit(a);
+}
+
 template <typename T, int NV, int K, int RING, bool MAIN, int AR, int VAR = kVarPlain>
 constexpr auto kernel_ptr() {
   return &tb_kernel<T, NV, K, RING, MAIN, AR, VAR>;
@@ -1254,6 +1396,11 @@ template <typename T, int AR>
 void dispatch_ins(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, int ins, hipStream_t s);
 template <typename T, int AR>
 int occupancy_blocks_ins(int k);
+// heat-source kernels: general kernel, ring 4, depths 1..kMaxTBSrc (tb_<dtype>_src[_fma].hip)
+template <typename T, int AR>
+void dispatch_src(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, T r, const T* q, hipStream_t s);
+template <typename T, int AR>
+int occupancy_waves_src(int k);
 #define H2D_TB_CASE(T, RING, MAIN, AR, KK)                                                                    \
   case KK:                                                                                                    \
     hipLaunchKernelGGL((tb_kernel<T, 1, KK, RING, MAIN, AR>), dim3(nblocks), dim3(256), 0, s, src, dst, a, r); \
@@ -1379,6 +1526,53 @@ int blocks_per_cu_ins() {
         break;                                                                                                \
     }                                                                                                         \
     return 1;                                                                                                 \
+  }
+
+
+// resident waves (one-wave workgroups) per CU of one tb_kernel_src instance
+template <typename T, int K, int AR>
+int waves_per_cu_src() {
+  static std::mutex mu;
+  static std::map<int, int> cache;  // device -> waves/CU
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> g(mu);
+  auto it = cache.find(dev);
+  if (it != cache.end()) return it->second;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tb_kernel_src<T, 1, K, 4, AR>), 64,
+                                                   0) != hipSuccess ||
+      nb <= 0)
+    nb = 4;
+  cache[dev] = nb;
+  return nb;
+}
+#define H2D_SRC_CASE(T, RING, MAIN, AR, KK)                                                                   \
+  case KK:                                                                                                    \
+    hipLaunchKernelGGL((tb_kernel_src<T, 1, KK, 4, AR>), dim3(nwaves), dim3(64), 0, s, src, dst, a, r, q);    \
+    return;
+#define H2D_SRC_OCC_CASE(T, RING, MAIN, AR, KK) \
+  case KK:                                      \
+    return waves_per_cu_src<T, KK, AR>();
+#define H2D_SRC_UNIT(T, AR)                                                                                   \
+  template <>                                                                                                 \
+  void dispatch_src<T, AR>(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, T r, const T* q,    \
+                           hipStream_t s) {                                                                   \
+    switch (k) {                                                                                              \
+      H2D_TB_CASES(H2D_SRC_CASE, T, 4, false, AR)                                                             \
+      default:                                                                                                \
+        break;                                                                                                \
+    }                                                                                                         \
+    HEAT2D_REQUIRE(false, "temporal depth not instantiated for the heat-source kernel");                      \
+  }                                                                                                           \
+  template <>                                                                                                 \
+  int occupancy_waves_src<T, AR>(int k) {                                                                     \
+    switch (k) {                                                                                              \
+      H2D_TB_CASES(H2D_SRC_OCC_CASE, T, 4, false, AR)                                                         \
+      default:                                                                                                \
+        break;                                                                                                \
+    }                                                                                                         \
+    return 4;                                                                                                 \
   }
 
 }  // namespace tbimpl

@@ -224,11 +224,12 @@ void write_meta(const std::string& dir, const std::string& name, const Meta& m) 
                 "{\n \"format\": \"%s\",\n \"step\": %lld,\n \"nranks\": %d,\n \"dtype\": \"%s\",\n"
                 " \"n_owned\": %lld,\n \"n_input\": %lld,\n \"convention\": \"%s\",\n \"sigma\": %.17g,\n"
                 " \"nu\": %.17g,\n \"dom_len\": %.17g,\n \"r\": %.17g,\n \"edge_shift\": %lld,\n"
-                " \"bc_x\": \"%s\",\n \"bc_y\": \"%s\",\n"
+                " \"bc_x\": \"%s\",\n \"bc_y\": \"%s\",\n \"source_sha256\": %s,\n"
                 " \"writer\": \"heat2d-cli\"\n}\n",
                 kFormat, (long long)m.step, m.nranks, m.dtype == 0 ? "fp32" : "fp64", (long long)m.n_owned,
                 (long long)m.n_input, m.convention.c_str(), m.sigma, m.nu, m.dom_len, m.r, (long long)m.edge_shift,
-                m.bc_x.c_str(), m.bc_y.c_str());
+                m.bc_x.c_str(), m.bc_y.c_str(),
+                m.source_sha256.empty() ? "null" : ("\"" + m.source_sha256 + "\"").c_str());
   write_atomic(join(join(dir, name), "meta.json"), buf);  // + fsync of the step directory (rank files' entries)
   write_atomic(join(dir, "latest"), name + "\n");  // the commit point
   // prune: keep the two newest complete saves, ordered by (step, generation)
@@ -283,10 +284,88 @@ Meta read_meta(const std::string& dir) {
   if (js.find("\"edge_shift\"") != std::string::npos) m.edge_shift = std::atoll(json_value(js, "edge_shift").c_str());
   if (js.find("\"bc_x\"") != std::string::npos) m.bc_x = json_value(js, "bc_x");
   if (js.find("\"bc_y\"") != std::string::npos) m.bc_y = json_value(js, "bc_y");
+  if (js.find("\"source_sha256\"") != std::string::npos) {
+    m.source_sha256 = json_value(js, "source_sha256");
+    while (!m.source_sha256.empty() && (m.source_sha256.back() == ' ' || m.source_sha256.back() == '\r')) m.source_sha256.pop_back();
+    if (m.source_sha256 == "null") m.source_sha256.clear();
+  }
   auto bc_ok = [](const std::string& v) { return v == "dirichlet" || v == "periodic" || v == "insulated"; };
   HEAT2D_REQUIRE(bc_ok(m.bc_x) && bc_ok(m.bc_y), dir + ": meta.json: bc_x / bc_y must be dirichlet, periodic or insulated");
   HEAT2D_REQUIRE(m.nranks >= 1 && m.step >= 0 && m.n_owned >= 1, dir + ": inconsistent meta.json");
   return m;
+}
+
+std::string sha256_hex(const void* data, size_t bytes) {
+  static const uint32_t k[64] = {
+      0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5, 0xd807aa98, 0x12835b01,
+      0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174, 0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc,
+      0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da, 0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147,
+      0x06ca6351, 0x14292967, 0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
+      0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070, 0x19a4c116, 0x1e376c08,
+      0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3, 0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208,
+      0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+  uint32_t h[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+  auto rotr = [](uint32_t x, int n) { return (x >> n) | (x << (32 - n)); };
+  auto block = [&](const unsigned char* p) {
+    uint32_t w[64];
+    for (int i = 0; i < 16; ++i)
+      w[i] = ((uint32_t)p[4 * i] << 24) | ((uint32_t)p[4 * i + 1] << 16) | ((uint32_t)p[4 * i + 2] << 8) | p[4 * i + 3];
+    for (int i = 16; i < 64; ++i) {
+      const uint32_t s0 = rotr(w[i - 15], 7) ^ rotr(w[i - 15], 18) ^ (w[i - 15] >> 3);
+      const uint32_t s1 = rotr(w[i - 2], 17) ^ rotr(w[i - 2], 19) ^ (w[i - 2] >> 10);
+      w[i] = w[i - 16] + s0 + w[i - 7] + s1;
+    }
+    uint32_t a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], hh = h[7];
+    for (int i = 0; i < 64; ++i) {
+      const uint32_t t1 = hh + (rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25)) + ((e & f) ^ (~e & g)) + k[i] + w[i];
+      const uint32_t t2 = (rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22)) + ((a & b) ^ (a & c) ^ (b & c));
+      hh = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+    }
+    h[0] += a; h[1] += b; h[2] += c; h[3] += d; h[4] += e; h[5] += f; h[6] += g; h[7] += hh;
+  };
+  const unsigned char* p = static_cast<const unsigned char*>(data);
+  size_t left = bytes;
+  for (; left >= 64; left -= 64, p += 64) block(p);
+  unsigned char tail[128] = {0};
+  std::memcpy(tail, p, left);
+  tail[left] = 0x80;
+  const size_t tl = left + 9 <= 64 ? 64 : 128;
+  const uint64_t bits = (uint64_t)bytes * 8;
+  for (int i = 0; i < 8; ++i) tail[tl - 1 - i] = (unsigned char)(bits >> (8 * i));
+  block(tail);
+  if (tl == 128) block(tail + 64);
+  char out[65];
+  for (int i = 0; i < 8; ++i) std::snprintf(out + 8 * i, 9, "%08x", h[i]);
+  return std::string(out, 64);
+}
+
+std::vector<char> read_source(const std::string& path, int64_t rows, int64_t cols, int dtype, std::string* sha256) {
+  File file(path, "rb");
+  const NpyInfo info = npy_header(file.f, path);
+  HEAT2D_REQUIRE(info.rows == rows && info.cols == cols,
+                 path + ": shape (" + std::to_string(info.rows) + ", " + std::to_string(info.cols) +
+                     "), the frame-inclusive grid is (" + std::to_string(rows) + ", " + std::to_string(cols) + ")");
+  const size_t n = (size_t)(rows * cols), es_in = info.dtype == 0 ? 4 : 8, es = dtype == 0 ? 4 : 8;
+  std::vector<char> raw(n * es_in);
+  HEAT2D_REQUIRE(std::fseek(file.f, info.data_off, SEEK_SET) == 0 && std::fread(raw.data(), es_in, n, file.f) == n,
+                 path + ": truncated data");
+  std::vector<char> out;
+  if (info.dtype == dtype) {
+    out.swap(raw);
+  } else {
+    out.resize(n * es);
+    if (dtype == 0) {
+      const double* in = reinterpret_cast<const double*>(raw.data());
+      float* o = reinterpret_cast<float*>(out.data());
+      for (size_t i = 0; i < n; ++i) o[i] = (float)in[i];
+    } else {
+      const float* in = reinterpret_cast<const float*>(raw.data());
+      double* o = reinterpret_cast<double*>(out.data());
+      for (size_t i = 0; i < n; ++i) o[i] = (double)in[i];
+    }
+  }
+  if (sha256) *sha256 = sha256_hex(out.data(), out.size());
+  return out;
 }
 
 void read_rows(const Meta& m, int64_t row0, int64_t nrows, int64_t ncols, int dtype, void* out) {

@@ -16,6 +16,7 @@ Parity map (reference -> here):
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 from typing import Optional
 
 import numpy as np
@@ -68,6 +69,23 @@ def _cycle_hist(h, reset: bool) -> dict:
     out = (C.c_int64 * n)()
     N.call("heat2d_solver_cycle_hist", h, out, n, int(bool(reset)))
     return {k: int(out[k]) for k in range(n) if out[k]}
+
+
+def _source_array(source, nrows_global: int, ncols: int, np_dtype) -> np.ndarray:
+    """The global frame-inclusive source array in the field's dtype (a wrong shape fails)."""
+    a = np.ascontiguousarray(source, dtype=np_dtype)
+    if a.shape != (nrows_global + 2, ncols + 2):
+        raise ValueError(f"source must be the frame-inclusive global array {(nrows_global + 2, ncols + 2)}, "
+                         f"got {a.shape}")
+    return a
+
+
+def _source_info(h) -> dict:
+    """info()["source"]: whether the solver was built for a heat source, whether
+    one is set, and the depth clamp that then applies (0: none)."""
+    v = (C.c_int32 * 3)()
+    N.call("heat2d_solver_source", h, v)
+    return {"enabled": bool(v[0]), "set": bool(v[1]), "max_tb": int(v[2]) if v[0] else 0}
 
 
 def _arith(h) -> int:
@@ -134,6 +152,17 @@ class HeatSolver:
             on more than one rank periodic x runs on the loopback, host-thread
             and torch.distributed (host-staged) transports (insulated x: every
             transport); "insulated" not with arith "fast".
+        source: a heat source, u_t = nu lap(u) + f: the GLOBAL frame-inclusive
+            array (rows + 2) x (n + 2) of the per-step increment S = dt * f (the
+            solver does no scaling; converted to the field's dtype; its frame
+            entries are ignored). One step is the update followed by one
+            separately rounded add, T' = update(T) + S, at every fused level:
+            bitwise equal to models.reference.ftcs(source=) at any depth, plan
+            and rank count. Each rank slices its own rows. Dirichlet axes,
+            engine "tb", no copy_swap, arith "exact" / "fma" ("auto" picks fma
+            when r is a power of two, else exact — never jacobi); the depth is
+            clamped to the source kernels' deepest pass (info()["source"]).
+            :meth:`set_source` replaces or clears it between steps.
     """
 
     def __init__(self, problem: Problem, *, dtype: str = "fp64", backend: str = "auto", tb: int = 0,
@@ -142,7 +171,7 @@ class HeatSolver:
                  device: Optional[int] = None, init: bool = True, rows: Optional[int] = None,
                  comm_cus: int = 0, autotune: int = -1, engine: str = "tb", arith: str = "auto",
                  slab_row0: Optional[int] = None, edge_shift: int = 0, bc_x: str = "dirichlet",
-                 bc_y: str = "dirichlet"):
+                 bc_y: str = "dirichlet", source=None):
         self.problem = problem
         self.edge_shift = 0 if bc_x == "periodic" else int(edge_shift)  # (periodic x: no edge slabs)
         self.bc_x, self.bc_y = bc_x, bc_y
@@ -187,14 +216,32 @@ class HeatSolver:
             raise ValueError(f"arith must be one of {sorted(N.ARITH)}")
         cfg.arith = N.ARITH[arith]
         self.arith = arith
+        cfg.source = int(source is not None)
+        self.source_sha256 = None
         self._cfg = cfg
         h = C.c_void_p()
         N.call("heat2d_solver_create", C.byref(cfg), self.transport.handle, C.byref(h))
         self._h = h
         self.layout = N.Layout()
         N.call("heat2d_solver_layout", self._h, C.byref(self.layout))
+        if source is not None:
+            self.set_source(source)
         if init:
             self.init()
+
+    def set_source(self, source) -> None:
+        """Replace the heat source (the global frame-inclusive array, see the
+        class docstring) or clear it (None: the solver then runs as one
+        without), between step() calls. The solver must have been created with
+        a source; nothing but captured graphs is invalidated."""
+        if source is None:
+            N.call("heat2d_solver_set_source", self._h, None, 0)
+            self.source_sha256 = None
+            return
+        a = _source_array(source, int(self.layout.nrows_global), self.ncols, self.np_dtype)
+        N.call("heat2d_solver_set_source", self._h, a.ctypes.data_as(C.c_void_p), a.shape[1])
+        # what a checkpoint records of the source (utils/checkpoint.py): the digest of the converted array
+        self.source_sha256 = hashlib.sha256(a.tobytes()).hexdigest()
 
     # ------------------------------------------------------------------ info
     @property
@@ -226,6 +273,7 @@ class HeatSolver:
                 "stream": stream.value, "backend": self.backend, "transport": self.transport.name,
                 "arith": _arith(self._h),  # the resolved code: 0 exact, 1 fma, 2 jacobi, 3 fast
                 "bc_x": self._bc()[0], "bc_y": self._bc()[1],  # "dirichlet" | "periodic" | "insulated", as the native solver runs
+                "source": _source_info(self._h),
                 "rank": self.rank, "size": self.size, "layout": self.layout.as_dict()}
 
     def _bc(self) -> tuple:
@@ -463,7 +511,7 @@ class LoopbackGroup:
     def __init__(self, problem: Problem, nranks: int, *, dtype: str = "fp64", backend: str = "auto",
                  tb: int = 0, tile_rows: int = 0, device: Optional[int] = None, arith: str = "auto",
                  overlap: bool = True, autotune: int = -1, comm_cus: int = 0, edge_shift: int = 0,
-                 bc_x: str = "dirichlet", bc_y: str = "dirichlet"):
+                 bc_x: str = "dirichlet", bc_y: str = "dirichlet", source=None):
         self.problem = problem
         self.bc_x, self.bc_y = bc_x, bc_y
         self.backend = resolve_backend(backend)
@@ -487,10 +535,13 @@ class LoopbackGroup:
         cfg.edge_shift = int(edge_shift)
         cfg.bc_x = N.bc_code(bc_x, "bc_x")
         cfg.bc_y = N.bc_code(bc_y, "bc_y")
+        cfg.source = int(source is not None)  # a heat source (HeatSolver source=): each member slices its rows
         self.nranks = nranks
         h = C.c_void_p()
         N.call("heat2d_group_create", C.byref(cfg), nranks, C.byref(h))
         self._h = h
+        if source is not None:
+            self.set_source(source)
         x = np.ascontiguousarray(problem.x, dtype=np.float64)
         ic = problem.ic.to_native()
         N.call("heat2d_group_init", self._h, C.byref(ic), x.ctypes.data_as(C.c_void_p),
@@ -498,6 +549,16 @@ class LoopbackGroup:
 
     def step(self, n: int) -> None:
         N.call("heat2d_group_step", self._h, int(n))
+
+    def set_source(self, source) -> None:
+        """Replace (the global frame-inclusive array) or clear (None) the heat
+        source of every member, between step() calls (HeatSolver.set_source)."""
+        if source is None:
+            N.call("heat2d_group_set_source", self._h, None, 0)
+            return
+        m = self.problem.n_owned
+        a = _source_array(source, m, m, NP_DTYPES[self.dtype])
+        N.call("heat2d_group_set_source", self._h, a.ctypes.data_as(C.c_void_p), m + 2)
 
     def upload(self, arr: np.ndarray) -> None:
         """Whole owned grid -> the members' slabs, then a loopback halo exchange."""

@@ -72,14 +72,98 @@ def wrap_frame(T: np.ndarray, bc_x: str = "dirichlet", bc_y: str = "dirichlet") 
     return out
 
 
-def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet") -> np.ndarray:
+def _two_sum(a, b):
+    """s + e == a + b exactly (Knuth), s the rounded sum."""
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def _sum_round_odd(a, b):
+    """a + b rounded to odd (float64): the rounded sum, moved to its odd
+    neighbour on the side of the exact sum when it is inexact and even. A
+    value rounded to odd rounds again, to nearest at a precision at least two
+    bits shorter, as the exact value would (Boldo & Melquiond, "Emulation of
+    FMA and correctly rounded sums", 2008)."""
+    s, e = _two_sum(a, b)
+    even = (s.view(np.int64) & 1) == 0
+    toward = np.where(e > 0, np.inf, -np.inf)
+    return np.where((e != 0) & even, np.nextafter(s, toward), s)
+
+
+def fma(a, b, c):
+    """Elementwise fused multiply-add a * b + c with ONE rounding, in the arrays'
+    dtype (float32 or float64), for the normal range the golden runs in: what
+    the engine's contracted arithmetic ("fma") executes. float32: the product
+    is exact in float64, the sum rounded to odd there, then to float32.
+    float64: the product split exactly (Veltkamp / Dekker), then Boldo &
+    Melquiond's emulation RN(th + RO(tl + ul))."""
+    a, b, c = np.broadcast_arrays(np.asarray(a), np.asarray(b), np.asarray(c))
+    if a.dtype == np.float32:
+        p = a.astype(np.float64) * b.astype(np.float64)
+        return _sum_round_odd(p, c.astype(np.float64)).astype(np.float32)
+    if a.dtype != np.float64:
+        raise TypeError("fma: float32 or float64 arrays")
+    uh = a * b
+    k = np.float64(134217729.0)  # 2^27 + 1
+    t = k * a
+    ah = t - (t - a)
+    al = a - ah
+    t = k * b
+    bh = t - (t - b)
+    bl = b - bh
+    ul = ((ah * bh - uh) + ah * bl + al * bh) + al * bl  # a * b == uh + ul
+    th, tl = _two_sum(c, uh)
+    return th + _sum_round_odd(tl, ul)
+
+
+def _ftcs_step_source(T: np.ndarray, r, arith: str, source: np.ndarray) -> np.ndarray:
+    """One step with a heat source: the update of :func:`ftcs_step`, rounded as
+    it is there, then one separately rounded add of the source,
+        exact: T' = (C + r*((((S_+E)+N)+W) - 4C)) + S[i,j]
+        fma:   T' = fma(r, fma(-4, C, sum), C)    + S[i,j]
+    at the owned points; the frame stays pinned and the frame entries of
+    ``source`` are ignored."""
+    if arith not in ("exact", "fma"):
+        raise ValueError("a heat source needs arith 'exact' or 'fma'")
+    if source.shape != T.shape:
+        raise ValueError(f"source must be frame-inclusive like the field, {T.shape}, got {source.shape}")
+    S = np.ascontiguousarray(source, dtype=T.dtype)
+    r = T.dtype.type(r)
+    four = T.dtype.type(4)
+    c = T[1:-1, 1:-1]
+    total = ((T[2:, 1:-1] + T[1:-1, 2:]) + T[:-2, 1:-1]) + T[1:-1, :-2]
+    out = T.copy()
+    if arith == "fma":
+        upd = fma(np.broadcast_to(r, c.shape), fma(np.broadcast_to(-four, c.shape), c, total), c)
+    else:
+        upd = c + r * (total - four * c)
+    out[1:-1, 1:-1] = upd + S[1:-1, 1:-1]
+    return out
+
+
+def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
+              source: np.ndarray | None = None) -> np.ndarray:
     """One FTCS step of a frame-inclusive field. On a Dirichlet axis the frame
     is kept fixed; on a periodic or insulated one it is refreshed from the
     owned points before the step (:func:`wrap_frame`) — the update and its
     operation order are the same — and holds the images of T at time t on
     return.
     arith "jacobi" (r == 1/4 only): r * sum, the zero centre weight folded
-    away — the engine's arith 2."""
+    away — the engine's arith 2.
+    source (frame-inclusive, the per-step increment S = dt * f; Dirichlet axes,
+    arith "exact" or "fma"): added after the update as an operation of its own
+    (:func:`_ftcs_step_source`). None: no source.
+    An asymmetry to know: WITH a source, "fma" is the contracted update with a
+    single rounding (:func:`fma`), what the engine's arith 1 executes; WITHOUT
+    one, "fma" keeps taking the exact expression as it always has here (equal
+    bits only where r is a power of two). So at such an r as 0.2,
+    ``ftcs(arith="fma", source=None)`` and ``ftcs(arith="fma", source=<all -0.0>)``
+    differ, while with "exact" they are bitwise equal."""
+    if source is not None:
+        if bc_x != "dirichlet" or bc_y != "dirichlet":
+            raise ValueError("a heat source needs Dirichlet boundaries on both axes")
+        return _ftcs_step_source(T, r, arith, source)
     T = wrap_frame(T, bc_x, bc_y)
     r = T.dtype.type(r)
     four = T.dtype.type(4)
@@ -99,11 +183,17 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
 
 
 def ftcs(problem: Problem, nsteps: int | None = None, dtype=np.float64, T0: np.ndarray | None = None,
-         arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet") -> np.ndarray:
+         arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
+         source: np.ndarray | None = None) -> np.ndarray:
     """Run FTCS; returns the frame-inclusive field (frame entries on periodic
-    / insulated axes: wrap / edge images of the returned owned points)."""
+    / insulated axes: wrap / edge images of the returned owned points).
+    source: a heat source added at every step (:func:`ftcs_step`)."""
     T = initial_field(problem, dtype) if T0 is None else T0.astype(dtype)
     n = problem.ntime if nsteps is None else nsteps
+    if source is not None:
+        for _ in range(n):
+            T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source)
+        return T
     for _ in range(n):
         T = ftcs_step(T, problem.r, arith, bc_x, bc_y)
     return wrap_frame(T, bc_x, bc_y)

@@ -86,7 +86,7 @@ def init_field(field: torch.Tensor, layout: N.Layout, ic, xcoord: np.ndarray,
 
 def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: float,
             rows: Optional[tuple[int, int]] = None, tile_rows: int = 0, arith: str = "exact",
-            bc_x: str = "dirichlet", bc_y: str = "dirichlet") -> None:
+            bc_x: str = "dirichlet", bc_y: str = "dirichlet", source: Optional[torch.Tensor] = None) -> None:
     """dst[rows] = k FTCS steps of src (temporal-blocked kernel). The k ghost rows
     around ``rows`` must be valid in ``src``; Dirichlet rows/cols are kept.
     ``arith``: "exact" (reference rounding), "fma" (contracted update) or
@@ -98,9 +98,23 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
     either axis: a point next to the wall takes its own value for the operand
     beyond it, at every level (``src``'s frame entries on that axis are not
     read by an owned point), and the frame images of the rows written are
-    refreshed in ``dst``; not with arith "fast"."""
+    refreshed in ``dst``; not with arith "fast".
+    ``source``: a heat source in the field's layout, dtype and device (the
+    per-step increment, with -0.0 in every frame row / column and pad entry so
+    that pinned points keep their bits: :func:`source_field`), added at every
+    fused level as an operation of its own; Dirichlet axes, arith "exact" /
+    "fma" / "auto"; on the device k is at most the source kernels' deepest pass
+    (common.hpp ``kMaxTBSrc``, reported as ``HeatSolver.info()["source"]["max_tb"]``)."""
     _check_field(src, layout)
     _check_field(dst, layout)
+    if source is not None:
+        _check_field(source, layout)
+        if source.dtype != src.dtype or source.device != src.device:
+            raise ValueError("source dtype/device mismatch")
+        if bc_x != "dirichlet" or bc_y != "dirichlet":
+            raise ValueError("a heat source needs Dirichlet boundaries on both axes")
+        if arith not in ("exact", "fma", "auto"):
+            raise ValueError("a heat source needs arith 'exact', 'fma' or 'auto'")
     if src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src/dst dtype/device mismatch")
     if src.data_ptr() == dst.data_ptr():
@@ -108,12 +122,36 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
     rb, re = (0, layout.nrows) if rows is None else rows
     ar = N.arith_code(arith, r)
     bc = N.bc_bits(bc_x, bc_y)
+    if source is not None:
+        if src.is_cuda:
+            N.call("heat2d_tb_src", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                   C.byref(layout), rb, re, k, r, _stream(src), tile_rows, ar, C.c_void_p(source.data_ptr()))
+        else:
+            N.call("heat2d_cpu_tb_src", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                   C.byref(layout), rb, re, k, r, ar, C.c_void_p(source.data_ptr()))
+        return
     if src.is_cuda:
         N.call("heat2d_tb_bc", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
                C.byref(layout), rb, re, k, r, _stream(src), tile_rows, ar, bc)
     else:
         N.call("heat2d_cpu_tb_bc", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
                C.byref(layout), rb, re, k, r, ar, bc)
+
+
+def source_field(S: np.ndarray, layout: N.Layout, dtype: torch.dtype, device="cpu") -> torch.Tensor:
+    """The heat-source buffer :func:`tb_step` takes, from the GLOBAL
+    frame-inclusive array ``S`` ((nrows_global + 2) x (ncols + 2)): -0.0
+    everywhere, then the owned points of every allocated row of the slab that
+    is an owned row of the grid (ghost rows included)."""
+    if S.shape != (layout.nrows_global + 2, layout.ncols + 2):
+        raise ValueError(f"source must be {(layout.nrows_global + 2, layout.ncols + 2)}, got {S.shape}")
+    f = torch.full((layout.rows_alloc(), layout.pitch), -0.0, dtype=dtype)
+    Sd = torch.as_tensor(np.ascontiguousarray(S)).to(dtype)
+    for i in range(-layout.halo, layout.nrows + layout.halo):
+        g = layout.row0 + i
+        if 0 <= g < layout.nrows_global:
+            f[i + layout.halo, layout.cpad:layout.cpad + layout.ncols] = Sd[g + 1, 1:-1]
+    return f.reshape(-1).to(device)
 
 
 WRAP_COLS = 24  # ghost columns per side that wrap_cols fills (kernels.hpp kWrapCols)

@@ -59,6 +59,11 @@ def build_parser():
                          "insulated: a zero-flux wall, any transport")
     ap.add_argument("--bc-y", default=None, choices=["dirichlet", "periodic", "insulated"],
                     help="boundary condition of the y (column) axis")
+    ap.add_argument("--source", default=None, metavar="FILE.npy",
+                    help="heat source u_t = nu lap(u) + f: the frame-inclusive (n+2) x (n+2) array of the per-step "
+                         "increment dt * f (converted to the run's dtype; a wrong shape fails), added at every step "
+                         "as an operation of its own. Dirichlet axes, engine tb, arith exact / fma (auto picks one of "
+                         "them). Checkpoints record its SHA-256; a restart needs the same file again")
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--ntime", type=int, default=None)
     ap.add_argument("--print-every", type=int, default=0)
@@ -222,7 +227,16 @@ def run(argv=None) -> int:
         print(" device limits: " + " ".join(f"{k}={v}" for k, v in lim.items()), flush=True)
     engine = a.engine or ("jit" if var.name == "pycuda" and backend == "hip" else "tb")
     arith = a.arith
-    if arith == "auto" and prob.r == 0.25 and prob.ic.sterbenz_safe() and not a.restart and engine == "tb":
+    source = None
+    if a.source:
+        import numpy as np
+        source = np.load(a.source, allow_pickle=False)
+        m = prob.n_owned + 2
+        if source.shape != (m, m):
+            raise SystemExit(f"heat2d: --source {a.source}: shape {source.shape}, the frame-inclusive grid is {(m, m)}")
+    # (with a source auto stays with the solver: fma when r is a power of two, else exact — never jacobi)
+    if arith == "auto" and prob.r == 0.25 and prob.ic.sterbenz_safe() and not a.restart and engine == "tb" \
+            and source is None:
         arith = "jacobi"  # bitwise the reference rounding on this IC (the CLI's auto does the same)
 
     def make_transport(kind):
@@ -257,7 +271,7 @@ def run(argv=None) -> int:
     if a.edge_shift not in ("auto", "measure"):
         edge_shift = int(a.edge_shift)
     elif world >= 3 and (backend == "hip" or a.edge_shift == "measure") and engine == "tb" and \
-            bc["bc_x"] != "periodic":  # (periodic x: no edge slabs)
+            bc["bc_x"] != "periodic" and source is None:  # (periodic x: no edge slabs; the probe slabs carry no source)
         edge_shift = _measure_edge_shift(prob, a, rank, world, local, backend, kinds[0], engine, arith,
                                          min(nsteps, 48), root and not a.quiet)
 
@@ -265,7 +279,7 @@ def run(argv=None) -> int:
         return HeatSolver(prob, dtype=a.dtype, backend=backend, tb=a.tb, overlap=not a.no_overlap,
                           copy_swap=a.copy_swap, managed=a.managed or var.managed, graph=a.graph, transport=tr,
                           device=local if backend == "hip" else None, engine=engine, arith=arith,
-                          edge_shift=edge_shift, **bc)
+                          edge_shift=edge_shift, source=source, **bc)
 
     tr, s, kind, fallback = _make_solver(kinds, make_transport, make_solver, world)
     if fallback and root and not a.quiet:

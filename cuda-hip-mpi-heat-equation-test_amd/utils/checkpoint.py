@@ -115,6 +115,10 @@ def save(solver, directory: str, step: Optional[int] = None, extra: Optional[dic
             "sigma": p.sigma, "nu": p.nu, "dom_len": p.dom_len, "r": p.r,
             "edge_shift": int(getattr(solver, "edge_shift", 0)),
             "bc_x": getattr(solver, "bc_x", "dirichlet"), "bc_y": getattr(solver, "bc_y", "dirichlet"),
+            # the heat source of the run: SHA-256 of the global frame-inclusive array's bytes in the
+            # run's dtype (HeatSolver.source_sha256), null without one. The source itself is not saved:
+            # a restart must be given the same one again (load() compares the digests)
+            "source_sha256": getattr(solver, "source_sha256", None),
         }
         meta.update(extra or {})
         _write_atomic(os.path.join(sd, "meta.json"), json.dumps(meta, indent=1))
@@ -154,6 +158,14 @@ def load(solver, directory: str) -> dict:
     for k in ("bc_x", "bc_y"):  # (older saves: dirichlet)
         if meta.get(k, "dirichlet") != getattr(solver, k, "dirichlet"):
             raise ValueError(f"checkpoint {k} = {meta.get(k, 'dirichlet')} != solver {k} = {getattr(solver, k, 'dirichlet')}")
+    have, saved = getattr(solver, "source_sha256", None), meta.get("source_sha256")  # (older saves: none)
+    if saved != have:
+        if saved is None:
+            raise ValueError("the checkpoint was written without a heat source, this run has one")
+        if have is None:
+            raise ValueError("the checkpoint was written with a heat source: give the restart the same source "
+                             f"(sha256 {saved})")
+        raise ValueError(f"the restart's heat source differs from the checkpoint's (sha256 {have} != {saved})")
     want = "fp64" if solver.np_dtype == np.float64 else "fp32"
     if meta["dtype"] != want:
         raise ValueError(f"checkpoint dtype {meta['dtype']} != solver dtype {want}")
