@@ -216,6 +216,22 @@ int heat2d_cpu_tb_src(int dtype, const void* src, void* dst, const heat2d_layout
   return guarded([&] { cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, arith, 0, source); });
 }
 
+int heat2d_tb_var(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                  void* stream, int64_t tile_rows, int arith, const void* rmap) {
+  return guarded([&] {
+    HEAT2D_REQUIRE(rmap != nullptr, "heat2d_tb_var needs a diffusivity-map buffer");
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, as_stream(stream), tile_rows, 0, arith, 0, nullptr, rmap);
+  });
+}
+
+int heat2d_cpu_tb_var(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                      int arith, const void* rmap) {
+  return guarded([&] {
+    HEAT2D_REQUIRE(rmap != nullptr, "heat2d_cpu_tb_var needs a diffusivity-map buffer");
+    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, arith, 0, nullptr, rmap);
+  });
+}
+
 int heat2d_wrap_cols(int dtype, void* field, const heat2d_layout* L, int64_t r0, int64_t r1, void* stream,
                      int on_device) {
   return guarded([&] {
@@ -363,6 +379,10 @@ int heat2d_plan_max_grid_src(int dtype, int nranks, int64_t budget_bytes, int so
   return guarded([&] { *n = plan_max_grid(dtype, nranks, budget_bytes, 0, source != 0); });
 }
 
+int heat2d_plan_max_grid_ext(int dtype, int nranks, int64_t budget_bytes, int source, int rmap, int64_t* n) {
+  return guarded([&] { *n = plan_max_grid(dtype, nranks, budget_bytes, 0, source != 0, rmap != 0); });
+}
+
 int heat2d_mem_info(int device, int64_t* free_bytes, int64_t* total_bytes) {
   return guarded([&] {
     if (hipSetDevice(device) != hipSuccess) fail(__FILE__, __LINE__, "hipSetDevice failed");
@@ -418,6 +438,18 @@ int heat2d_solver_source(void* s, int32_t* out3) {
     out3[0] = static_cast<Solver*>(s)->config().source;
     out3[1] = static_cast<Solver*>(s)->has_source() ? 1 : 0;
     out3[2] = kMaxTBSrc;
+  });
+}
+
+int heat2d_solver_set_rmap(void* s, const void* host, int64_t ld) {
+  return guarded([&] { static_cast<Solver*>(s)->set_rmap(host, ld); });
+}
+
+int heat2d_solver_rmap(void* s, int32_t* out3) {
+  return guarded([&] {
+    out3[0] = static_cast<Solver*>(s)->config().rmap;
+    out3[1] = static_cast<Solver*>(s)->has_rmap() ? 1 : 0;
+    out3[2] = kMaxTBVar;
   });
 }
 
@@ -534,6 +566,10 @@ int heat2d_group_upload_field(void* g, const void* host, int64_t ld) {
 
 int heat2d_group_set_source(void* g, const void* host, int64_t ld) {
   return guarded([&] { static_cast<LoopbackGroup*>(g)->set_source(host, ld); });
+}
+
+int heat2d_group_set_rmap(void* g, const void* host, int64_t ld) {
+  return guarded([&] { static_cast<LoopbackGroup*>(g)->set_rmap(host, ld); });
 }
 
 int heat2d_group_member(void* g, int i, void** solver) {

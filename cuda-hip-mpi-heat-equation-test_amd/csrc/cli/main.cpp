@@ -85,6 +85,9 @@ struct Args {
   // --source FILE.npy: heat source, the frame-inclusive (n+2) x (n+2) per-step increment dt * f
   // (SolverConfig::source; converted to the run's dtype, a wrong shape fails)
   std::string source;
+  // --rmap FILE.npy: diffusivity map, the frame-inclusive (n+2) x (n+2) per-point diffusion number
+  // nu(x, y) dt / dx^2 (SolverConfig::rmap; converted to the run's dtype, a wrong shape fails)
+  std::string rmap;
 };
 
 void usage() {
@@ -97,7 +100,7 @@ void usage() {
       "              [--checkpoint DIR [--checkpoint-every N]] [--restart DIR]\n"
       "              [--transport auto|rccl|peer] [--share-gpu] [--autotune auto|on|off] [--edge-shift N]\n"
       "              [--bc-x dirichlet|periodic|insulated] [--bc-y dirichlet|periodic|insulated]\n"
-      "              [--source FILE.npy]\n");
+      "              [--source FILE.npy] [--rmap FILE.npy]\n");
 }
 
 Args parse_args(int argc, char** argv) {
@@ -143,6 +146,7 @@ Args parse_args(int argc, char** argv) {
     else if (s == "--transport") a.transport = need("--transport");
     else if (s == "--share-gpu") a.share_gpu = true;
     else if (s == "--source") a.source = need("--source");
+    else if (s == "--rmap") a.rmap = need("--rmap");
     else if (s == "--bc-x" || s == "--bc-y") {
       const std::string v = need(s.c_str());
       if (v != "dirichlet" && v != "periodic" && v != "insulated") {
@@ -200,6 +204,9 @@ struct Shared {
   // --source: the global array in the run's dtype (read by the first rank to need it, under mu) and its digest
   std::vector<char> source;
   std::string source_sha256;
+  // --rmap: the same for the diffusivity map
+  std::vector<char> rmap;
+  std::string rmap_sha256;
 };
 
 // Collective checkpoint (every rank its slab, then rank 0 publishes meta.json).
@@ -228,6 +235,7 @@ void save_checkpoint(Shared& sh, Solver& s, Transport& tr, int rank, int64_t ste
     m.bc_x = bc_names[s.config().bc_x];
     m.bc_y = bc_names[s.config().bc_y];
     m.source_sha256 = sh.source_sha256;  // (empty: no source, written as null)
+    m.rmap_sha256 = sh.rmap_sha256;      // (empty: no map, the key is not written)
     ckpt::write_meta(a.checkpoint, name, m);
   }
   tr.barrier();
@@ -306,6 +314,20 @@ void run_rank(Shared& sh, int rank) {
       if (sh.source.empty())
         sh.source = ckpt::read_source(a.source, sh.prob.n_owned + 2, sh.prob.n_owned + 2, cfg.dtype, &sh.source_sha256);
     }
+    if (!a.rmap.empty()) {
+      cfg.rmap = 1;
+      std::lock_guard<std::mutex> g(sh.mu);
+      if (sh.rmap.empty()) {
+        const int64_t m = sh.prob.n_owned + 2;
+        sh.rmap = ckpt::read_source(a.rmap, m, m, cfg.dtype, &sh.rmap_sha256);
+        double rmax = 0;  // the stability warning of the scalar r, on the largest owned entry
+        for (int64_t i = 1; i < m - 1; ++i)
+          for (int64_t j = 1; j < m - 1; ++j)
+            rmax = std::max(rmax, cfg.dtype == 0 ? (double)reinterpret_cast<const float*>(sh.rmap.data())[i * m + j]
+                                                 : reinterpret_cast<const double*>(sh.rmap.data())[i * m + j]);
+        if (rmax > 0.25 + 1e-12) std::fprintf(stderr, "warning: max r = %.6g > 0.25: FTCS is unstable in 2-D\n", rmax);
+      }
+    }
     // boundary conditions: the flags, or a restart's checkpointed settings (a
     // flag that says otherwise fails: the resumed run would not be the saved one)
     std::string bc_x = a.bc_x.empty() ? "dirichlet" : a.bc_x, bc_y = a.bc_y.empty() ? "dirichlet" : a.bc_y;
@@ -325,6 +347,14 @@ void run_rank(Shared& sh, int rank) {
         fail(__FILE__, __LINE__, "the restart's heat source differs from the checkpoint's (sha256 " + sh.source_sha256 +
                                      " != " + m0.source_sha256 + ")");
       }
+      // ... and the diffusivity map the checkpointed run had (it is not saved either), and no other
+      if (m0.rmap_sha256 != sh.rmap_sha256) {
+        HEAT2D_REQUIRE(!m0.rmap_sha256.empty(), "the checkpoint was written without a diffusivity map, this run has one (--rmap)");
+        HEAT2D_REQUIRE(!sh.rmap_sha256.empty(), "the checkpoint was written with a diffusivity map: give the restart the same "
+                                                "--rmap (sha256 " + m0.rmap_sha256 + ")");
+        fail(__FILE__, __LINE__, "the restart's diffusivity map differs from the checkpoint's (sha256 " + sh.rmap_sha256 +
+                                     " != " + m0.rmap_sha256 + ")");
+      }
     }
     auto bc_code = [](const std::string& v) { return v == "periodic" ? kBcPeriodic : v == "insulated" ? kBcInsulated : kBcDirichlet; };
     cfg.bc_x = bc_code(bc_x);
@@ -340,18 +370,20 @@ void run_rank(Shared& sh, int rank) {
       // the whole run — the IC in [m, 2m] (the reference's: 1 and 2) keeps
       // every sum - 4c exact; a restart's data is not known to be
       // (with a source auto stays with the solver: fma or exact, never jacobi)
-      if (sh.prob.r == 0.25 && ic_sterbenz_safe(sh.prob.ic) && a.restart.empty() && cfg.engine == 0 && !cfg.source) {
+      if (sh.prob.r == 0.25 && ic_sterbenz_safe(sh.prob.ic) && a.restart.empty() && cfg.engine == 0 && !cfg.source && !cfg.rmap) {
         cfg.arith = 2;
         arith_used = "jacobi (auto)";
       } else {
         int e = 0;
         const bool pow2 = sh.prob.r > 0 && std::frexp(sh.prob.r, &e) == 0.5;
-        arith_used = pow2 ? "fma (auto)" : "exact (auto)";
+        // (with a diffusivity map the solver's auto is exact: the multipliers are no one power of two)
+        arith_used = pow2 && !cfg.rmap ? "fma (auto)" : "exact (auto)";
       }
     }
     if (root) sh.arith_used = arith_used;
     Solver s(cfg, tr);
     if (cfg.source) s.set_source(sh.source.data(), sh.prob.n_owned + 2);
+    if (cfg.rmap) s.set_rmap(sh.rmap.data(), sh.prob.n_owned + 2);
     s.init(sh.prob.ic, sh.prob.x.data(), sh.prob.x.data());
     const bool inclusive = sh.prob.conv == Convention::Inclusive;
     int64_t start = 0;

@@ -68,6 +68,28 @@ void row_fma_sw(const T* up, const T* mid, const T* dn, T* out, int64_t n, T r) 
     out[j] = std::fma(r, sum - T(4) * mid[j], mid[j]);
   }
 }
+// ... with a diffusivity map: the multiplier is the map's element rm[j]
+template <typename T>
+void row_var_exact(const T* up, const T* mid, const T* dn, T* out, int64_t n, const T* rm) {
+  for (int64_t j = 0; j < n; ++j) {
+    const T sum = ((dn[j] + mid[j + 1]) + up[j]) + mid[j - 1];
+    out[j] = mid[j] + rm[j] * (sum - T(4) * mid[j]);
+  }
+}
+template <typename T>
+__attribute__((target("fma"))) void row_var_fma_hw(const T* up, const T* mid, const T* dn, T* out, int64_t n, const T* rm) {
+  for (int64_t j = 0; j < n; ++j) {
+    const T sum = ((dn[j] + mid[j + 1]) + up[j]) + mid[j - 1];
+    out[j] = std::fma(rm[j], std::fma(T(-4), mid[j], sum), mid[j]);
+  }
+}
+template <typename T>
+void row_var_fma_sw(const T* up, const T* mid, const T* dn, T* out, int64_t n, const T* rm) {
+  for (int64_t j = 0; j < n; ++j) {
+    const T sum = ((dn[j] + mid[j + 1]) + up[j]) + mid[j - 1];
+    out[j] = std::fma(rm[j], std::fma(T(-4), mid[j], sum), mid[j]);
+  }
+}
 // arith 2 (r == 1/4): the centre weight 1 - 4r is zero, r * sum (r*x exact)
 template <typename T>
 void row_jacobi(const T* up, const T* mid, const T* dn, T* out, int64_t n, T r) {
@@ -110,9 +132,12 @@ void ins_cols_impl(T* f, const SlabLayout& L, int64_t r0, int64_t r1) {
 // q (a heat source in the field's layout, Dirichlet axes only): every level adds
 // its row of q to the updated owned points, T' = update + q, as an add of its
 // own (the device march's tb_impl.hpp March SRC); pinned points are copied.
+// rm (a diffusivity map in the field's layout, Dirichlet axes only): the
+// multiplier of an owned point's update is its element of rm instead of r (the
+// device march's tb_impl.hpp March VAR); pinned points are copied.
 template <typename T>
 void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re, int k, T r, int arith, int bc,
-             const T* q = nullptr) {
+             const T* q = nullptr, const T* rm = nullptr) {
   const SlabLayout L = kern::bc_layout(L0, bc & kern::kBcPeriodicX);  // (the columns: free_cols below)
   const bool free_cols = (bc & kern::kBcPeriodicY) != 0;
   const bool ins_x = (bc & kern::kBcInsulatedX) != 0, ins_y = (bc & kern::kBcInsulatedY) != 0;
@@ -152,6 +177,12 @@ void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re,
         T* out = b + li * P + c - g;
         if (row < fixed_lo || row >= fixed_hi) {
           std::memcpy(out, mid, sizeof(T) * (size_t)(L.ncols + 2 * g));
+          continue;
+        }
+        if (rm) {
+          const T* rr = rm + L.offset(row, 0);
+          if (arith == 1) (host_has_fma() ? row_var_fma_hw<T> : row_var_fma_sw<T>)(up, mid, dn, out, L.ncols, rr);
+          else row_var_exact<T>(up, mid, dn, out, L.ncols, rr);
           continue;
         }
         row_update(up, mid, dn, out, L.ncols + 2 * g, r);
@@ -251,7 +282,7 @@ int num_threads() {
 }
 
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end,
-        int k, double r, int arith, int bc, const void* source) {
+        int k, double r, int arith, int bc, const void* source, const void* rmap) {
   HEAT2D_REQUIRE(k >= 1 && k <= L.halo, "k out of range");
   HEAT2D_REQUIRE(arith >= 0 && arith <= 3, "arith must be 0, 1, 2 or 3");
   HEAT2D_REQUIRE(arith != 2 || r == 0.25, "arith 2 (jacobi) needs r == 1/4 exactly");
@@ -262,14 +293,16 @@ void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_b
                  "insulated boundaries have no arith 3 (fast) kernels");
   HEAT2D_REQUIRE(!source || ((arith == 0 || arith == 1) && bc == 0),
                  "a heat source needs arith 0 (exact) or 1 (fma) and Dirichlet boundaries on both axes");
+  HEAT2D_REQUIRE(!rmap || ((arith == 0 || arith == 1) && bc == 0 && !source),
+                 "a diffusivity map needs arith 0 (exact) or 1 (fma), Dirichlet boundaries on both axes and no heat source");
   if (arith == 3) arith = 1;
   if (row_end <= row_begin) return;
   if (dt == DType::F32)
     tb_impl<float>(static_cast<const float*>(src), static_cast<float*>(dst), L, row_begin, row_end, k, (float)r, arith, bc,
-                   static_cast<const float*>(source));
+                   static_cast<const float*>(source), static_cast<const float*>(rmap));
   else
     tb_impl<double>(static_cast<const double*>(src), static_cast<double*>(dst), L, row_begin, row_end, k, r, arith, bc,
-                    static_cast<const double*>(source));
+                    static_cast<const double*>(source), static_cast<const double*>(rmap));
 }
 
 void init(DType dt, void* field, const SlabLayout& L, const kern::IcParams& ic, const double* xc,

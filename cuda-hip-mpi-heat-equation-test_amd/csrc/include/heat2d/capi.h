@@ -36,7 +36,8 @@ typedef struct heat2d_config {
   int32_t edge_shift; /* rows each edge slab gives the middle ones (common.hpp decompose) */
   int64_t slab_row0, slab_rows_global; /* 1-rank rehearsal of a middle slab (0: the slab is the grid) */
   int32_t bc_x, bc_y; /* boundary condition of the row / column axis: 0 dirichlet, 1 periodic, 2 insulated */
-  int32_t source, pad0; /* source = 1: the solver carries a heat source (heat2d_solver_set_source) */
+  int32_t source; /* 1: the solver carries a heat source (heat2d_solver_set_source) */
+  int32_t rmap;   /* 1: the solver carries a diffusivity map (heat2d_solver_set_rmap) */
 } heat2d_config;
 
 typedef struct heat2d_tb_plan {
@@ -184,6 +185,21 @@ int heat2d_tb_src(int dtype, const void* src, void* dst, const heat2d_layout* L,
                   double r, void* stream, int64_t tile_rows, int arith, const void* source);
 int heat2d_cpu_tb_src(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                       double r, int arith, const void* source);
+/* The diffusivity map of a solver created with config.rmap = 1: `host` is the GLOBAL frame-inclusive
+   array (nrows_global + 2) x (ncols + 2) of the per-point diffusion number R = nu(x, y) dt / dx^2 in the
+   field's dtype (frame entries ignored; owned entries finite and >= 0); the rank copies its own rows.
+   One step is T' = C + R[i,j] * (sum - 4C) at every fused level; R = 0 holds a point. host = NULL
+   returns to the scalar r. Between steps. */
+int heat2d_solver_set_rmap(void* s, const void* host, int64_t ld);
+/* out3 = {config.rmap, a map is set, the deepest pass with a map (kMaxTBVar)} */
+int heat2d_solver_rmap(void* s, int32_t* out3);
+/* heat2d_tb / heat2d_cpu_tb with a diffusivity-map buffer in the field's layout (+0.0 in its frame
+   rows / columns, pad entries and rows outside the grid): Dirichlet axes, arith 0 / 1, k <= kMaxTBVar
+   on the device */
+int heat2d_tb_var(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                  void* stream, int64_t tile_rows, int arith, const void* rmap);
+int heat2d_cpu_tb_var(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                      int arith, const void* rmap);
 /* any rectangle of the current field, local rows [r0, r1) x columns [c0, c1), ghost / frame included */
 int heat2d_solver_download_region(void* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, void* host, int64_t ld);
 // memory-fit planner (runtime.hpp solver_footprint / plan_max_grid): out3 =
@@ -193,6 +209,8 @@ int heat2d_solver_footprint(const heat2d_config* cfg, int rank, int nranks, int6
 int heat2d_plan_max_grid(int dtype, int nranks, int64_t budget_bytes, int64_t* n);
 /* ... of solvers that carry a heat source (source = 1: a third field buffer) */
 int heat2d_plan_max_grid_src(int dtype, int nranks, int64_t budget_bytes, int source, int64_t* n);
+/* ... and / or a diffusivity map (rmap = 1: one more field buffer) */
+int heat2d_plan_max_grid_ext(int dtype, int nranks, int64_t budget_bytes, int source, int rmap, int64_t* n);
 // hipMemGetInfo of device
 int heat2d_mem_info(int device, int64_t* free_bytes, int64_t* total_bytes);
 // s's current field, local rows [r0, r0 + nrows), against other's, rows
@@ -232,6 +250,8 @@ int heat2d_group_download(void* g, void* host, int64_t ld);
 int heat2d_group_upload_field(void* g, const void* host, int64_t ld);
 /* heat2d_solver_set_source on every member (each slices its rows of the global array) */
 int heat2d_group_set_source(void* g, const void* host, int64_t ld);
+/* heat2d_solver_set_rmap on every member */
+int heat2d_group_set_rmap(void* g, const void* host, int64_t ld);
 /* whole global owned region -> the members' slabs, then a loopback halo exchange */
 int heat2d_group_upload(void* g, const void* host, int64_t ld);
 /* member i's solver (borrowed handle: valid while the group lives; plan / info / hist queries) */

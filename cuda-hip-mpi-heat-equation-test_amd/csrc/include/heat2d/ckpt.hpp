@@ -23,6 +23,8 @@ struct Meta {
   // the run's heat source: SHA-256 (hex) of the global frame-inclusive array's bytes in the run's
   // dtype, as utils/checkpoint.py records it; empty: none (null, or absent in older saves)
   std::string source_sha256;
+  // the run's diffusivity map, recorded the same way; empty: none (the key is absent)
+  std::string rmap_sha256;
   std::string dir;  // read_meta: the directory holding this step's files
 };
 // A heat source file (--source FILE.npy): a 2-D little-endian f4 / f8 array of exactly rows x cols

@@ -57,6 +57,9 @@ inline int max_tb(DType dt) { return dt == DType::F64 ? kMaxTB : kMaxTBF32; }
 // Deepest pass with a heat source (tb_kernel_src is instantiated for depths
 // 1..kMaxTBSrc, both dtypes; a solver with a source clamps its depth to it).
 constexpr int kMaxTBSrc = 16;
+// Deepest pass with a diffusivity map (tb_kernel_var: depths 1..kMaxTBVar, both
+// dtypes, exact and fma, none with scratch; a solver with a map clamps to it).
+constexpr int kMaxTBVar = 16;
 // Default halo depth (ghost rows per side). Must be >= temporal depth used.
 constexpr int64_t kDefaultHalo = kMaxTB;
 

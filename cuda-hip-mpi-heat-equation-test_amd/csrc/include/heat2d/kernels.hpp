@@ -112,13 +112,20 @@ void launch_ins_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool h
 // entry so that pinned points keep their bits. With a source every rect of the
 // launch runs tb_kernel_src (tb_impl.hpp): Dirichlet on both axes, arith 0 / 1,
 // depths 1..kMaxTBSrc, no wave-pair plans. nullptr: today's dispatch.
+// rmap (optional, after source): the per-point diffusion number R in the
+// field's layout and dtype, the multiplier of every point's update at every
+// fused level, T' = C + R * (sum - 4C) — `r` is then not used. It holds +0.0
+// in every frame row / column, pad entry and row outside the grid: that is the
+// pinning, and a 0 at an owned point holds that point. With a map every rect of
+// the launch runs tb_kernel_var (tb_impl.hpp): Dirichlet on both axes, arith
+// 0 / 1, depths 1..kMaxTBVar, no wave-pair plans, not together with a source.
 void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
                int64_t row_end, int k, double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0,
-               int arith = 0, int bc = 0, const void* source = nullptr);
+               int arith = 0, int bc = 0, const void* source = nullptr, const void* rmap = nullptr);
 // Same for TWO disjoint row ranges [rb0, re0) and [rb1, re1) in one launch.
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
                 int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0,
-                int arith = 0, int bc = 0, const void* source = nullptr);
+                int arith = 0, int bc = 0, const void* source = nullptr, const void* rmap = nullptr);
 
 // Split schedule of one cycle (k steps over the whole slab) into two launches
 // on two streams:
@@ -195,11 +202,12 @@ bool edges_on_main(const SlabLayout& L, const SplitPlan& p);
 // stays clear of the global frame rows, else the general one (edge ranks).
 bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i);
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
-                      hipStream_t stream, int arith = 0, int bc = 0, const void* source = nullptr);
+                      hipStream_t stream, int arith = 0, int bc = 0, const void* source = nullptr,
+                      const void* rmap = nullptr);
 // queue: 2 device counters (zeroed once) for plans with flags & kPlanDynamic (dynamic items)
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
                   double r, hipStream_t stream, int arith = 0, uint32_t* queue = nullptr, int bc = 0,
-                  const void* source = nullptr);
+                  const void* source = nullptr, const void* rmap = nullptr);
 
 // Initial / boundary condition kinds (covers every IC of the reference
 // variants, see models/presets.py for the mapping).

@@ -69,7 +69,14 @@ struct SolverConfig {
   // picks another), engine "tb", no copy_swap; the depth is clamped to
   // kMaxTBSrc. 0: no source, today's solver.
   int32_t source;
-  int32_t pad0;
+  // 1: the solver carries a diffusivity map (u_t = nu(x, y) lap(u), the
+  // non-divergence form): one more buffer in the field's layout, filled by
+  // Solver::set_rmap with the per-point diffusion number R = nu(x, y) dt / dx^2,
+  // the multiplier of every point's update in place of the scalar r
+  // (kernels.hpp launch_tb `rmap`). Dirichlet on both axes, arith exact / fma
+  // (auto resolves to exact), engine "tb", no copy_swap, no source; the depth
+  // is clamped to kMaxTBVar. 0: one r, today's solver.
+  int32_t rmap;
 };
 constexpr int32_t kBcDirichlet = 0, kBcPeriodic = 1, kBcInsulated = 2;
 // the kernels' bit set (kernels.hpp kBcPeriodicX / ... / kBcInsulatedY) of a config
@@ -253,7 +260,8 @@ std::shared_ptr<Transport> make_ipc_loop_transport(int device);
 
 namespace cpu {
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
-        int64_t row_end, int k, double r, int arith = 0, int bc = 0, const void* source = nullptr);
+        int64_t row_end, int k, double r, int arith = 0, int bc = 0, const void* source = nullptr,
+        const void* rmap = nullptr);
 void wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1);
 void wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k);
 // insulated frame images (kern::launch_ins_cols / launch_ins_rows)
@@ -335,7 +343,9 @@ Footprint solver_footprint(const SolverConfig& cfg, int rank, int nranks);
 // whole-field host mirror (fortran/hip/heat.F90:161-176); here the IC is made
 // on the device, so only the two device fields count (three with a heat
 // source: SolverConfig::source).
-int64_t plan_max_grid(int dtype, int nranks, int64_t budget_bytes, int64_t halo = 0, bool source = false);
+// (or a diffusivity map: SolverConfig::rmap)
+int64_t plan_max_grid(int dtype, int nranks, int64_t budget_bytes, int64_t halo = 0, bool source = false,
+                      bool rmap = false);
 
 class Solver {
  public:
@@ -433,6 +443,16 @@ class Solver {
   // without. Between step() calls; invalidates nothing but the captured graphs.
   void set_source(const void* host, int64_t ld);
   bool has_source() const { return src_on_; }
+  // The diffusivity map (SolverConfig::rmap = 1): `host` is the GLOBAL
+  // frame-inclusive array of the per-point diffusion number, (nrows_global + 2)
+  // x (ncols + 2) in the field's dtype, leading dimension ld; this rank copies
+  // its rows, ghost rows included (the map does not change in time: never
+  // exchanged). Owned entries must be finite and >= 0. Frame entries are
+  // ignored: the solver's copy holds +0.0 in every frame row / column, pad entry
+  // and allocated row outside the grid — the kernels' pinning. nullptr returns
+  // to the scalar-r kernels. Between step() calls; drops the captured graphs.
+  void set_rmap(const void* host, int64_t ld);
+  bool has_rmap() const { return rmap_on_; }
   // Cycles launched by step() since the last reset, by depth: hist[k] for
   // k = 0..kMaxTB (graph replays count their two cycles each).
   void cycle_hist(int64_t out[kMaxTB + 1], bool reset);
@@ -533,6 +553,10 @@ class Solver {
   void* src_buf_ = nullptr;  // the heat source (cfg_.source), in L_'s layout
   bool src_on_ = false;      // set_source has filled it
   const void* source() const { return src_on_ ? src_buf_ : nullptr; }
+  void* rmap_buf_ = nullptr;  // the diffusivity map (cfg_.rmap), in L_'s layout
+  bool rmap_on_ = false;      // set_rmap has filled it
+  const void* rmap() const { return rmap_on_ ? rmap_buf_ : nullptr; }
+  void drop_graphs();         // captured graphs hold the kernels of the run with / without a source or map
   int cur_ = 0;
   int64_t steps_ = 0;
   int64_t band_ = 0;     // largest boundary band / halo exchange depth (= K)
@@ -615,6 +639,7 @@ class LoopbackGroup {
   // the whole frame-inclusive field (n + 2) x (n_cols + 2) (Solver::upload_framed per member), then a halo exchange
   void upload_field(const void* host, int64_t ld);
   void set_source(const void* host, int64_t ld);  // Solver::set_source on every member (the global array)
+  void set_rmap(const void* host, int64_t ld);    // Solver::set_rmap on every member (the global array)
   int nranks() const { return (int)members_.size(); }
   Solver& member(int i) { return *members_[i]; }
 

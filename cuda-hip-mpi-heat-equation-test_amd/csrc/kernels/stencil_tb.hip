@@ -298,6 +298,13 @@ int occupancy_src(DType dt, int k, int arith) {
   return dt == DType::F32 ? occupancy_waves_src<float, 0>(k) : occupancy_waves_src<double, 0>(k);
 }
 
+// Diffusivity map (tb_kernel_var): resident waves per CU (one-wave workgroups)
+int occupancy_var(DType dt, int k, int arith) {
+  HEAT2D_REQUIRE(arith == 0 || arith == 1, "a diffusivity map needs arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 assume one r");
+  if (arith == 1) return dt == DType::F32 ? occupancy_waves_var<float, 1>(k) : occupancy_waves_var<double, 1>(k);
+  return dt == DType::F32 ? occupancy_waves_var<float, 0>(k) : occupancy_waves_var<double, 0>(k);
+}
+
 // The frame entries the launchers keep behind a stencil launch over `rects`:
 // periodic y the ghost columns, insulated y the frame columns, insulated x the
 // frame row of a slab at the wall — one fill per run of rows the rects cover
@@ -347,7 +354,19 @@ void fill_frames(DType dt, void* dst, const SlabLayout& L0, const TbRect* rects,
 // most as many waves as that kernel keeps resident.
 int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
                        const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
-                       double* partials, uint32_t* queue, int bc, bool pipe, const void* source = nullptr) {
+                       double* partials, uint32_t* queue, int bc, bool pipe, const void* source = nullptr,
+                       const void* rmap = nullptr) {
+  // rmap != nullptr (the per-point diffusion number in the field's layout, +0.0 at every pinned
+  // point; Dirichlet axes only): every launch, interior ones too, runs tb_kernel_var (ring 4) on at
+  // most as many waves as that kernel keeps resident; `r` is not used.
+  if (rmap) {
+    HEAT2D_REQUIRE(!source, "a diffusivity map and a heat source in one launch: no kernel carries both rings");
+    HEAT2D_REQUIRE(bc == 0, "a diffusivity map needs Dirichlet boundaries on both axes");
+    HEAT2D_REQUIRE(!partials && !pipe, "a diffusivity map has no fused-statistics and no wave-pair kernel");
+    HEAT2D_REQUIRE(k <= kMaxTBVar, "temporal depth exceeds the diffusivity-map kernels' deepest pass (kMaxTBVar)");
+    nwaves = std::min<int64_t>(nwaves, (int64_t)cu_count() * occupancy_var(dt, k, arith));
+    main = false;
+  }
   if (source) {
     HEAT2D_REQUIRE(bc == 0, "a heat source needs Dirichlet boundaries on both axes");
     HEAT2D_REQUIRE(!partials && !pipe, "a heat source has no fused-statistics and no wave-pair kernel");
@@ -397,7 +416,7 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
   a.partials = partials;
   // (the pair kernel and the heat-source kernel record no wave times: HEAT2D_WAVE_TIMES keeps
   // the last other launch's)
-  a.wtimes = (pipe || source) ? nullptr : wave_times_buf(a.nwaves);
+  a.wtimes = (pipe || source || rmap) ? nullptr : wave_times_buf(a.nwaves);  // (nor the diffusivity-map kernel)
   if (arith == 3) {  // scaled levels (tb_impl.hpp AR 3): coefficients of this depth, in double
     HEAT2D_REQUIRE(r > 0.0, "arith 3 (fast) needs r > 0");
     a.fb = (1.0 - 4.0 * r) / r;
@@ -416,6 +435,16 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
       dispatch_pipe<decltype(ar)::value>(k, (unsigned)((a.nwaves + 1) / 2), static_cast<const double*>(src) + o,
                                          static_cast<double*>(dst) + o, a, r, status, stream);
     });
+  } else if (rmap) {
+    if (dt == DType::F32) {
+      const float *s32 = static_cast<const float*>(src) + o, *m32 = static_cast<const float*>(rmap) + o;
+      if (arith == 1) dispatch_var<float, 1>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, m32, stream);
+      else dispatch_var<float, 0>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, m32, stream);
+    } else {
+      const double *s64 = static_cast<const double*>(src) + o, *m64 = static_cast<const double*>(rmap) + o;
+      if (arith == 1) dispatch_var<double, 1>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, m64, stream);
+      else dispatch_var<double, 0>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, m64, stream);
+    }
   } else if (source) {
     if (dt == DType::F32) {
       const float *s32 = static_cast<const float*>(src) + o, *q32 = static_cast<const float*>(source) + o;
@@ -470,17 +499,17 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
 int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
                      const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
                      double* partials = nullptr, uint32_t* queue = nullptr, int bc = 0, bool pipe = false,
-                     const void* source = nullptr) {
+                     const void* source = nullptr, const void* rmap = nullptr) {
   HEAT2D_REQUIRE((bc & ~kBcAll) == 0, "bc must be a set of kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY");
   HEAT2D_REQUIRE(!((bc & kBcPeriodicX) && (bc & kBcInsulatedX)) && !((bc & kBcPeriodicY) && (bc & kBcInsulatedY)),
                  "an axis is periodic or insulated, not both");
   if (!(main && (bc & kBcInsulatedY))) {
     const int64_t nw = launch_rects_1(dt, src, dst, L0, k, ring, main, rects, nrect, nwaves, r, stream, arith, partials,
-                                      queue, bc, pipe, source);
+                                      queue, bc, pipe, source, rmap);
     fill_frames(dt, dst, L0, rects, nrect, bc, stream);
     return nw;
   }
-  HEAT2D_REQUIRE(!source, "a heat source needs Dirichlet boundaries on both axes");
+  HEAT2D_REQUIRE(!source && !rmap, "a heat source / diffusivity map needs Dirichlet boundaries on both axes");
   HEAT2D_REQUIRE(!pipe, "insulated y: the wave-pair kernel's wide strips are not carved (no pipe plans)");
   HEAT2D_REQUIRE(nrect >= 1 && nrect <= kMainRects, "bad rect count");
   const int64_t U = useful_width(dt, k);
@@ -565,13 +594,14 @@ TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end
 }
 
 void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end, int k,
-               double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc, const void* source) {
-  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith, bc, source);
+               double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc, const void* source,
+               const void* rmap) {
+  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith, bc, source, rmap);
 }
 
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
                 int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc,
-                const void* source) {
+                const void* source, const void* rmap) {
   check_layout(dt, L, k);
   const int64_t n0 = std::max<int64_t>(0, re0 - rb0), n1 = std::max<int64_t>(0, re1 - rb1);
   if (n0 + n1 == 0) return;
@@ -586,7 +616,7 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
     if (n0 > 0) rects[nr++] = TbRect{rb0, re0, 0, p.nstrips, -std::min<int64_t>(s0, n0 * p.nstrips)};
     if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, -std::min<int64_t>(std::max<int64_t>(1, ns - s0), n1 * p.nstrips)};
     launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, p.nwaves, r, stream, arith, nullptr, nullptr, bc,
-                 false, source);
+                 false, source, rmap);
     return;
   }
   const int64_t nb = std::max<int64_t>(p.ntiles, (n0 > 0) + (n1 > 0));
@@ -595,7 +625,7 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
   if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, std::min<int64_t>(nb - nb0, n1)};
   const int64_t slots = (int64_t)(cus > 0 ? cus : cu_count()) * p.blocks_per_cu * 4;
   launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, slots, r, stream, arith, nullptr, nullptr, bc, false,
-               source);
+               source, rmap);
 }
 
 // r = 1/4 kernels (arith 2): an interior item costs 3 adds + 2 DPP moves per
@@ -869,19 +899,21 @@ bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i) {
 }
 
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
-                      hipStream_t stream, int arith, int bc, const void* source) {
+                      hipStream_t stream, int arith, int bc, const void* source, const void* rmap) {
   HEAT2D_REQUIRE(i >= 0 && i < p.nedge, "edge rect index");
   const TbRect& R = p.edge[i];
   const bool on_main = edges_on_main(bc_layout(L, bc), p.k, &R, 1);
   const int64_t items = R.nb > 0 ? R.nb * (R.s1 - R.s0) : -R.nb;
   const int64_t slots = (int64_t)cu_count() * occupancy(dt, p.ring, on_main, p.k, arith) * 4;
   launch_rects(dt, src, dst, L, p.k, p.ring, on_main, &R, 1, std::min<int64_t>(items, slots), r, stream, arith,
-               nullptr, nullptr, bc, false, source);
+               nullptr, nullptr, bc, false, source, rmap);
 }
 
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
-                  double r, hipStream_t stream, int arith, uint32_t* queue, int bc, const void* source) {
+                  double r, hipStream_t stream, int arith, uint32_t* queue, int bc, const void* source,
+                  const void* rmap) {
   HEAT2D_REQUIRE(!source || !(p.flags & kPlanPipe), "a heat source has no wave-pair kernel (no pipe plans)");
+  HEAT2D_REQUIRE(!rmap || !(p.flags & kPlanPipe), "a diffusivity map has no wave-pair kernel (no pipe plans)");
   // (SplitPlan::flags & kPlanDynamic: the main part takes its items from the dynamic queue)
   uint32_t* q = (p.flags & kPlanDynamic) ? queue : nullptr;
   HEAT2D_REQUIRE(p.valid, "invalid split plan");
@@ -891,15 +923,15 @@ void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, con
   if (p.valid == 2) {  // single general launch over the whole slab (no edge part)
     if (main_part)
       launch_rects(dt, src, dst, L, p.k, p.ring, false, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc, false,
-                   source);
+                   source, rmap);
     return;
   }
   if (main_part)
     launch_rects(dt, src, dst, L, p.k, p.ring, true, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc,
-                 (p.flags & kPlanPipe) != 0, source);
+                 (p.flags & kPlanPipe) != 0, source, rmap);
   else
     launch_rects(dt, src, dst, L, p.k, p.ring, edges_on_main(bc_layout(L, bc), p.k, p.edge, p.nedge), p.edge, p.nedge,
-                 p.edge_waves, r, stream, arith, nullptr, nullptr, bc, false, source);
+                 p.edge_waves, r, stream, arith, nullptr, nullptr, bc, false, source, rmap);
 }
 
 }  // namespace kern

@@ -380,9 +380,19 @@ struct SrcState<K, RING, true> {
     return *reinterpret_cast<const Q4*>(src_ring<K>() + o + qlane);
   }
 };
+// VAR (tb_kernel_var, a per-point diffusion number: the update's multiplier r
+// is the element of a second field, the map, T' = C + R[i,j] * (sum - 4C)):
+// the map's rows take the way the source rows take — loaded beside the level-0
+// ring into Qb, pushed into the wave-private LDS ring as the centre row, read
+// back by level s as row m + off(s) — and the 16 B a lane reads are the `re` of
+// its elements in update(). The map is the pinning as well: the solver's copy
+// holds +0.0 in every frame row / column, pad entry and row outside the grid
+// (and a dead priming row loads as 0), and r = 0 is what the edge kinds select
+// at those points, so every kind of item runs the one march (EK 0) and has the
+// bits of the scalar kernels' kinds. A VAR march has no source (one ring).
 template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false,
-          bool SRC = false>
-struct March : WallState<INS>, SrcState<K, RING, SRC> {
+          bool SRC = false, bool VAR = false>
+struct March : WallState<INS>, SrcState<K, RING, SRC || VAR> {
   using S = TbShape<T, NV, K>;
   static constexpr int V = S::V;
   static constexpr int VM = S::VM;
@@ -392,6 +402,9 @@ struct March : WallState<INS>, SrcState<K, RING, SRC> {
   static_assert(RING % 2 == 0 && RING >= 4, "ring must be even (parity-indexed level rings) and >= 4");
   static_assert(!SRC || (NV == 1 && CL == K && (AR == 0 || AR == 1) && !ST),
                 "source term: 16 B per lane, one chain, unscaled arithmetic, no fused statistics");
+  static_assert(!VAR || (NV == 1 && CL == K && (AR == 0 || AR == 1) && !ST && !SRC && !INS && EK == 0),
+                "diffusivity map: 16 B per lane, one chain, unscaled arithmetic, no statistics, source or insulated "
+                "edges; the map pins (EK 0)");
 
   const char* srow;  // byte address of (row 0, column -cpad) in src   [wave-uniform]
   char* drow;        // same in dst                                      [wave-uniform]
@@ -484,8 +497,9 @@ struct March : WallState<INS>, SrcState<K, RING, SRC> {
   }
 
   // ((part + N) + W) then C + r*(sum - 4C), pinned columns / rows kept.
+  // (rv — VAR only: the map's elements of this row, the r of each element)
   __device__ __forceinline__ void update(const T (&part)[V], const T (&C)[V], const T (&N)[V], int32_t row,
-                                         T (&out)[V]) const {
+                                         T (&out)[V], const VT* rv = nullptr) const {
     const T west0 = from_lower(C[V - 1]);
     const bool frame_row = (EK & 1) && ((uint32_t)(row - fixed_lo) >= (uint32_t)(fixed_hi - fixed_lo));  // wave-uniform
     const T rs = frame_row ? T(0) : r;                                      // EK 1: scalar select
@@ -502,7 +516,8 @@ struct March : WallState<INS>, SrcState<K, RING, SRC> {
       // stays unfused, as in the reference.
       const T sum = (part[e] + north) + west;
       T re;
-      if constexpr (EK == 0) re = r;
+      if constexpr (VAR) re = (*rv)[e];
+      else if constexpr (EK == 0) re = r;
       else if constexpr (EK == 1) re = rs;
       else if constexpr (EK == 2) re = rl[e];
       else re = frame_row ? T(0) : rl[e];
@@ -535,7 +550,7 @@ struct March : WallState<INS>, SrcState<K, RING, SRC> {
     constexpr int sN = P0, sC = (P0 + RING - 1) % RING, sS = (P0 + RING - 2) % RING;  // level-0 slots
     T part[V];
     T C0[V], N0[V];
-    if constexpr (SRC) this->q_push(this->Qb[sC]);  // source row m + 1 (loaded beside the centre row)
+    if constexpr (SRC || VAR) this->q_push(this->Qb[sC]);  // source / map row m + 1 (loaded beside the centre row)
     {
       T S0[V];
       unpack(Lb[sS], S0);
@@ -550,11 +565,11 @@ struct March : WallState<INS>, SrcState<K, RING, SRC> {
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (kIncPtr) {
         load_row_p(lp, nxt >= mload, Lb[sS]);
-        if constexpr (SRC) this->Qb[sS] = load_q(lp, nxt >= mload);
+        if constexpr (SRC || VAR) this->Qb[sS] = load_q(lp, nxt >= mload);
         lp -= pitch_b;
       } else {
         load_row(nxt >= mload ? nxt : mload, Lb[sS]);
-        if constexpr (SRC) this->Qb[sS] = load_q(srow + (int64_t)(nxt >= mload ? nxt : mload) * pitch_b, true);
+        if constexpr (SRC || VAR) this->Qb[sS] = load_q(srow + (int64_t)(nxt >= mload ? nxt : mload) * pitch_b, true);
       }
     }
     unpack(Lb[sN], N0);
@@ -576,7 +591,12 @@ struct March : WallState<INS>, SrcState<K, RING, SRC> {
       const int ps = Ch::slot(PH, 0, s < K ? s : 1);  // this level's slot of this iteration
       // level s+1's S+E from level s's S (the slot about to be overwritten) and C
       if (s < K) partial(X[ps][s - 1], X[Ch::slot(PH, Ch::delta(s + 1), s)][s - 1], nxtpart, m + Ch::off(s + 1));
-      update(part, C, N, m + Ch::off(s), out);
+      if constexpr (VAR) {  // R(row m + off(s)) is this level's multiplier
+        const VT rv = __builtin_bit_cast(VT, this->q_level(s));
+        update(part, C, N, m + Ch::off(s), out, &rv);
+      } else {
+        update(part, C, N, m + Ch::off(s), out);
+      }
       if constexpr (SRC) {  // + S(row m + off(s)): its own rounded add (-ffp-contract=off)
         const VT q = __builtin_bit_cast(VT, this->q_level(s));
 #pragma unroll
@@ -644,7 +664,7 @@ struct March : WallState<INS>, SrcState<K, RING, SRC> {
     for (int q = RING - 2; q < RING; ++q)
 #pragma unroll
       for (int v = 0; v < NV; ++v) Lb[q][v] = VT{};
-    if constexpr (SRC) {
+    if constexpr (SRC || VAR) {
 #pragma unroll
       for (int q = 0; q < RING - 2; ++q)
         this->Qb[q] = load_q(srow + (int64_t)(mtop - q >= mload ? mtop - q : mload) * pitch_b, true);
@@ -690,8 +710,10 @@ struct March : WallState<INS>, SrcState<K, RING, SRC> {
 // descriptors / edge kinds are March's.
 // SRC: a source row sits in LDS in the even/odd order (c0, c2, c1, c3), so a
 // level adds it with two packed adds (see SrcState).
-template <int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false, bool SRC = false>
-struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
+// VAR: a map row sits there in the same order and is the Row `re` of the level.
+template <int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false, bool SRC = false,
+          bool VAR = false>
+struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC || VAR> {
   using F2 = float __attribute__((ext_vector_type(2)));
   using VT = float __attribute__((ext_vector_type(4)));
   using U4 = unsigned int __attribute__((ext_vector_type(4)));
@@ -699,6 +721,8 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
   static_assert(RING % 2 == 0 && RING >= 4, "ring must be even and >= 4");
   static_assert(!SRC || (CL == K && (AR == 0 || AR == 1) && !ST),
                 "source term: one chain, unscaled arithmetic, no fused statistics");
+  static_assert(!VAR || (CL == K && (AR == 0 || AR == 1) && !ST && !SRC && !INS && EK == 0),
+                "diffusivity map: one chain, unscaled arithmetic, no statistics, source or insulated edges; the map pins");
   struct Row {
     F2 a, b;  // a = (c0, c2), b = (c1, c3)
   };
@@ -790,13 +814,16 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
     return __builtin_fmaf(re, sum, __builtin_fmaf(re, -4.f * c, c));
   }
   // sum - 4C (in) and the per-element r (re) of the update C + r*(sum - 4C)
+  // (rv — VAR only: the map's elements of this row)
   __device__ __forceinline__ void terms(const Row& part, const Row& C, const Row& N, int32_t row, Row& in,
-                                        Row& re) const {
+                                        Row& re, const Row* rv = nullptr) const {
     const Row sum = sum4(part, C, N, row);
     const F2 m4 = {-4.f, -4.f};
     in = Row{__builtin_elementwise_fma(m4, C.a, sum.a), __builtin_elementwise_fma(m4, C.b, sum.b)};
     const bool frame_row = (EK & 1) && ((uint32_t)(row - fixed_lo) >= (uint32_t)(fixed_hi - fixed_lo));  // wave-uniform
-    if constexpr (EK == 0) {
+    if constexpr (VAR) {
+      re = *rv;
+    } else if constexpr (EK == 0) {
       re = Row{F2{r, r}, F2{r, r}};
     } else if constexpr (EK == 1) {
       const float rs = frame_row ? 0.f : r;
@@ -808,7 +835,8 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
       re = frame_row ? Row{z, z} : rl;
     }
   }
-  __device__ __forceinline__ Row update(const Row& part, const Row& C, const Row& N, int32_t row) const {
+  __device__ __forceinline__ Row update(const Row& part, const Row& C, const Row& N, int32_t row,
+                                        const Row* rv = nullptr) const {
     if constexpr (AR == 3 && EK == 0) {  // scaled: fma(b, C, sum) on packed pairs
       const Row sum = sum4(part, C, N, row);
       const F2 b2 = {fb, fb};
@@ -828,7 +856,7 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
       return Row{pin2(re.a, sum.a, C.a), pin2(re.b, sum.b, C.b)};
     }
     Row in, re;
-    terms(part, C, N, row, in, re);
+    terms(part, C, N, row, in, re, rv);
     if constexpr (AR == 1)
       return Row{__builtin_elementwise_fma(re.a, in.a, C.a), __builtin_elementwise_fma(re.b, in.b, C.b)};
     else
@@ -841,7 +869,8 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
   // The stored (last) level: its 4 final ops as scalar fp32 ops writing the
   // store vector in memory order (c0, c1, c2, c3) — a packed op would produce
   // the even/odd pairs and need a transpose before the 16-B store.
-  __device__ __forceinline__ VT update_last(const Row& part, const Row& C, const Row& N, int32_t row) const {
+  __device__ __forceinline__ VT update_last(const Row& part, const Row& C, const Row& N, int32_t row,
+                                            const Row* rv = nullptr) const {
     if constexpr (AR == 3 && EK == 0) {  // scaled level K, unscaled by r^K at the store
       const Row sum = sum4(part, C, N, row);
       return VT{__builtin_fmaf(fb, C.a.x, sum.a.x) * fu, __builtin_fmaf(fb, C.b.x, sum.b.x) * fu,
@@ -866,7 +895,7 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
                 pin1(re.b.y, sum.b.y, C.b.y)};
     }
     Row in, re;
-    terms(part, C, N, row, in, re);
+    terms(part, C, N, row, in, re, rv);
     return VT{fin(re.a.x, in.a.x, C.a.x), fin(re.b.x, in.b.x, C.b.x), fin(re.a.y, in.a.y, C.a.y),
               fin(re.b.y, in.b.y, C.b.y)};
   }
@@ -876,7 +905,7 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
     constexpr int P0 = PH % RING;
     constexpr int sN = P0, sC = (P0 + RING - 1) % RING, sS = (P0 + RING - 2) % RING;
     const Row C0 = Lb[sC];
-    if constexpr (SRC) {  // source row m + 1 (loaded beside the centre row), as (c0, c2, c1, c3)
+    if constexpr (SRC || VAR) {  // source / map row m + 1 (loaded beside the centre row), as (c0, c2, c1, c3)
       const U4 q = this->Qb[sC];
       this->q_push(U4{q.x, q.z, q.y, q.w});
     }
@@ -885,7 +914,7 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
       const int32_t nxt = m + 2 - RING;
       __builtin_amdgcn_sched_barrier(0);
       load_row_p(lp, nxt >= mload, Lb[sS]);
-      if constexpr (SRC) this->Qb[sS] = load_q(lp, nxt >= mload);
+      if constexpr (SRC || VAR) this->Qb[sS] = load_q(lp, nxt >= mload);
       lp -= pitch_b;
     }
     Lb[sN] = split(Lb[sN]);  // first use of this row: to even/odd form, in place
@@ -901,7 +930,13 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
         const int i = s < K ? s - 1 : 0;
         const int ps = Ch::slot(PH, 0, s < K ? s : 1);
         const Row nxtpart = partial(X[ps][i], X[Ch::slot(PH, Ch::delta(s + 1), s < K ? s : 1)][i], m + Ch::off(s + 1));
-        X[ps][i] = update(part, C, N, m + Ch::off(s));
+        if constexpr (VAR) {  // R(row m + off(s)), a = (c0, c2), b = (c1, c3) as the ring holds it
+          const VT q = __builtin_bit_cast(VT, this->q_level(s));
+          const Row rv{F2{q.x, q.y}, F2{q.z, q.w}};
+          X[ps][i] = update(part, C, N, m + Ch::off(s), &rv);
+        } else {
+          X[ps][i] = update(part, C, N, m + Ch::off(s));
+        }
         if constexpr (SRC) {  // + S(row m + off(s)): its own rounded add (-ffp-contract=off)
           const VT q = __builtin_bit_cast(VT, this->q_level(s));
           X[ps][i] = Row{X[ps][i].a + F2{q.x, q.y}, X[ps][i].b + F2{q.z, q.w}};
@@ -910,7 +945,14 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
       } else {
         const int32_t row = m + Ch::off(K);
         const bool live = (uint32_t)(row - t0) < (uint32_t)(t1 - t0);  // row in [t0, t1), wave-uniform
-        VT w = update_last(part, C, N, row);
+        VT w;
+        if constexpr (VAR) {
+          const VT q = __builtin_bit_cast(VT, this->q_level(K));
+          const Row rv{F2{q.x, q.y}, F2{q.z, q.w}};
+          w = update_last(part, C, N, row, &rv);
+        } else {
+          w = update_last(part, C, N, row);
+        }
         if constexpr (SRC) {  // (w in memory order, the ring row as (c0, c2, c1, c3))
           const VT q = __builtin_bit_cast(VT, this->q_level(K));
           w = VT{w.x + q.x, w.y + q.z, w.z + q.y, w.w + q.w};
@@ -955,7 +997,7 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC> {
     for (int q = 0; q < RING - 2; ++q) load_row(mtop - q >= mload ? mtop - q : mload, Lb[q]);
 #pragma unroll
     for (int q = RING - 2; q < RING; ++q) Lb[q] = Row{F2{0.f, 0.f}, F2{0.f, 0.f}};
-    if constexpr (SRC) {
+    if constexpr (SRC || VAR) {
 #pragma unroll
       for (int q = 0; q < RING - 2; ++q)
         this->Qb[q] = load_q(srow + (int64_t)(mtop - q >= mload ? mtop - q : mload) * pitch_b, true);
@@ -998,7 +1040,7 @@ constexpr bool kPackedF32 = false;
 constexpr int kInsRowLo = 1, kInsRowHi = 2, kInsColLo = 4, kInsColHi = 8;
 
 template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, bool PS = false, int CLX = 0,
-          bool INS = false, bool SRC = false>
+          bool INS = false, bool SRC = false, bool VAR = false>
 __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r, int64_t strip, int64_t t0,
                                       int64_t t1, int lane, StatAcc* acc = nullptr, int ins = 0,
                                       const T* qsrc = nullptr) {
@@ -1013,8 +1055,8 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
   // the chains' extra rows spill at fp64 K >= 21
   // (CLX > 0: an explicit chain length — the boundary-band kernel)
   constexpr int CL = CLX > 0 ? (CLX < K ? CLX : K) : (ST ? K : chain_len<T, K>());
-  using W = typename std::conditional<kPackedF32<T, NV>, MarchF32<K, EK, RING, AR, ST, CL, INS, SRC>,
-                                      March<T, NV, K, EK, RING, AR, ST, CL, INS, SRC>>::type;
+  using W = typename std::conditional<kPackedF32<T, NV>, MarchF32<K, EK, RING, AR, ST, CL, INS, SRC, VAR>,
+                                      March<T, NV, K, EK, RING, AR, ST, CL, INS, SRC, VAR>>::type;
   W w;
   // row base = column col_lo (= -cpad) of row 0; offsets are relative to it
   w.srow = reinterpret_cast<const char*>(src + a.col_lo);
@@ -1064,7 +1106,7 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
     for (int e = 0; e < V; ++e) me |= ((ins & kInsColHi) && mycol + e == a.ncols - 1) ? (1u << e) : 0u;
     w.wall_e = me;
   }
-  if constexpr (SRC) {  // the source buffer has the field's layout
+  if constexpr (SRC || VAR) {  // the source buffer / the map (qsrc) has the field's layout
     w.qrow = reinterpret_cast<const char*>(qsrc + a.col_lo);
     w.qdelta = w.qrow - w.srow;
     w.q_reset(lane);
@@ -1356,6 +1398,35 @@ __global__ __launch_bounds__(64) void tb_kernel_src(const T* __restrict__ src, T
   queue_exit(a);
 }
 
+// The general kernel with a diffusivity map (`rmap`: the per-point diffusion
+// number in the field's layout, +0.0 at every pinned point, an argument of this
+// kernel only — TbArgs and every other kernel stay as they are; the scalar r is
+// not an argument). The same items as the general kernel; every item, whatever
+// its edge kind, runs the one march whose multiplier is the map's element
+// (March VAR: the map's zeros are the frame rows, frame columns and pads the
+// kinds would select). One wave per workgroup: the wave's ring of K map rows
+// in LDS (K KiB) is the workgroup's whole allocation; nothing waits on another wave.
+template <typename T, int NV, int K, int RING, int AR>
+__global__ __launch_bounds__(64) void tb_kernel_var(const T* __restrict__ src, T* __restrict__ dst, TbArgs a,
+                                                    const T* __restrict__ rmap) {
+  const int lane = threadIdx.x;
+  const int64_t wid = (int64_t)blockIdx.x;
+  if (wid >= a.nwaves) return;
+  int64_t it = wid;
+  int32_t lin = tb_span<kMaxRects>(a, it).lin;
+  while (it < a.nitems) {
+    int64_t strip, t0, t1;
+    if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {
+      it = next_item(a, it);
+      if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;
+      continue;
+    }
+    lin += (int32_t)(t1 - t0);
+    march<T, NV, K, 0, RING, AR, false, false, K, false, false, true>(src, dst, a, T(0), strip, t0, t1, lane, nullptr, 0, rmap);
+  }
+  queue_exit(a);
+}
+
 template <typename T, int NV, int K, int RING, bool MAIN, int AR, int VAR = kVarPlain>
 constexpr auto kernel_ptr() {
   return &tb_kernel<T, NV, K, RING, MAIN, AR, VAR>;
@@ -1401,6 +1472,11 @@ template <typename T, int AR>
 void dispatch_src(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, T r, const T* q, hipStream_t s);
 template <typename T, int AR>
 int occupancy_waves_src(int k);
+// diffusivity-map kernels: ring 4, depths 1..kMaxTBVar (tb_<dtype>_var[_fma].hip)
+template <typename T, int AR>
+void dispatch_var(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, const T* rmap, hipStream_t s);
+template <typename T, int AR>
+int occupancy_waves_var(int k);
 #define H2D_TB_CASE(T, RING, MAIN, AR, KK)                                                                    \
   case KK:                                                                                                    \
     hipLaunchKernelGGL((tb_kernel<T, 1, KK, RING, MAIN, AR>), dim3(nblocks), dim3(256), 0, s, src, dst, a, r); \
@@ -1569,6 +1645,52 @@ int waves_per_cu_src() {
   int occupancy_waves_src<T, AR>(int k) {                                                                     \
     switch (k) {                                                                                              \
       H2D_TB_CASES(H2D_SRC_OCC_CASE, T, 4, false, AR)                                                         \
+      default:                                                                                                \
+        break;                                                                                                \
+    }                                                                                                         \
+    return 4;                                                                                                 \
+  }
+
+// resident waves (one-wave workgroups) per CU of one tb_kernel_var instance
+template <typename T, int K, int AR>
+int waves_per_cu_var() {
+  static std::mutex mu;
+  static std::map<int, int> cache;  // device -> waves/CU
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> g(mu);
+  auto it = cache.find(dev);
+  if (it != cache.end()) return it->second;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tb_kernel_var<T, 1, K, 4, AR>), 64,
+                                                   0) != hipSuccess ||
+      nb <= 0)
+    nb = 4;
+  cache[dev] = nb;
+  return nb;
+}
+#define H2D_VAR_CASE(T, RING, MAIN, AR, KK)                                                                   \
+  case KK:                                                                                                    \
+    hipLaunchKernelGGL((tb_kernel_var<T, 1, KK, 4, AR>), dim3(nwaves), dim3(64), 0, s, src, dst, a, rmap);    \
+    return;
+#define H2D_VAR_OCC_CASE(T, RING, MAIN, AR, KK) \
+  case KK:                                      \
+    return waves_per_cu_var<T, KK, AR>();
+#define H2D_VAR_UNIT(T, AR)                                                                                   \
+  template <>                                                                                                 \
+  void dispatch_var<T, AR>(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, const T* rmap,      \
+                           hipStream_t s) {                                                                   \
+    switch (k) {                                                                                              \
+      H2D_TB_CASES(H2D_VAR_CASE, T, 4, false, AR)                                                             \
+      default:                                                                                                \
+        break;                                                                                                \
+    }                                                                                                         \
+    HEAT2D_REQUIRE(false, "temporal depth not instantiated for the diffusivity-map kernel");                  \
+  }                                                                                                           \
+  template <>                                                                                                 \
+  int occupancy_waves_var<T, AR>(int k) {                                                                     \
+    switch (k) {                                                                                              \
+      H2D_TB_CASES(H2D_VAR_OCC_CASE, T, 4, false, AR)                                                         \
       default:                                                                                                \
         break;                                                                                                \
     }                                                                                                         \

@@ -224,12 +224,14 @@ void write_meta(const std::string& dir, const std::string& name, const Meta& m) 
                 "{\n \"format\": \"%s\",\n \"step\": %lld,\n \"nranks\": %d,\n \"dtype\": \"%s\",\n"
                 " \"n_owned\": %lld,\n \"n_input\": %lld,\n \"convention\": \"%s\",\n \"sigma\": %.17g,\n"
                 " \"nu\": %.17g,\n \"dom_len\": %.17g,\n \"r\": %.17g,\n \"edge_shift\": %lld,\n"
-                " \"bc_x\": \"%s\",\n \"bc_y\": \"%s\",\n \"source_sha256\": %s,\n"
+                " \"bc_x\": \"%s\",\n \"bc_y\": \"%s\",\n \"source_sha256\": %s,\n%s"
                 " \"writer\": \"heat2d-cli\"\n}\n",
                 kFormat, (long long)m.step, m.nranks, m.dtype == 0 ? "fp32" : "fp64", (long long)m.n_owned,
                 (long long)m.n_input, m.convention.c_str(), m.sigma, m.nu, m.dom_len, m.r, (long long)m.edge_shift,
                 m.bc_x.c_str(), m.bc_y.c_str(),
-                m.source_sha256.empty() ? "null" : ("\"" + m.source_sha256 + "\"").c_str());
+                m.source_sha256.empty() ? "null" : ("\"" + m.source_sha256 + "\"").c_str(),
+                // (the key only with a diffusivity map: saves without one keep their key set)
+                m.rmap_sha256.empty() ? "" : (" \"rmap_sha256\": \"" + m.rmap_sha256 + "\",\n").c_str());
   write_atomic(join(join(dir, name), "meta.json"), buf);  // + fsync of the step directory (rank files' entries)
   write_atomic(join(dir, "latest"), name + "\n");  // the commit point
   // prune: keep the two newest complete saves, ordered by (step, generation)
@@ -288,6 +290,11 @@ Meta read_meta(const std::string& dir) {
     m.source_sha256 = json_value(js, "source_sha256");
     while (!m.source_sha256.empty() && (m.source_sha256.back() == ' ' || m.source_sha256.back() == '\r')) m.source_sha256.pop_back();
     if (m.source_sha256 == "null") m.source_sha256.clear();
+  }
+  if (js.find("\"rmap_sha256\"") != std::string::npos) {
+    m.rmap_sha256 = json_value(js, "rmap_sha256");
+    while (!m.rmap_sha256.empty() && (m.rmap_sha256.back() == ' ' || m.rmap_sha256.back() == '\r')) m.rmap_sha256.pop_back();
+    if (m.rmap_sha256 == "null") m.rmap_sha256.clear();
   }
   auto bc_ok = [](const std::string& v) { return v == "dirichlet" || v == "periodic" || v == "insulated"; };
   HEAT2D_REQUIRE(bc_ok(m.bc_x) && bc_ok(m.bc_y), dir + ": meta.json: bc_x / bc_y must be dirichlet, periodic or insulated");

@@ -74,20 +74,21 @@ SlabLayout solver_layout(const SolverConfig& cfg, int rank, int nranks) {
 Footprint solver_footprint(const SolverConfig& cfg, int rank, int nranks) {
   const SlabLayout L = solver_layout(cfg, rank, nranks);
   Footprint f{};
-  f.field_bytes = (cfg.source ? 3 : 2) * L.elems() * (int64_t)dtype_size((DType)cfg.dtype);
+  f.field_bytes = (2 + (cfg.source ? 1 : 0) + (cfg.rmap ? 1 : 0)) * L.elems() * (int64_t)dtype_size((DType)cfg.dtype);
   if (cfg.backend == (int32_t)Backend::Hip)
     f.work_bytes = (kern::stats_work_elems() + 8) * 8 + 6 * kern::max_stats_waves() * 8 + 2 * 4;
   f.total_bytes = f.field_bytes + f.work_bytes;
   return f;
 }
 
-int64_t plan_max_grid(int dtype, int nranks, int64_t budget_bytes, int64_t halo, bool source) {
+int64_t plan_max_grid(int dtype, int nranks, int64_t budget_bytes, int64_t halo, bool source, bool rmap) {
   HEAT2D_REQUIRE(nranks >= 1 && budget_bytes > 0, "plan_max_grid needs nranks >= 1 and a positive budget");
   SolverConfig c{};
   c.dtype = dtype;
   c.backend = (int32_t)Backend::Hip;
   c.halo = halo;
   c.source = source ? 1 : 0;
+  c.rmap = rmap ? 1 : 0;
   // the largest slab is rank 0's (decompose() gives the remainder to the first ranks)
   auto fits = [&](int64_t n) {
     c.n_rows = c.n_cols = n;
@@ -137,6 +138,21 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
     HEAT2D_REQUIRE(cfg_.engine == 0, "a heat source needs the temporal-blocked engine (engine \"jit\" has no source term)");
     HEAT2D_REQUIRE(!cfg_.copy_swap, "a heat source has no copy-swap mode");
     K = std::min<int>(K, kMaxTBSrc);  // the source kernels' deepest pass
+  }
+  HEAT2D_REQUIRE(cfg_.rmap == 0 || cfg_.rmap == 1, "rmap must be 0 or 1");
+  if (cfg_.rmap) {
+    HEAT2D_REQUIRE(!cfg_.source,
+                   "a diffusivity map and a heat source together: no kernel carries both rings yet (a known limit)");
+    HEAT2D_REQUIRE(cfg_.arith != 2 && cfg_.arith != 3,
+                   "a diffusivity map has no arith jacobi / fast: their scaled levels assume one r for the whole grid "
+                   "(use exact, fma or auto)");
+    HEAT2D_REQUIRE(cfg_.bc_x == kBcDirichlet && cfg_.bc_y == kBcDirichlet,
+                   "a diffusivity map needs Dirichlet boundaries on both axes (no periodic or insulated map kernels)");
+    HEAT2D_REQUIRE(cfg_.engine == 0, "a diffusivity map needs the temporal-blocked engine (engine \"jit\" takes one r)");
+    HEAT2D_REQUIRE(!cfg_.copy_swap, "a diffusivity map has no copy-swap mode");
+    K = std::min<int>(K, kMaxTBVar);  // the map kernels' deepest pass
+    // auto: exact (fma has the reference's bits only where every multiplier is a power of two)
+    if (cfg_.arith < 0) cfg_.arith = 0;
   }
   if (cfg_.arith < 0) {
     // auto: the contracted form when it is bitwise identical to the reference
@@ -211,6 +227,7 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
       else H2D_HIP(hipMalloc(&buf_[b], alloc));
     }
     if (cfg_.source) H2D_HIP(hipMalloc(&src_buf_, bytes));
+    if (cfg_.rmap) H2D_HIP(hipMalloc(&rmap_buf_, bytes));
     // (solver_footprint() counts exactly these allocations: keep them in step)
     H2D_HIP(hipMalloc(reinterpret_cast<void**>(&d_work_), (size_t)(kern::stats_work_elems() + 8) * sizeof(double)));
     H2D_HIP(hipMalloc(reinterpret_cast<void**>(&d_part_), (size_t)(6 * kern::max_stats_waves()) * sizeof(double)));
@@ -265,6 +282,7 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
   } else {
     for (int b = 0; b < 2; ++b) buf_[b] = host_alloc(bytes);
     if (cfg_.source) src_buf_ = host_alloc(bytes);
+    if (cfg_.rmap) rmap_buf_ = host_alloc(bytes);
     cfg_.overlap = 0;
     cfg_.use_graph = 0;
   }
@@ -281,6 +299,7 @@ Solver::~Solver() {
     for (auto& b : buf_)
       if (b) (void)hipFree(b);
     if (src_buf_) (void)hipFree(src_buf_);
+    if (rmap_buf_) (void)hipFree(rmap_buf_);
     if (d_work_) (void)hipFree(d_work_);
     if (d_part_) (void)hipFree(d_part_);
     if (d_queue_) (void)hipFree(d_queue_);
@@ -298,6 +317,7 @@ Solver::~Solver() {
   } else {
     for (auto& b : buf_) std::free(b);
     std::free(src_buf_);
+    std::free(rmap_buf_);
   }
 }
 
@@ -349,15 +369,16 @@ void Solver::wrap_cols_all(void* field) {
 
 bool Solver::pipe_ok(int k) const {
   // (nor with a heat source: the source kernel is the one-wave general one)
-  return kern::pipe_available(dtype(), k, cfg_.arith) && !(bc_ & kern::kBcInsulatedY) && !cfg_.source;
+  // (nor with a diffusivity map, for the same reason)
+  return kern::pipe_available(dtype(), k, cfg_.arith) && !(bc_ & kern::kBcInsulatedY) && !cfg_.source && !cfg_.rmap;
 }
 
 void Solver::launch_tb(const void* src, void* dst, int64_t rb, int64_t re, int k) {
   if (re <= rb) return;
   if (hip_)
-    kern::launch_tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, s_compute_, cfg_.tile_rows, compute_cus_, cfg_.arith, bc_, source());
+    kern::launch_tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, s_compute_, cfg_.tile_rows, compute_cus_, cfg_.arith, bc_, source(), rmap());
   else
-    cpu::tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, cfg_.arith, bc_, source());
+    cpu::tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, cfg_.arith, bc_, source(), rmap());
 }
 
 void Solver::exchange_on(void* field, int64_t k, hipStream_t s) {
@@ -484,7 +505,7 @@ void Solver::cycle_finish() {
     if (pe) H2D_HIP(hipEventRecord(pe->ev[5], s_comm_));
     if (pend_frame_ >= 0) {  // the edge rank's frame-side band (launch_overlap), after the exchange
       kern::launch_edge_rect(dtype(), buf_[cur_], dst, L_, split_plan_banded(pend_k_, pend_frame_b_), pend_frame_, cfg_.r,
-                             s_comm_, cfg_.arith, bc_, source());
+                             s_comm_, cfg_.arith, bc_, source(), rmap());
       // the next cycle's compute-stream work waits for it (and so for the
       // exchange ahead of it); ev_bnd_, posted to the transport, is left alone
       H2D_HIP(hipEventRecord(ev_frame_, s_comm_));
@@ -747,8 +768,8 @@ void Solver::trial_cycle(const kern::SplitPlan& c) {
   last_k_ = 0;  // the other buffer no longer holds T_{n-1}: stats(residual) reports NaN
   if (c.valid == 3) {  // edge-first: both parts in order on the compute stream
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
-    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source());
-    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source());
+    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap());
+    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
     return;
@@ -756,15 +777,15 @@ void Solver::trial_cycle(const kern::SplitPlan& c) {
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
   H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));
   if (c.flags & kern::kPlanLead) {  // lead: the band launch issued first
-    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source());
-    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source());
+    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap());
+    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
     return;
   }
-  kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source());
+  kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
   H2D_HIP(hipEventRecord(ev_int_, s_compute_));
-  kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source());
+  kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap());
   H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
 }
 
@@ -829,7 +850,8 @@ std::string Solver::cache_ctx() const {
                 (long long)L_.pitch, (long long)L_.halo, pos, compute_cus_, spare_waves(), tr_->exchanges() ? 1 : 0,
                 tr_->name().c_str(), (int)cfg_.bc_x, (int)cfg_.bc_y, (unsigned long long)plan_env_hash());
   // (plans tuned with the source kernels are another family; keys without a source stay as they were)
-  return cfg_.source ? std::string(b) + "|src1" : std::string(b);
+  // (and so are plans tuned with the diffusivity-map kernels)
+  return std::string(b) + (cfg_.source ? "|src1" : "") + (cfg_.rmap ? "|rmap1" : "");
 }
 
 // The cached autotuned plan of depth k for this slab, re-validated by one
@@ -1166,9 +1188,9 @@ void Solver::launch_overlap(int k, int64_t B) {
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));  // edge part c-1
     H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));     // main part c-1
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_comm_));
-    kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, cfg_.arith, bc_, source());
+    kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, cfg_.arith, bc_, source(), rmap());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_comm_));
@@ -1184,12 +1206,12 @@ void Solver::launch_overlap(int k, int64_t B) {
     // comm stream (cycle_finish) = [bands(c) done] exchange(c), beside the interior.
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_comm_, 0));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
     if (tr_->exchanges()) tr_->post(dst, L_, ev_bnd_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     pend_ = Pending::EdgeFirst;
@@ -1200,23 +1222,23 @@ void Solver::launch_overlap(int k, int64_t B) {
   if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_comm_));
   if (lead) {
     // lead: the band launch first (comm stream), then the interior beside it
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
   } else if (sp.valid) {
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap());
   } else {  // slab too thin / narrow to split: all of it beside the exchange
     if (pe) {
       H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
       H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     }
-    kern::launch_tb(dtype(), src, dst, L_, 0, L_.nrows, k, cfg_.r, s_comm_, 0, 0, cfg_.arith, bc_, source());
+    kern::launch_tb(dtype(), src, dst, L_, 0, L_.nrows, k, cfg_.r, s_comm_, 0, 0, cfg_.arith, bc_, source(), rmap());
   }
   if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_comm_));
   H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
@@ -1912,7 +1934,7 @@ void Solver::step_stats(int64_t n, double out[6]) {
   // (periodic y: the fused-statistics march would count its ghost columns;
   // insulated axes: the fused-statistics kernel has no insulated edges)
   // (a heat source: the fused-statistics kernel has no source term)
-  if (!hip_ || jit_ || cfg_.copy_swap || cfg_.bc_y || cfg_.bc_x == kBcInsulated || cfg_.source) {
+  if (!hip_ || jit_ || cfg_.copy_swap || cfg_.bc_y || cfg_.bc_x == kBcInsulated || cfg_.source || cfg_.rmap) {
     step(n - 1);
     step(1);
     stats(out, true);
@@ -2064,21 +2086,23 @@ void Solver::upload_framed(const void* host, int64_t ld) {
   if (hip_) H2D_HIP(hipStreamSynchronize(s_compute_));
 }
 
+void Solver::drop_graphs() {
+  if (!hip_) return;
+  H2D_HIP(hipSetDevice(cfg_.device));
+  synchronize();
+  if (graph_exec_) {
+    hipGraphExec_t old = graph_exec_;
+    graph_exec_ = nullptr;
+    H2D_HIP(hipGraphExecDestroy(old));
+  }
+  for (auto& g : sched_graph_) (void)hipGraphExecDestroy(g.second);
+  sched_graph_.clear();
+}
+
 void Solver::set_source(const void* host, int64_t ld) {
   HEAT2D_REQUIRE(host == nullptr || cfg_.source,
                  "this solver was built without a heat source (SolverConfig::source = 0): pass source= when it is created");
-  if (hip_) {
-    H2D_HIP(hipSetDevice(cfg_.device));
-    synchronize();
-    // captured graphs hold the kernels of the run with / without a source
-    if (graph_exec_) {
-      hipGraphExec_t old = graph_exec_;
-      graph_exec_ = nullptr;
-      H2D_HIP(hipGraphExecDestroy(old));
-    }
-    for (auto& g : sched_graph_) (void)hipGraphExecDestroy(g.second);
-    sched_graph_.clear();
-  }
+  drop_graphs();
   if (!host) {
     src_on_ = false;
     return;
@@ -2100,6 +2124,41 @@ void Solver::set_source(const void* host, int64_t ld) {
   if (hip_) H2D_HIP(hipMemcpy(src_buf_, stage.data(), stage.size(), hipMemcpyHostToDevice));
   else std::memcpy(src_buf_, stage.data(), stage.size());
   src_on_ = true;
+}
+
+void Solver::set_rmap(const void* host, int64_t ld) {
+  HEAT2D_REQUIRE(host == nullptr || cfg_.rmap,
+                 "this solver was built without a diffusivity map (SolverConfig::rmap = 0): pass rmap= when it is created");
+  if (!host) {
+    drop_graphs();
+    rmap_on_ = false;
+    return;
+  }
+  HEAT2D_REQUIRE(ld >= L_.ncols + 2, "set_rmap: leading dimension below ncols + 2");
+  // this rank's copy: +0.0 everywhere (the kernels' pinning: frame rows and
+  // columns, pad entries, allocated rows outside the grid), then the owned
+  // points of every allocated row that is an owned row of the global grid
+  const size_t es = dtype_size(dtype());
+  std::vector<char> stage((size_t)L_.elems() * es, 0);
+  bool ok = true;
+  for (int64_t i = -L_.halo; i < L_.nrows + L_.halo; ++i) {
+    const int64_t g = L_.row0 + i;
+    if (g < 0 || g >= L_.nrows_global) continue;
+    char* to = stage.data() + (size_t)L_.offset(i, 0) * es;
+    std::memcpy(to, static_cast<const char*>(host) + (size_t)((g + 1) * ld + 1) * es, (size_t)L_.ncols * es);
+    if (dtype() == DType::F32) {
+      const float* v = reinterpret_cast<const float*>(to);
+      for (int64_t j = 0; j < L_.ncols; ++j) ok = ok && std::isfinite(v[j]) && v[j] >= 0.f;
+    } else {
+      const double* v = reinterpret_cast<const double*>(to);
+      for (int64_t j = 0; j < L_.ncols; ++j) ok = ok && std::isfinite(v[j]) && v[j] >= 0.0;
+    }
+  }
+  HEAT2D_REQUIRE(ok, "set_rmap: the owned entries of a diffusivity map must be finite and >= 0");
+  drop_graphs();
+  if (hip_) H2D_HIP(hipMemcpy(rmap_buf_, stage.data(), stage.size(), hipMemcpyHostToDevice));
+  else std::memcpy(rmap_buf_, stage.data(), stage.size());
+  rmap_on_ = true;
 }
 
 void Solver::upload_field(const void* host, int64_t ld) {
@@ -2194,6 +2253,10 @@ void LoopbackGroup::upload(const void* host, int64_t ld) {
 
 void LoopbackGroup::set_source(const void* host, int64_t ld) {
   for (auto& m : members_) m->set_source(host, ld);
+}
+
+void LoopbackGroup::set_rmap(const void* host, int64_t ld) {
+  for (auto& m : members_) m->set_rmap(host, ld);
 }
 
 void LoopbackGroup::upload_field(const void* host, int64_t ld) {

@@ -88,6 +88,34 @@ def _source_info(h) -> dict:
     return {"enabled": bool(v[0]), "set": bool(v[1]), "max_tb": int(v[2]) if v[0] else 0}
 
 
+def _rmap_array(rmap, nrows_global: int, ncols: int, np_dtype) -> np.ndarray:
+    """The global frame-inclusive diffusivity map in the field's dtype (a wrong
+    shape, or an owned entry that is negative or not finite, fails)."""
+    a = np.ascontiguousarray(rmap, dtype=np_dtype)
+    if a.shape != (nrows_global + 2, ncols + 2):
+        raise ValueError(f"rmap must be the frame-inclusive global array {(nrows_global + 2, ncols + 2)}, "
+                         f"got {a.shape}")
+    own = a[1:-1, 1:-1]
+    if not (np.isfinite(own).all() and (own >= 0).all()):
+        raise ValueError("the owned entries of rmap must be finite and >= 0")
+    return a
+
+
+def _rmap_info(h) -> dict:
+    """info()["rmap"]: whether the solver was built for a diffusivity map,
+    whether one is set, and the depth clamp that then applies (0: none)."""
+    v = (C.c_int32 * 3)()
+    N.call("heat2d_solver_rmap", h, v)
+    return {"enabled": bool(v[0]), "set": bool(v[1]), "max_tb": int(v[2]) if v[0] else 0}
+
+
+def rmap_from_nu(problem: Problem, nu_xy) -> np.ndarray:
+    """The diffusion-number map of a diffusivity field: ``problem.r * nu_xy /
+    problem.nu`` in float64 (r = nu dt / dx^2 scales with nu; ``nu_xy`` is nu on
+    the frame-inclusive grid, the array ``rmap=`` takes)."""
+    return np.float64(problem.r) * np.asarray(nu_xy, dtype=np.float64) / np.float64(problem.nu)
+
+
 def _arith(h) -> int:
     """The arithmetic form (ops._native.ARITH code) a native solver runs: "auto" resolved."""
     v = C.c_int32()
@@ -163,6 +191,20 @@ class HeatSolver:
             when r is a power of two, else exact — never jacobi); the depth is
             clamped to the source kernels' deepest pass (info()["source"]).
             :meth:`set_source` replaces or clears it between steps.
+        rmap: a diffusivity map, u_t = nu(x, y) lap(u) (the NON-divergence
+            form: variable heat capacity over constant conductivity; not
+            div(k grad u)): the GLOBAL frame-inclusive array (rows + 2) x
+            (n + 2) of the per-point diffusion number R = nu(x, y) dt / dx^2
+            (:func:`rmap_from_nu`; the solver does no scaling; converted to the
+            field's dtype; frame entries are ignored; owned entries finite and
+            >= 0). One step is T' = C + R[i,j] * (sum - 4C) in the reference's
+            operand order ("fma": fma(R, fma(-4, C, sum), C)), bitwise equal to
+            models.reference.ftcs(rmap=) at any depth, plan and rank count;
+            R == 0 holds a point at its value. Each rank slices its own rows.
+            Dirichlet axes, engine "tb", no copy_swap, no source, arith "exact"
+            / "fma" ("auto" is exact); the depth is clamped to the map kernels'
+            deepest pass (info()["rmap"]). :meth:`set_rmap` replaces it, or
+            returns to the scalar r, between steps.
     """
 
     def __init__(self, problem: Problem, *, dtype: str = "fp64", backend: str = "auto", tb: int = 0,
@@ -171,7 +213,7 @@ class HeatSolver:
                  device: Optional[int] = None, init: bool = True, rows: Optional[int] = None,
                  comm_cus: int = 0, autotune: int = -1, engine: str = "tb", arith: str = "auto",
                  slab_row0: Optional[int] = None, edge_shift: int = 0, bc_x: str = "dirichlet",
-                 bc_y: str = "dirichlet", source=None):
+                 bc_y: str = "dirichlet", source=None, rmap=None):
         self.problem = problem
         self.edge_shift = 0 if bc_x == "periodic" else int(edge_shift)  # (periodic x: no edge slabs)
         self.bc_x, self.bc_y = bc_x, bc_y
@@ -218,6 +260,10 @@ class HeatSolver:
         self.arith = arith
         cfg.source = int(source is not None)
         self.source_sha256 = None
+        cfg.rmap = int(rmap is not None)
+        self.rmap_sha256 = None
+        if rmap is not None and arith == "auto":
+            self.arith = "exact"  # (the native solver resolves it the same way)
         self._cfg = cfg
         h = C.c_void_p()
         N.call("heat2d_solver_create", C.byref(cfg), self.transport.handle, C.byref(h))
@@ -226,8 +272,24 @@ class HeatSolver:
         N.call("heat2d_solver_layout", self._h, C.byref(self.layout))
         if source is not None:
             self.set_source(source)
+        if rmap is not None:
+            self.set_rmap(rmap)
         if init:
             self.init()
+
+    def set_rmap(self, rmap) -> None:
+        """Replace the diffusivity map (the global frame-inclusive array, see
+        the class docstring) or drop it (None: the solver then runs the
+        scalar-r kernels), between step() calls. The solver must have been
+        created with a map; nothing but captured graphs is invalidated."""
+        if rmap is None:
+            N.call("heat2d_solver_set_rmap", self._h, None, 0)
+            self.rmap_sha256 = None
+            return
+        a = _rmap_array(rmap, int(self.layout.nrows_global), self.ncols, self.np_dtype)
+        N.call("heat2d_solver_set_rmap", self._h, a.ctypes.data_as(C.c_void_p), a.shape[1])
+        # what a checkpoint records of the map (utils/checkpoint.py): the digest of the converted array
+        self.rmap_sha256 = hashlib.sha256(a.tobytes()).hexdigest()
 
     def set_source(self, source) -> None:
         """Replace the heat source (the global frame-inclusive array, see the
@@ -274,6 +336,7 @@ class HeatSolver:
                 "arith": _arith(self._h),  # the resolved code: 0 exact, 1 fma, 2 jacobi, 3 fast
                 "bc_x": self._bc()[0], "bc_y": self._bc()[1],  # "dirichlet" | "periodic" | "insulated", as the native solver runs
                 "source": _source_info(self._h),
+                "rmap": _rmap_info(self._h),
                 "rank": self.rank, "size": self.size, "layout": self.layout.as_dict()}
 
     def _bc(self) -> tuple:
@@ -511,7 +574,7 @@ class LoopbackGroup:
     def __init__(self, problem: Problem, nranks: int, *, dtype: str = "fp64", backend: str = "auto",
                  tb: int = 0, tile_rows: int = 0, device: Optional[int] = None, arith: str = "auto",
                  overlap: bool = True, autotune: int = -1, comm_cus: int = 0, edge_shift: int = 0,
-                 bc_x: str = "dirichlet", bc_y: str = "dirichlet", source=None):
+                 bc_x: str = "dirichlet", bc_y: str = "dirichlet", source=None, rmap=None):
         self.problem = problem
         self.bc_x, self.bc_y = bc_x, bc_y
         self.backend = resolve_backend(backend)
@@ -536,12 +599,15 @@ class LoopbackGroup:
         cfg.bc_x = N.bc_code(bc_x, "bc_x")
         cfg.bc_y = N.bc_code(bc_y, "bc_y")
         cfg.source = int(source is not None)  # a heat source (HeatSolver source=): each member slices its rows
+        cfg.rmap = int(rmap is not None)  # a diffusivity map (HeatSolver rmap=): likewise
         self.nranks = nranks
         h = C.c_void_p()
         N.call("heat2d_group_create", C.byref(cfg), nranks, C.byref(h))
         self._h = h
         if source is not None:
             self.set_source(source)
+        if rmap is not None:
+            self.set_rmap(rmap)
         x = np.ascontiguousarray(problem.x, dtype=np.float64)
         ic = problem.ic.to_native()
         N.call("heat2d_group_init", self._h, C.byref(ic), x.ctypes.data_as(C.c_void_p),
@@ -559,6 +625,16 @@ class LoopbackGroup:
         m = self.problem.n_owned
         a = _source_array(source, m, m, NP_DTYPES[self.dtype])
         N.call("heat2d_group_set_source", self._h, a.ctypes.data_as(C.c_void_p), m + 2)
+
+    def set_rmap(self, rmap) -> None:
+        """Replace (the global frame-inclusive array) or drop (None) the
+        diffusivity map of every member, between step() calls (HeatSolver.set_rmap)."""
+        if rmap is None:
+            N.call("heat2d_group_set_rmap", self._h, None, 0)
+            return
+        m = self.problem.n_owned
+        a = _rmap_array(rmap, m, m, NP_DTYPES[self.dtype])
+        N.call("heat2d_group_set_rmap", self._h, a.ctypes.data_as(C.c_void_p), m + 2)
 
     def upload(self, arr: np.ndarray) -> None:
         """Whole owned grid -> the members' slabs, then a loopback halo exchange."""

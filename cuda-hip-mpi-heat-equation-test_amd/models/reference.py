@@ -142,8 +142,32 @@ def _ftcs_step_source(T: np.ndarray, r, arith: str, source: np.ndarray) -> np.nd
     return out
 
 
+def _ftcs_step_rmap(T: np.ndarray, arith: str, rmap: np.ndarray) -> np.ndarray:
+    """One step with a diffusivity map (u_t = nu(x, y) lap(u), the
+    non-divergence form): the scalar r of :func:`ftcs_step` replaced by the
+    map's element at every owned point, in the reference's operand order,
+        exact: T' = C + R[i,j] * ((((S_+E)+N)+W) - 4C)
+        fma:   T' = fma(R[i,j], fma(-4, C, sum), C)      (:func:`fma`: one rounding each)
+    The frame stays pinned and the frame entries of ``rmap`` are ignored;
+    R[i,j] == 0 holds the point at its value."""
+    if arith not in ("exact", "fma"):
+        raise ValueError("a diffusivity map needs arith 'exact' or 'fma' (jacobi assumes r == 1/4 everywhere)")
+    if rmap.shape != T.shape:
+        raise ValueError(f"rmap must be frame-inclusive like the field, {T.shape}, got {rmap.shape}")
+    R = np.ascontiguousarray(rmap, dtype=T.dtype)[1:-1, 1:-1]
+    four = T.dtype.type(4)
+    c = T[1:-1, 1:-1]
+    total = ((T[2:, 1:-1] + T[1:-1, 2:]) + T[:-2, 1:-1]) + T[1:-1, :-2]
+    out = T.copy()
+    if arith == "fma":
+        out[1:-1, 1:-1] = fma(R, fma(np.broadcast_to(-four, c.shape), c, total), c)
+    else:
+        out[1:-1, 1:-1] = c + R * (total - four * c)
+    return out
+
+
 def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
-              source: np.ndarray | None = None) -> np.ndarray:
+              source: np.ndarray | None = None, rmap: np.ndarray | None = None) -> np.ndarray:
     """One FTCS step of a frame-inclusive field. On a Dirichlet axis the frame
     is kept fixed; on a periodic or insulated one it is refreshed from the
     owned points before the step (:func:`wrap_frame`) — the update and its
@@ -160,6 +184,14 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
     bits only where r is a power of two). So at such an r as 0.2,
     ``ftcs(arith="fma", source=None)`` and ``ftcs(arith="fma", source=<all -0.0>)``
     differ, while with "exact" they are bitwise equal."""
+    if rmap is not None:
+        # rmap (frame-inclusive, the per-point diffusion number; Dirichlet axes, arith "exact" or
+        # "fma", no source): replaces r (:func:`_ftcs_step_rmap`). None: today's function.
+        if bc_x != "dirichlet" or bc_y != "dirichlet":
+            raise ValueError("a diffusivity map needs Dirichlet boundaries on both axes")
+        if source is not None:
+            raise ValueError("a diffusivity map and a heat source together are not offered")
+        return _ftcs_step_rmap(T, arith, rmap)
     if source is not None:
         if bc_x != "dirichlet" or bc_y != "dirichlet":
             raise ValueError("a heat source needs Dirichlet boundaries on both axes")
@@ -184,12 +216,17 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
 
 def ftcs(problem: Problem, nsteps: int | None = None, dtype=np.float64, T0: np.ndarray | None = None,
          arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
-         source: np.ndarray | None = None) -> np.ndarray:
+         source: np.ndarray | None = None, rmap: np.ndarray | None = None) -> np.ndarray:
     """Run FTCS; returns the frame-inclusive field (frame entries on periodic
     / insulated axes: wrap / edge images of the returned owned points).
-    source: a heat source added at every step (:func:`ftcs_step`)."""
+    source: a heat source added at every step (:func:`ftcs_step`).
+    rmap: a diffusivity map in place of problem.r (:func:`ftcs_step`)."""
     T = initial_field(problem, dtype) if T0 is None else T0.astype(dtype)
     n = problem.ntime if nsteps is None else nsteps
+    if rmap is not None:
+        for _ in range(n):
+            T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source, rmap)
+        return T
     if source is not None:
         for _ in range(n):
             T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source)

@@ -99,7 +99,8 @@ class Config(C.Structure):
         ("engine", C.c_int32), ("arith", C.c_int32),
         ("edge_shift", C.c_int32), ("slab_row0", C.c_int64), ("slab_rows_global", C.c_int64),
         ("bc_x", C.c_int32), ("bc_y", C.c_int32),
-        ("source", C.c_int32), ("pad0", C.c_int32),  # source = 1: the solver carries a heat source
+        ("source", C.c_int32),  # 1: the solver carries a heat source
+        ("rmap", C.c_int32),  # 1: the solver carries a diffusivity map
     ]
 
 
@@ -200,10 +201,16 @@ _SIGS = {
     "heat2d_solver_source": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "heat2d_tb_src": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, _P, _I64, C.c_int, _P]),
     "heat2d_cpu_tb_src": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, C.c_int, _P]),
+    "heat2d_solver_set_rmap": (C.c_int, [_P, _P, _I64]),
+    "heat2d_group_set_rmap": (C.c_int, [_P, _P, _I64]),
+    "heat2d_solver_rmap": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "heat2d_tb_var": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, _P, _I64, C.c_int, _P]),
+    "heat2d_cpu_tb_var": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_int, _P]),
     "heat2d_solver_compare": (C.c_int, [_P, _P, _I64, _I64, _I64, _P]),
     "heat2d_solver_footprint": (C.c_int, [C.POINTER(Config), C.c_int, C.c_int, C.POINTER(_I64)]),
     "heat2d_plan_max_grid": (C.c_int, [C.c_int, C.c_int, _I64, C.POINTER(_I64)]),
     "heat2d_plan_max_grid_src": (C.c_int, [C.c_int, C.c_int, _I64, C.c_int, C.POINTER(_I64)]),
+    "heat2d_plan_max_grid_ext": (C.c_int, [C.c_int, C.c_int, _I64, C.c_int, C.c_int, C.POINTER(_I64)]),
     "heat2d_mem_info": (C.c_int, [C.c_int, C.POINTER(_I64), C.POINTER(_I64)]),
     "heat2d_solver_upload": (C.c_int, [_P, _P, _I64]),
     "heat2d_solver_layout": (C.c_int, [_P, _LP]),

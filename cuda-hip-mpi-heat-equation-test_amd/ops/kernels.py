@@ -86,7 +86,8 @@ def init_field(field: torch.Tensor, layout: N.Layout, ic, xcoord: np.ndarray,
 
 def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: float,
             rows: Optional[tuple[int, int]] = None, tile_rows: int = 0, arith: str = "exact",
-            bc_x: str = "dirichlet", bc_y: str = "dirichlet", source: Optional[torch.Tensor] = None) -> None:
+            bc_x: str = "dirichlet", bc_y: str = "dirichlet", source: Optional[torch.Tensor] = None,
+            rmap: Optional[torch.Tensor] = None) -> None:
     """dst[rows] = k FTCS steps of src (temporal-blocked kernel). The k ghost rows
     around ``rows`` must be valid in ``src``; Dirichlet rows/cols are kept.
     ``arith``: "exact" (reference rounding), "fma" (contracted update) or
@@ -104,9 +105,26 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
     that pinned points keep their bits: :func:`source_field`), added at every
     fused level as an operation of its own; Dirichlet axes, arith "exact" /
     "fma" / "auto"; on the device k is at most the source kernels' deepest pass
-    (common.hpp ``kMaxTBSrc``, reported as ``HeatSolver.info()["source"]["max_tb"]``)."""
+    (common.hpp ``kMaxTBSrc``, reported as ``HeatSolver.info()["source"]["max_tb"]``).
+    ``rmap``: a diffusivity map in the field's layout, dtype and device (the
+    per-point diffusion number, with +0.0 in every frame row / column, pad
+    entry and row outside the grid — the pinning: :func:`rmap_field`), the
+    multiplier of every point's update at every fused level; ``r`` is then not
+    used. Dirichlet axes, arith "exact" / "fma" ("auto" is exact), no
+    ``source``; on the device k is at most ``kMaxTBVar``
+    (``HeatSolver.info()["rmap"]["max_tb"]``)."""
     _check_field(src, layout)
     _check_field(dst, layout)
+    if rmap is not None:
+        _check_field(rmap, layout)
+        if rmap.dtype != src.dtype or rmap.device != src.device:
+            raise ValueError("rmap dtype/device mismatch")
+        if source is not None:
+            raise ValueError("a diffusivity map and a heat source together: no kernel carries both")
+        if bc_x != "dirichlet" or bc_y != "dirichlet":
+            raise ValueError("a diffusivity map needs Dirichlet boundaries on both axes")
+        if arith not in ("exact", "fma", "auto"):
+            raise ValueError("a diffusivity map needs arith 'exact', 'fma' or 'auto'")
     if source is not None:
         _check_field(source, layout)
         if source.dtype != src.dtype or source.device != src.device:
@@ -122,6 +140,15 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
     rb, re = (0, layout.nrows) if rows is None else rows
     ar = N.arith_code(arith, r)
     bc = N.bc_bits(bc_x, bc_y)
+    if rmap is not None:
+        ar = N.ARITH["fma"] if arith == "fma" else N.ARITH["exact"]
+        if src.is_cuda:
+            N.call("heat2d_tb_var", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                   C.byref(layout), rb, re, k, _stream(src), tile_rows, ar, C.c_void_p(rmap.data_ptr()))
+        else:
+            N.call("heat2d_cpu_tb_var", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                   C.byref(layout), rb, re, k, ar, C.c_void_p(rmap.data_ptr()))
+        return
     if source is not None:
         if src.is_cuda:
             N.call("heat2d_tb_src", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
@@ -151,6 +178,22 @@ def source_field(S: np.ndarray, layout: N.Layout, dtype: torch.dtype, device="cp
         g = layout.row0 + i
         if 0 <= g < layout.nrows_global:
             f[i + layout.halo, layout.cpad:layout.cpad + layout.ncols] = Sd[g + 1, 1:-1]
+    return f.reshape(-1).to(device)
+
+
+def rmap_field(R: np.ndarray, layout: N.Layout, dtype: torch.dtype, device="cpu") -> torch.Tensor:
+    """The diffusivity-map buffer :func:`tb_step` takes, from the GLOBAL
+    frame-inclusive array ``R`` ((nrows_global + 2) x (ncols + 2)): +0.0
+    everywhere, then the owned points of every allocated row of the slab that
+    is an owned row of the grid (ghost rows included)."""
+    if R.shape != (layout.nrows_global + 2, layout.ncols + 2):
+        raise ValueError(f"rmap must be {(layout.nrows_global + 2, layout.ncols + 2)}, got {R.shape}")
+    f = torch.zeros((layout.rows_alloc(), layout.pitch), dtype=dtype)
+    Rd = torch.as_tensor(np.ascontiguousarray(R)).to(dtype)
+    for i in range(-layout.halo, layout.nrows + layout.halo):
+        g = layout.row0 + i
+        if 0 <= g < layout.nrows_global:
+            f[i + layout.halo, layout.cpad:layout.cpad + layout.ncols] = Rd[g + 1, 1:-1]
     return f.reshape(-1).to(device)
 
 

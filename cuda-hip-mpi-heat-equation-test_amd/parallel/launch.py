@@ -64,6 +64,12 @@ def build_parser():
                          "increment dt * f (converted to the run's dtype; a wrong shape fails), added at every step "
                          "as an operation of its own. Dirichlet axes, engine tb, arith exact / fma (auto picks one of "
                          "them). Checkpoints record its SHA-256; a restart needs the same file again")
+    ap.add_argument("--rmap", default=None, metavar="FILE.npy",
+                    help="diffusivity map u_t = nu(x, y) lap(u) (non-divergence form): the frame-inclusive (n+2) x (n+2) "
+                         "array of the per-point diffusion number nu(x, y) dt / dx^2 (converted to the run's dtype; a "
+                         "wrong shape fails), used in place of r at every point; 0 holds a point. Dirichlet axes, engine "
+                         "tb, arith exact / fma (auto is exact), not with --source. Checkpoints record its SHA-256; a "
+                         "restart needs the same file again")
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--ntime", type=int, default=None)
     ap.add_argument("--print-every", type=int, default=0)
@@ -234,6 +240,18 @@ def run(argv=None) -> int:
         m = prob.n_owned + 2
         if source.shape != (m, m):
             raise SystemExit(f"heat2d: --source {a.source}: shape {source.shape}, the frame-inclusive grid is {(m, m)}")
+    rmap = None
+    if a.rmap:
+        import numpy as np
+        rmap = np.load(a.rmap, allow_pickle=False)
+        m = prob.n_owned + 2
+        if rmap.shape != (m, m):
+            raise SystemExit(f"heat2d: --rmap {a.rmap}: shape {rmap.shape}, the frame-inclusive grid is {(m, m)}")
+        rmax = float(rmap[1:-1, 1:-1].max())
+        if rmax > 0.25 + 1e-12 and root:
+            print(f"warning: max r = {rmax:.6g} > 0.25: FTCS is unstable in 2-D", file=sys.stderr)
+        if arith == "auto":
+            arith = "exact"  # (as the solver and the CLI resolve it with a map)
     # (with a source auto stays with the solver: fma when r is a power of two, else exact — never jacobi)
     if arith == "auto" and prob.r == 0.25 and prob.ic.sterbenz_safe() and not a.restart and engine == "tb" \
             and source is None:
@@ -271,7 +289,7 @@ def run(argv=None) -> int:
     if a.edge_shift not in ("auto", "measure"):
         edge_shift = int(a.edge_shift)
     elif world >= 3 and (backend == "hip" or a.edge_shift == "measure") and engine == "tb" and \
-            bc["bc_x"] != "periodic" and source is None:  # (periodic x: no edge slabs; the probe slabs carry no source)
+            bc["bc_x"] != "periodic" and source is None and rmap is None:  # (periodic x: no edge slabs; the probe slabs carry no source / map)
         edge_shift = _measure_edge_shift(prob, a, rank, world, local, backend, kinds[0], engine, arith,
                                          min(nsteps, 48), root and not a.quiet)
 
@@ -279,7 +297,7 @@ def run(argv=None) -> int:
         return HeatSolver(prob, dtype=a.dtype, backend=backend, tb=a.tb, overlap=not a.no_overlap,
                           copy_swap=a.copy_swap, managed=a.managed or var.managed, graph=a.graph, transport=tr,
                           device=local if backend == "hip" else None, engine=engine, arith=arith,
-                          edge_shift=edge_shift, source=source, **bc)
+                          edge_shift=edge_shift, source=source, rmap=rmap, **bc)
 
     tr, s, kind, fallback = _make_solver(kinds, make_transport, make_solver, world)
     if fallback and root and not a.quiet:

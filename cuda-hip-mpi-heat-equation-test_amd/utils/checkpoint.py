@@ -120,6 +120,10 @@ def save(solver, directory: str, step: Optional[int] = None, extra: Optional[dic
             # a restart must be given the same one again (load() compares the digests)
             "source_sha256": getattr(solver, "source_sha256", None),
         }
+        # the diffusivity map of the run, recorded the same way (HeatSolver.rmap_sha256); the key
+        # only when there is one, so saves without a map keep their key set
+        if getattr(solver, "rmap_sha256", None) is not None:
+            meta["rmap_sha256"] = solver.rmap_sha256
         meta.update(extra or {})
         _write_atomic(os.path.join(sd, "meta.json"), json.dumps(meta, indent=1))
         _write_atomic(os.path.join(directory, "latest"), os.path.basename(sd) + "\n")  # the commit point
@@ -166,6 +170,14 @@ def load(solver, directory: str) -> dict:
             raise ValueError("the checkpoint was written with a heat source: give the restart the same source "
                              f"(sha256 {saved})")
         raise ValueError(f"the restart's heat source differs from the checkpoint's (sha256 {have} != {saved})")
+    have, saved = getattr(solver, "rmap_sha256", None), meta.get("rmap_sha256")  # (absent: none)
+    if saved != have:
+        if saved is None:
+            raise ValueError("the checkpoint was written without a diffusivity map, this run has one")
+        if have is None:
+            raise ValueError("the checkpoint was written with a diffusivity map: give the restart the same rmap "
+                             f"(sha256 {saved})")
+        raise ValueError(f"the restart's diffusivity map differs from the checkpoint's (sha256 {have} != {saved})")
     want = "fp64" if solver.np_dtype == np.float64 else "fp32"
     if meta["dtype"] != want:
         raise ValueError(f"checkpoint dtype {meta['dtype']} != solver dtype {want}")
