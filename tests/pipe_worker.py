@@ -30,7 +30,8 @@ def kind0_strips(n, k):
 
 
 def cases():
-    """name -> dict(n, tb, steps, ic, arith, env, kind). Grids are square: the
+    """name -> dict(n, tb, steps, ic, arith, env, kind; calls: the step() calls
+    that make up `steps`, default one). Grids are square: the
     column cases set n around the wide strip's useful width U(tb), the row
     cases take the thinnest slab the split accepts (6 tb rows: an interior of
     4 tb) and cut it into bands of 2 tb rows (5 FIFO depths)."""
@@ -72,6 +73,16 @@ def cases():
     for arith, k in (("exact", 21), ("fma", 20), ("fast", 19)):
         c[f"arith_{arith}_r02"] = dict(n=2 * useful(k) + 37, tb=k, steps=k + 3, ic="rough", arith=arith, sigma=0.2,
                                        kind0=True)
+    # every instance once (depths 16..24 x 4 forms): the cols_2u_partial shape of its depth (three
+    # strips, the middle one of kind 0), 2 k + 3 steps: two full passes and a shallower one, as
+    # three step() calls (`calls`: one step(2 k + 3) runs balanced cycles of depth ~2 k / 3, never
+    # one of depth k). exact and fma at sigma 0.2; fast at r = 1/4 (bitwise the jacobi form) at
+    # even depths, at sigma 0.2 (within its bound) at odd ones
+    for k in range(16, 25):
+        for arith in ("exact", "fma", "jacobi", "fast"):
+            sigma = 0.25 if arith == "jacobi" or (arith == "fast" and k % 2 == 0) else 0.2
+            c[f"inst_{arith}_{k}"] = dict(n=2 * useful(k) + 37, tb=k, steps=2 * k + 3, calls=[k, k, 3], ic="rough",
+                                          arith=arith, sigma=sigma, kind0=True)
     # other paths: graph replay, loopback exchange between two slabs
     c["graph"] = dict(n=u20 + 1, tb=16, steps=3 * 16, ic="rough", kind="graph")
     c["loopback"] = dict(n=2 * useful(16) + 37, tb=16, steps=2 * 16 + 3, ic="rough", kind="loopback")
@@ -119,12 +130,15 @@ def main(outdir):
                            graph=(kind == "graph"))
             if a["ic"] == "rough":
                 s.upload(rough(a["n"]))
-            s.step(p.ntime)
+            for m in a.get("calls", [p.ntime]):
+                s.step(m)
             out, plan = s.download(), s.plan(a["tb"])
+            depths = sorted(s.cycle_hist())
             s.close()
         np.save(os.path.join(outdir, name + ".npy"), out)
         info[name] = {k: plan.get(k) for k in ("pipe", "valid", "dynamic", "main_bands", "main_items", "main_waves",
                                                 "main_rect", "main_strip_w", "main_useful_w")}
+        info[name]["depths"] = None if kind == "loopback" else depths  # the cycle depths that ran
         print(name, info[name], flush=True)
     with open(os.path.join(outdir, "info.json"), "w") as f:
         json.dump(info, f)

@@ -85,8 +85,10 @@ def test_bad_arith(native):
 @pytest.mark.parametrize("dtype", ["fp64", "fp32"])
 @pytest.mark.parametrize("tb", [1, 4, 12, 16])
 def test_hip_fma_matches_cpu_twin(gpu, native, dtype, tb):
-    """Any r: gfx950 kernel (fma form, every edge kind) == CPU twin, bitwise."""
-    p = prob(301, 29, "ghost", "uniform", sigma=0.2)
+    """Any r: gfx950 kernel (fma form, every edge kind) == CPU twin, bitwise.
+    (fp32 at n = 517: its 256-column strips have none clear of both frame
+    columns below n = 500, tests/instance_matrix.py.)"""
+    p = prob(301 if dtype == "fp64" else 517, 29, "ghost", "uniform", sigma=0.2)
     npdt = np.float64 if dtype == "fp64" else np.float32
     T0 = random_field(p, npdt)
     gpu_out = run(p, "hip", dtype, tb, "fma", upload=T0)

@@ -240,8 +240,10 @@ EDGE_CASES = ([("fp64", tb, 0.2) for tb in (1, 4, 12, 16, 17, 20, 24)] +
 @pytest.mark.parametrize("dtype,tb,sigma", EDGE_CASES)
 def test_hip_exact_every_edge_kind(gpu, native, dtype, tb, sigma):
     """Every edge kind (frame rows, frame columns, corners, interior) of the
-    general kernel on a small odd grid, rough data, every depth class."""
-    c = case(301, sigma, dtype, 2 * tb + 3).powered()
+    general kernel on a small odd grid, rough data, every depth class. (fp32
+    at n = 517: its 256-column strips have none clear of both frame columns
+    below n = 500, tests/instance_matrix.py.)"""
+    c = case(301 if dtype == "fp64" else 517, sigma, dtype, 2 * tb + 3).powered()
     got = run(c.p, "hip", dtype, tb, upload=c.T0)
     assert np.array_equal(got, c.gold), np.abs(got.astype(np.float64) - c.gold).max()
 

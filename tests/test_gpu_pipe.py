@@ -18,7 +18,14 @@ rounding at sigma 0.2 (models.reference.fast_error_bound), where its bits
 depend on which strips are interior ones, so the two runs are not compared.
 The cases marked kind0 assert from the geometry that a strip clear of both
 frame columns exists: only such strips carry scaled levels through the FIFO
-and unscale once at the store."""
+and unscale once at the store.
+
+The inst_<form>_<K> cases run every pair instance once (depths 16..24 x 4
+forms; tests/test_instance_matrix.py holds the table against the built code
+objects). They make their 2 K + 3 steps as step(K), step(K), step(3) and
+assert from cycle_hist() that cycles of depth K ran: one step(n) call runs
+balanced cycles, ceil(n / K) of them, so step(2 K + 3) alone never reaches
+depth K."""
 import json
 import os
 import subprocess
@@ -88,6 +95,9 @@ def test_pipe_bitwise(runs, name):
     # (the library's strip shape against this file's own formula)
     assert pl_on["main_strip_w"] == 256 and pl_on["main_useful_w"] == W.useful(a["tb"])
     assert pl_on["main_rect"][3] == -(-a["n"] // W.useful(a["tb"]))  # wide strips cover the columns
+    if "calls" in a:  # the every-instance cases: cycles of depth tb really ran (two, and a 3-step one)
+        assert sum(a["calls"]) == a["steps"]
+        assert pl_on["depths"] == [3, a["tb"]] and pl_off["depths"] == [3, a["tb"]], (pl_on, pl_off)
     if a.get("kind0"):
         assert W.kind0_strips(a["n"], a["tb"]), "no strip clear of the frame columns: the scaled path would not run"
     ref = golden(a)

@@ -12,6 +12,8 @@ Oracles:
     (Sterbenz: the reference IC, values in [1, 2]) — the bench configuration.
 GPU cases cover every edge kind, the split schedule + autotuner, the fused
 statistics, the hipRTC engine and multi-rank slabs."""
+import dataclasses
+
 import numpy as np
 import pytest
 
@@ -94,8 +96,10 @@ def test_jacobi_needs_quarter_r(native):
 def test_hip_jacobi_equals_golden(gpu, native, dtype, tb):
     """Every edge kind (frame rows, frame columns, corners, interior) on a small
     odd grid, rough data: the scaled interior and the unscaled pinned kinds
-    give the golden bits."""
-    p = prob(301, 2 * tb + 3)
+    give the golden bits. (fp32 at n = 517: its 256-column strips have none
+    clear of both frame columns below n = 500, tests/instance_matrix.py.)"""
+    p = prob(301 if dtype == "fp64" else 517, 2 * tb + 3)
+    p = dataclasses.replace(p, r=0.25)  # (n = 517: r = nu dt / delta^2 is 1/4 only up to rounding)
     npdt = np.float64 if dtype == "fp64" else np.float32
     T0 = rough(p, npdt)
     got = run(p, "hip", dtype, tb, upload=T0)
