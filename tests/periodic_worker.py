@@ -5,8 +5,10 @@ rank of a periodic run on the CPU twin over torch.distributed (gloo, the
 callback transport); rank 0 gathers the field into OUTDIR/result.npy.
 
 `python tests/periodic_worker.py single OUTDIR JSON_ARGS`: a one-rank run on
-the GPU in a fresh process (HEAT2D_SPLIT_ORDER is read once per process);
-writes OUTDIR/result.npy and OUTDIR/info.json.
+the GPU in a fresh process (HEAT2D_SPLIT_ORDER and HEAT2D_PIPE are read once
+per process); writes OUTDIR/result.npy and OUTDIR/info.json (the plan of depth
+tb, cycle_hist() and the plan of every depth that ran). JSON_ARGS may hold
+"calls", the step() calls that make up the steps, and may be a list of runs.
 """
 import json
 import os
@@ -56,21 +58,39 @@ def gloo(argv):
 
 def single(argv):
     outdir, a = argv[0], json.loads(argv[1])
-    import numpy as np
     import torch
+    torch.cuda.set_device(0)
+    if isinstance(a, list):  # several runs in this one process: result_<i>.npy, info.json a list
+        infos = [single_run(outdir, x, f"result_{i}.npy") for i, x in enumerate(a)]
+    else:
+        infos = single_run(outdir, a, "result.npy")
+    with open(os.path.join(outdir, "info.json"), "w") as f:
+        json.dump(infos, f)
+
+
+def single_run(outdir, a, result):
+    """One run: the steps as one step(steps) call, or as the step() calls of
+    a["calls"] (tests/cycles.py calls(): cycles of depth tb). Returns the plan
+    of depth tb, cycle_hist() and the plan of every depth that ran."""
+    import numpy as np
 
     from heat2d.models.heat2d import HeatSolver
-    torch.cuda.set_device(0)
     p = problem(a["n"], a["steps"])
     s = HeatSolver(p, dtype=a["dtype"], backend="hip", tb=a["tb"], arith="exact", device=0, bc_x=a["bc_x"],
                    bc_y=a["bc_y"])
     s.upload(rough_field(a["n"], a["dtype"]))
-    s.prepare(a["steps"])
-    s.step(a["steps"])
-    np.save(os.path.join(outdir, "result.npy"), s.download())
-    with open(os.path.join(outdir, "info.json"), "w") as f:
-        json.dump({"plan": s.plan(a["tb"]), "transport": s.info()["transport"]}, f)
+    sizes = a.get("calls", [a["steps"]])
+    assert sum(sizes) == a["steps"]
+    for m in sizes:
+        s.prepare(m)
+        s.step(m)
+    np.save(os.path.join(outdir, result), s.download())
+    hist = s.cycle_hist()
+    info = {"plan": s.plan(a["tb"]), "transport": s.info()["transport"], "cycle_hist": {str(k): v for k, v in hist.items()},
+            "plans": {str(k): s.plan(k) for k in sorted(hist)}}
     s.close()
+    print(a, "cycle_hist", hist, flush=True)
+    return info
 
 
 if __name__ == "__main__":

@@ -49,11 +49,15 @@ def main(argv):
     s = HeatSolver(p, dtype=a["dtype"], backend="hip", tb=a["tb"], arith=a["arith"], device=0, rows=rows,
                    source=rough_source(a["n"], a["dtype"], rows=rows))
     s.upload(rough_field(a["n"], a["dtype"], rows=rows))
-    s.prepare(a["steps"])
-    s.step(a["steps"])
+    sizes = a.get("calls", [a["steps"]])  # the step() calls that make up the steps (tests/cycles.py calls())
+    assert sum(sizes) == a["steps"]
+    for m in sizes:
+        s.prepare(m)
+        s.step(m)
     np.save(os.path.join(outdir, "result.npy"), s.download())
     with open(os.path.join(outdir, "info.json"), "w") as f:
-        json.dump({"plan": s.plan(a["tb"]), "info": {k: v for k, v in s.info().items() if k in ("tb", "arith", "source")}}, f)
+        json.dump({"plan": s.plan(a["tb"]), "info": {k: v for k, v in s.info().items() if k in ("tb", "arith", "source")},
+                   "cycle_hist": {str(k): v for k, v in s.cycle_hist().items()}}, f)
     s.close()
 
 

@@ -7,12 +7,18 @@ reference line. Oracles:
   * any r: the CPU twin (std::fma) and the gfx950 kernels agree bitwise, the
     decomposition is bitwise invariant, and the result stays within rounding of
     the NumPy golden (and actually differs from it, i.e. the fma path ran)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 import heat2d
 from heat2d.models import reference as R
 from heat2d.models.heat2d import HeatSolver, LoopbackGroup
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cycles as Y  # noqa: E402
 
 
 def prob(n, steps, conv="ghost", ic="uniform", dom=1.0, sigma=0.25):
@@ -23,13 +29,19 @@ def random_field(p, npdt, seed=0):
     return np.random.default_rng(seed).random((p.n_owned, p.n_owned)).astype(npdt)
 
 
-def run(p, backend, dtype, tb, arith, upload=None, **kw):
+def run(p, backend, dtype, tb, arith, upload=None, full=0, **kw):
+    """full > 0: the steps as tests/cycles.py calls(tb, steps, full) — `full`
+    cycles of depth tb, asserted from cycle_hist(), then the remainder — and
+    not as one step() call, whose balanced cycles are all shallower than tb."""
     s = HeatSolver(p, dtype=dtype, backend=backend, tb=tb, arith=arith, device=0 if backend == "hip" else None, **kw)
     if upload is not None:
         s.upload(upload)
-    s.step(p.ntime)
-    out = s.download()
+    for m in Y.calls(tb, p.ntime, full) if full else [p.ntime]:
+        s.step(m)
+    out, hist = s.download(), s.cycle_hist()
     s.close()
+    if full:
+        Y.assert_ran(hist, tb, full)
     return out
 
 
@@ -91,7 +103,7 @@ def test_hip_fma_matches_cpu_twin(gpu, native, dtype, tb):
     p = prob(301 if dtype == "fp64" else 517, 29, "ghost", "uniform", sigma=0.2)
     npdt = np.float64 if dtype == "fp64" else np.float32
     T0 = random_field(p, npdt)
-    gpu_out = run(p, "hip", dtype, tb, "fma", upload=T0)
+    gpu_out = run(p, "hip", dtype, tb, "fma", upload=T0, full=1)  # (tb 16: one step(29) call runs 15, 14)
     cpu_out = run(p, "cpu", dtype, tb, "fma", upload=T0)
     assert np.array_equal(gpu_out, cpu_out), np.abs(gpu_out.astype(np.float64) - cpu_out).max()
 
@@ -103,7 +115,7 @@ def test_hip_fma_split_schedule(gpu, native, dtype, tb, n):
     p = prob(n, 2 * tb + 3, "ghost", "uniform", sigma=0.2)
     npdt = np.float64 if dtype == "fp64" else np.float32
     T0 = random_field(p, npdt)
-    gpu_out = run(p, "hip", dtype, tb, "fma", upload=T0, autotune=1)
+    gpu_out = run(p, "hip", dtype, tb, "fma", upload=T0, autotune=1, full=2)
     cpu_out = run(p, "cpu", dtype, tb, "fma", upload=T0)
     assert np.array_equal(gpu_out, cpu_out)
 

@@ -12,6 +12,8 @@ sigmas (r), depths, both dtypes and both plan shapes (split + single launch).
 At r = 1/4 it is bitwise the r = 1/4 form ("jacobi"). The CPU twin runs the
 unscaled contracted form (arith 1) for it."""
 import dataclasses
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -19,6 +21,9 @@ import pytest
 import heat2d
 from heat2d.models import reference as R
 from heat2d.models.heat2d import HeatSolver
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cycles as Y  # noqa: E402
 
 
 def prob(n, steps, sigma):
@@ -36,13 +41,21 @@ def exact(p, npdt, T0, steps):
     return R.owned(R.ftcs(p, steps, dtype=npdt, T0=full, arith="exact"))
 
 
-def run(p, backend, dtype, tb, arith, T0, steps, **kw):
+def run(p, backend, dtype, tb, arith, T0, steps, full=0, **kw):
+    """full > 0: the steps as tests/cycles.py calls(tb, steps, full) — `full`
+    cycles of depth tb, asserted from cycle_hist(), then the remainder — and
+    not as one step() call, whose balanced cycles are all shallower than tb."""
     s = HeatSolver(p, dtype=dtype, backend=backend, tb=tb, arith=arith, device=0 if backend == "hip" else None, **kw)
     s.upload(T0)
-    s.step(steps)
-    out = s.download()
+    k = s.tb  # (the depth in use: fp32 clamps tb so that r^K stays in the exponent range, 20 -> 18 at sigma 0.1)
+    for m in Y.calls(k, steps, full) if full else [steps]:
+        s.step(m)
+    out, hist = s.download(), s.cycle_hist()
     info = s.info()
     s.close()
+    if full:
+        assert k == tb or (arith == "fast" and dtype == "fp32" and k < tb), (k, tb)
+        Y.assert_ran(hist, k, full)
     return out, info
 
 
@@ -85,14 +98,15 @@ def test_fast_depth_clamped_to_exponent_range(native):
 @pytest.mark.parametrize("sigma", [0.2, 0.1, 0.2371])
 @pytest.mark.parametrize("tb,steps", [(1, 5), (7, 31), (16, 49), (20, 61)])
 def test_hip_fast_within_bound(gpu, native, dtype, sigma, tb, steps):
-    """Split schedule (autotuned plans, measured schedule: every kernel kind,
-    scaled interior + unscaled pinned items) on 1100^2 rough data."""
+    """Split schedule (autotuned plans: every kernel kind, scaled interior +
+    unscaled pinned items) on 1100^2 rough data; a cycle of depth tb, then the
+    balanced remainder (one step(61) call at tb 20 runs 16, 15, 15, 15)."""
     if dtype == "fp32" and tb > 20:
         pytest.skip("fp32 depth")
     p = prob(1100, steps, sigma)
     npdt = np.float64 if dtype == "fp64" else np.float32
     T0 = rough(p, npdt) + npdt(0.5)
-    got, info = run(p, "hip", dtype, tb, "fast", T0, steps, autotune=1)
+    got, info = run(p, "hip", dtype, tb, "fast", T0, steps, autotune=1, full=1)
     ref = exact(p, npdt, T0, steps)
     d = np.abs(got.astype(np.float64) - ref.astype(np.float64)).max()
     bound = R.fast_error_bound(steps, npdt, float(T0.max()))
@@ -111,7 +125,7 @@ def test_hip_fast_single_launch_within_bound(gpu, native, monkeypatch, dtype, tb
     p = prob(1100, 2 * tb + 3, 0.2)
     npdt = np.float64 if dtype == "fp64" else np.float32
     T0 = rough(p, npdt)
-    got, _ = run(p, "hip", dtype, tb, "fast", T0, p.ntime, autotune=0)
+    got, _ = run(p, "hip", dtype, tb, "fast", T0, p.ntime, autotune=0, full=2)
     d = np.abs(got.astype(np.float64) - exact(p, npdt, T0, p.ntime).astype(np.float64)).max()
     assert d <= R.fast_error_bound(p.ntime, npdt, float(T0.max())), d
 

@@ -39,7 +39,9 @@ Two cases cannot meet the condition and are exempt, each for a stated reason:
     golden); the case still checks that ``auto`` resolves from the double r to
     form 0 and that the fp32 form-0 kernel gives the golden.
 """
+import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -48,6 +50,9 @@ import heat2d
 from heat2d.models import reference as R
 from heat2d.models.heat2d import HeatSolver, LoopbackGroup
 from heat2d.ops import _native as N
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cycles as Y  # noqa: E402
 
 POWER = 0.01
 SIGMAS = [0.1, 0.2, 0.2371, 0.3]
@@ -70,24 +75,36 @@ def golden(p, npdt, T0=None, arith="exact", steps=None):
     return R.owned(R.ftcs(p, steps, dtype=npdt, T0=full, arith=arith))
 
 
-def run(p, backend, dtype, tb, arith="exact", upload=None, steps=None, **kw):
+def run(p, backend, dtype, tb, arith="exact", upload=None, steps=None, full=0, **kw):
+    """full > 0: the steps as tests/cycles.py calls(tb, steps, full) — `full`
+    cycles of depth tb, asserted from cycle_hist(), then the remainder — and
+    not as one step() call, whose balanced cycles are all shallower than tb."""
     s = HeatSolver(p, dtype=dtype, backend=backend, tb=tb, arith=arith, device=0 if backend == "hip" else None, **kw)
     if upload is not None:
         s.upload(upload)
-    s.step(p.ntime if steps is None else steps)
-    out = s.download()
+    steps = p.ntime if steps is None else steps
+    for m in Y.calls(tb, steps, full) if full else [steps]:
+        s.step(m)
+    out, hist = s.download(), s.cycle_hist()
     s.close()
+    if full:
+        Y.assert_ran(hist, tb, full)
     return out
 
 
 def solve(c, dtype, tb, **kw):
-    """c's problem on the HIP engine in form 0 from c.T0: (field, plan of depth tb)."""
+    """c's problem on the HIP engine in form 0 from c.T0: (field, plan of depth
+    tb). Two cycles of depth tb ran that plan, asserted from cycle_hist():
+    step(tb), step(tb), the remainder — or, with graph=True, one call whose
+    pair branch replays the captured pair of depth tb."""
     s = HeatSolver(c.p, dtype=dtype, backend="hip", tb=tb, device=0, arith="exact", **kw)
     s.upload(c.T0)
-    s.step(c.p.ntime)
-    got = s.download()
+    for m in [c.p.ntime] if kw.get("graph") else Y.calls(tb, c.p.ntime, 2):
+        s.step(m)
+    got, hist = s.download(), s.cycle_hist()
     pl = s.plan(tb)
     s.close()
+    Y.assert_ran(hist, tb, 2)
     return got, pl
 
 
@@ -244,7 +261,7 @@ def test_hip_exact_every_edge_kind(gpu, native, dtype, tb, sigma):
     at n = 517: its 256-column strips have none clear of both frame columns
     below n = 500, tests/instance_matrix.py.)"""
     c = case(301 if dtype == "fp64" else 517, sigma, dtype, 2 * tb + 3).powered()
-    got = run(c.p, "hip", dtype, tb, upload=c.T0)
+    got = run(c.p, "hip", dtype, tb, upload=c.T0, full=2)  # step(tb), step(tb), step(3)
     assert np.array_equal(got, c.gold), np.abs(got.astype(np.float64) - c.gold).max()
 
 

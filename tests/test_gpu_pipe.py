@@ -22,10 +22,21 @@ and unscale once at the store.
 
 The inst_<form>_<K> cases run every pair instance once (depths 16..24 x 4
 forms; tests/test_instance_matrix.py holds the table against the built code
-objects). They make their 2 K + 3 steps as step(K), step(K), step(3) and
-assert from cycle_hist() that cycles of depth K ran: one step(n) call runs
+objects).
+
+Every case makes its steps with tests/cycles.py calls() — step(K), step(K),
+the remainder — and test_pipe_bitwise asserts from cycle_hist() that cycles
+of depth K ran (every member's, for the loopback cases): one step(n) call runs
 balanced cycles, ceil(n / K) of them, so step(2 K + 3) alone never reaches
-depth K."""
+depth K, and below depth 16 there is no pair kernel at all. Plan assertions
+are made on the plan of every depth the history shows, not on plan(K) alone.
+tests/test_cycles.py audits the table without a GPU.
+
+The loopback cases run the pair kernel beside a halo exchange: two edge slabs,
+three slabs (a middle one), and a depth-16 cycle followed by the exchange for
+a depth-17 one (the plan re-made over wider boundary bands). The
+test_pipe_boundary_conditions cases force it under periodic x, periodic y,
+both, and insulated x."""
 import json
 import os
 import subprocess
@@ -38,7 +49,9 @@ from heat2d.models import reference as R
 from heat2d.models.heat2d import HeatSolver
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cycles as Y  # noqa: E402
 import pipe_worker as W  # noqa: E402
+from test_cycles import RELAUNCH  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -83,21 +96,57 @@ def golden(a):
     return _golden[key]
 
 
+def ran_plans(a, info, relaunch):
+    """The plans of the cycles that ran, [(member, depth, plan)], after asserting
+    from every member's cycle_hist() that the case made its cycles: exactly
+    those of its calls, tb among them (twice where it names a relaunch)."""
+    want = Y.hist_of(Y.depths(a["tb"], a["calls"], graph=a.get("kind") == "graph"))
+    out = []
+    for i, m in enumerate(info["members"]):
+        hist = {int(k): v for k, v in m["hist"].items()}
+        Y.assert_ran(hist, a["tb"], 2 if relaunch else 1)
+        for k in a.get("also", []):
+            Y.assert_ran(hist, k)
+        assert hist == want, (i, hist, want)
+        assert sorted(int(k) for k in m["plans"]) == sorted(hist)
+        out += [(i, int(k), pl) for k, pl in m["plans"].items()]
+    return out
+
+
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_pipe_bitwise(runs, name):
     a = CASES[name]
     on = np.load(os.path.join(runs["1"][0], name + ".npy"))
     off = np.load(os.path.join(runs["0"][0], name + ".npy"))
     pl_on, pl_off = runs["1"][1][name], runs["0"][1][name]
-    # the plans that ran: the pair kernel on wide strips where forced, never with the knob off
+    print(name, "tb", a["tb"], "cycle_hist on", [m["hist"] for m in pl_on["members"]], "off",
+          [m["hist"] for m in pl_off["members"]])
+    assert len(pl_on["members"]) == len(pl_off["members"]) == a.get("ranks", 1)
+    # the plans that ran (every member's, of every depth in its history): the pair kernel on
+    # wide strips at every depth it exists at where forced, never with the knob off
+    for i, k, pl in ran_plans(a, pl_off, name in RELAUNCH):
+        assert pl["pipe"] == 0 and pl["main_strip_w"] == 128, (i, k, pl)
+    for i, k, pl in ran_plans(a, pl_on, name in RELAUNCH):
+        if k >= 16:
+            assert pl["pipe"] == 1 and pl["valid"] in (1, 3), (i, k, pl)
+            # (the library's strip shape against this file's own formula)
+            assert pl["main_strip_w"] == 256 and pl["main_useful_w"] == W.useful(k), (i, k, pl)
+            assert pl["main_rect"][3] == -(-a["n"] // W.useful(k)), (i, k, pl)  # wide strips cover the columns
+        else:  # (no pair instance below depth 16: the one-wave kernel)
+            assert pl["pipe"] == 0 and pl["main_strip_w"] == 128, (i, k, pl)
     assert pl_off["pipe"] == 0 and pl_off["main_strip_w"] == 128
     assert pl_on["pipe"] == 1 and pl_on["valid"] in (1, 3), pl_on
-    # (the library's strip shape against this file's own formula)
     assert pl_on["main_strip_w"] == 256 and pl_on["main_useful_w"] == W.useful(a["tb"])
-    assert pl_on["main_rect"][3] == -(-a["n"] // W.useful(a["tb"]))  # wide strips cover the columns
-    if "calls" in a:  # the every-instance cases: cycles of depth tb really ran (two, and a 3-step one)
-        assert sum(a["calls"]) == a["steps"]
-        assert pl_on["depths"] == [3, a["tb"]] and pl_off["depths"] == [3, a["tb"]], (pl_on, pl_off)
+    assert pl_on["main_rect"][3] == -(-a["n"] // W.useful(a["tb"]))
+    assert sum(a["calls"]) == a["steps"]
+    if name.startswith("inst_"):  # the every-instance cases: two cycles of depth tb and a 3-step one
+        for pl in (pl_on, pl_off):
+            assert pl["members"][0]["hist"] == {"3": 1, str(a["tb"]): 2}, pl["members"]
+    if a.get("kind") == "loopback":
+        # the slabs: every member's interior between its two boundary bands ran the pair kernel
+        # (asserted above from its own plans); three ranks have a middle slab
+        rows = [m["rows"] for m in pl_on["members"]]
+        assert sum(rows) == a["n"] and min(rows) - 2 * a["tb"] >= 4 * a["tb"], rows
     if a.get("kind0"):
         assert W.kind0_strips(a["n"], a["tb"]), "no strip clear of the frame columns: the scaled path would not run"
     ref = golden(a)
@@ -115,8 +164,14 @@ def test_pipe_bitwise(runs, name):
 
 def test_pipe_items_exceed_pairs(runs):
     """The several-items-per-pair cases really had more items than pairs, and
-    the dynamic ones really ran the queue."""
-    info = runs["1"][1]
+    the dynamic ones really ran the queue: read from the plan of the depth
+    that ran (twice: cycle_hist)."""
+    info = {}
+    for name in RELAUNCH:
+        m = runs["1"][1][name]["members"][0]
+        Y.assert_ran(m["hist"], CASES[name]["tb"], 2)
+        info[name] = m["plans"][str(CASES[name]["tb"])]
+        assert info[name]["pipe"] == 1, (name, info[name])
     for name in ("items_static", "items_dynamic", "segments_dynamic", "depth_24_items", "depth_21_segments",
                  "depth_19_items"):
         assert info[name]["main_items"] > info[name]["main_waves"], info[name]
@@ -124,6 +179,57 @@ def test_pipe_items_exceed_pairs(runs):
     assert info["depth_24_items"]["dynamic"] == 1
     assert info["items_static"]["dynamic"] == 0 and info["depth_19_items"]["dynamic"] == 0
     assert info["segments"]["main_bands"] < 0 and info["depth_21_segments"]["main_bands"] < 0  # segments
+
+
+# ---- the pair kernel under the other boundary conditions pipe_ok allows: periodic x (one rank: the
+# self-wrap exchange), periodic y (the march over the view widened by 24 ghost columns a side; tight
+# at depth 24) and both, at depths 24 and 16; insulated x with Dirichlet y at depth 20 (insulated y
+# is refused: tests/test_insulated.py test_hip_forced_pipe). No kernel family of their own, so no row
+# of the instance matrix. n = 2 U(K) + 37 (periodic x: rows per rank >= tb; periodic y: n >= 24),
+# 2 K + 3 steps as step(K), step(K), step(3); rough data, arith "exact" at r = 0.2371, bitwise
+# against models.reference.ftcs(bc_x=, bc_y=) and against the knob-off run.
+BC_WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "periodic_worker.py")
+BC_CASES = {f"{idx}_{k}": dict(n=2 * W.useful(k) + 37, steps=2 * k + 3, calls=Y.calls(k, 2 * k + 3, 2), tb=k, dtype="fp64",
+                               bc_x=bx, bc_y=by)
+            for idx, bx, by in (("px", "periodic", "dirichlet"), ("py", "dirichlet", "periodic"),
+                                ("pxy", "periodic", "periodic")) for k in (24, 16)}
+BC_CASES["ix_20"] = dict(n=2 * W.useful(20) + 37, steps=43, calls=Y.calls(20, 43, 2), tb=20, dtype="fp64", bc_x="insulated",
+                         bc_y="dirichlet")
+
+
+@pytest.fixture(scope="module")
+def bc_runs(gpu, native, tmp_path_factory):
+    """{knob value: (outdir, [info per BC_CASES entry])}: one worker per knob value."""
+    out = {}
+    for knob in ("1", "0"):
+        d = str(tmp_path_factory.mktemp("pipebc" + knob))
+        env = dict(os.environ, HEAT2D_PIPE=knob, HEAT2D_PLAN_CACHE="off")
+        r = subprocess.run([sys.executable, BC_WORKER, "single", d, json.dumps(list(BC_CASES.values()))], env=env,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (knob, r.stdout[-2000:], r.stderr[-4000:])
+        out[knob] = (d, json.load(open(os.path.join(d, "info.json"))))
+    return out
+
+
+@pytest.mark.parametrize("name", list(BC_CASES))
+def test_pipe_boundary_conditions(bc_runs, name):
+    from periodic_worker import problem, rough_field
+    a, i = BC_CASES[name], list(BC_CASES).index(name)
+    on, off = (np.load(os.path.join(bc_runs[knob][0], f"result_{i}.npy")) for knob in ("1", "0"))
+    inf_on, inf_off = bc_runs["1"][1][i], bc_runs["0"][1][i]
+    print(name, "tb", a["tb"], "cycle_hist on", inf_on["cycle_hist"], "off", inf_off["cycle_hist"])
+    for inf in (inf_on, inf_off):
+        assert {int(k): v for k, v in inf["cycle_hist"].items()} == Y.hist_of(Y.depths(a["tb"], a["calls"]))
+        Y.assert_ran(inf["cycle_hist"], a["tb"], 2)
+    # the plan of the depth that ran: the pair kernel on wide strips where forced
+    pl_on, pl_off = inf_on["plans"][str(a["tb"])], inf_off["plans"][str(a["tb"])]
+    assert pl_off["pipe"] == 0 and pl_off["main_strip_w"] == 128, pl_off
+    assert pl_on["pipe"] == 1 and pl_on["valid"] in (1, 3), pl_on
+    assert pl_on["main_strip_w"] == 256 and pl_on["main_useful_w"] == W.useful(a["tb"]), pl_on
+    ref = R.owned(R.ftcs(problem(a["n"], a["steps"]), a["steps"], dtype=np.float64, T0=rough_field(a["n"], "fp64"),
+                         arith="exact", bc_x=a["bc_x"], bc_y=a["bc_y"]))
+    assert np.array_equal(on, off), np.abs(on - off).max()
+    assert np.array_equal(on, ref), np.abs(on - ref).max()
 
 
 def test_kind0_cases_cover_the_scaled_path():

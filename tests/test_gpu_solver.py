@@ -6,12 +6,18 @@ contracted kernels (same bits as the reference rounding at a power-of-two r).
 The one exception, n = 777 (r = 0.25 - 2^-55), runs on smooth sine data, on
 which the two forms cannot be told apart; the unfused form at r != 1/4 on
 rough data is covered in tests/test_exact_general_r.py."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 import heat2d
 from heat2d.models import reference as R
 from heat2d.models.heat2d import HeatSolver, LoopbackGroup
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cycles as Y  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -67,9 +73,12 @@ def test_hip_split_schedule_bitwise(gpu, native, dtype, tb, n):
     for overlap in (True, False):
         s = HeatSolver(p, dtype=dtype, backend="hip", tb=tb, device=0, overlap=overlap)
         s.upload(T0)
-        s.step(p.ntime)
+        for m in Y.calls(tb, p.ntime):  # one cycle of depth tb, then the balanced remainder
+            s.step(m)
         outs.append(s.download())
+        hist = s.cycle_hist()
         s.close()
+        Y.assert_ran(hist, tb)
     ref = R.owned(R.ftcs(p, dtype=npdt))
     assert np.array_equal(outs[0], ref), np.abs(outs[0].astype(np.float64) - ref).max()
     assert np.array_equal(outs[1], ref)
@@ -287,10 +296,14 @@ def test_edge_band_plans_bitwise(gpu, native, order, nb, dtype, monkeypatch):
     npdt = np.float64 if dtype == "fp64" else np.float32
     g = LoopbackGroup(p, 3, dtype=dtype, backend="hip", tb=tb, device=0, autotune=0)
     g.upload(R.owned(R.initial_field(p, npdt)))
-    g.step(p.ntime)
+    for m in Y.calls(tb, p.ntime, 2):  # two cycles of depth tb and a 3-step one
+        g.step(m)
     got = g.download()
     plans = [g.plan(i, tb) for i in range(3)]
+    hists = [g.cycle_hist(i) for i in range(3)]
     g.close()
+    for h in hists:  # the plans asserted on are those of a depth that ran
+        Y.assert_ran(h, tb, 2)
     for pl in plans:
         assert all(e[4] == min(nb, e[1] - e[0]) for e in pl["edge_rects"]), pl
     assert np.array_equal(got, R.owned(R.ftcs(p, dtype=npdt)))
@@ -313,18 +326,24 @@ def test_segment_plans_bitwise(gpu, native, order, nseg, dtype, monkeypatch):
     if order == "single":
         s = HeatSolver(p, dtype=dtype, backend="hip", tb=tb, device=0, autotune=0)
         s.upload(R.owned(R.initial_field(p, npdt)))
-        s.step(p.ntime)
+        for m in Y.calls(tb, p.ntime, 2):  # two cycles of depth tb and a 3-step one
+            s.step(m)
         got = s.download()
         pl = s.plan(tb)
+        hists = [s.cycle_hist()]
         s.close()
         plans = [pl]
     else:
         g = LoopbackGroup(p, 3, dtype=dtype, backend="hip", tb=tb, device=0, autotune=0)
         g.upload(R.owned(R.initial_field(p, npdt)))
-        g.step(p.ntime)
+        for m in Y.calls(tb, p.ntime, 2):
+            g.step(m)
         got = g.download()
         plans = [g.plan(i, tb) for i in range(3)]
+        hists = [g.cycle_hist(i) for i in range(3)]
         g.close()
+    for h in hists:  # the plans asserted on are those of a depth that ran (twice: the relaunch)
+        Y.assert_ran(h, tb, 2)
     for pl in plans:
         if nseg > 0:
             assert pl["main_bands"] == -pl["main_items"] and 0 < pl["main_items"] <= nseg, pl
@@ -415,14 +434,18 @@ def test_measured_schedule(gpu, native, dtype, n, steps):
 
 @pytest.mark.parametrize("k", [17, 20, 24])
 def test_deep_fp64_bitwise(gpu, native, k):
-    """fp64 depths 17..24 (one-pass short runs): both kernels (split + single) bitwise."""
+    """fp64 depths 17..24 (one-pass short runs): both kernels (split + single) bitwise.
+    step(k), step(k), step(3): two cycles of depth k (one step(2 k + 3) call runs
+    three of depth about 2 k / 3)."""
     p = prob(1100, 2 * k + 3, "ghost", "sine")
     for overlap in (True, False):
         s = HeatSolver(p, dtype="fp64", backend="hip", tb=k, device=0, overlap=overlap)
         s.upload(R.owned(R.initial_field(p)))
-        s.step(p.ntime)
-        got = s.download()
+        for m in Y.calls(k, p.ntime, 2):
+            s.step(m)
+        got, hist = s.download(), s.cycle_hist()
         s.close()
+        Y.assert_ran(hist, k, 2)
         assert np.array_equal(got, R.owned(R.ftcs(p))), (k, overlap)
 
 

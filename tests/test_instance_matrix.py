@@ -53,6 +53,7 @@ from heat2d.ops import _native as N
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tools"))
+import cycles  # noqa: E402
 import instance_matrix as M  # noqa: E402
 import isa_report  # noqa: E402
 import pipe_worker  # noqa: E402
@@ -328,13 +329,10 @@ def test_step_counts_reach_depth(k):
 
 
 def chunks(k):
-    """The step() calls that make 2 K + 3 steps with two cycles of depth K."""
-    rest = 3
-    out = [k, k]
-    while rest > 0:
-        out.append(min(rest, k))
-        rest -= out[-1]
-    return out
+    """The step() calls that make 2 K + 3 steps with two cycles of depth K
+    (tests/cycles.py calls()), the 3-step remainder as one-cycle calls too."""
+    out = cycles.calls(k, 2 * k + 3, 2)
+    return out[:2] + cycles.balanced(k, out[2])
 
 
 # ------------------------------------------------------------------ GPU

@@ -48,6 +48,7 @@ from heat2d.utils import io
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import cycles as Y  # noqa: E402
 from periodic_worker import problem, rough_field  # noqa: E402
 
 NP = {"fp64": np.float64, "fp32": np.float32}
@@ -73,24 +74,44 @@ def gold(n, dtype, bc_x, bc_y, steps=STEPS, sigma=0.2371, arith="exact", lo=-1.0
 
 
 def run(n, dtype, backend, tb, bc_x, bc_y, steps=STEPS, sigma=0.2371, arith="exact", T0=None, ranks=1, prepare=False,
-        lo=-1.0, hi=1.0, stats=False, **kw):
+        lo=-1.0, hi=1.0, stats=False, calls=None, **kw):
+    """One run of `steps` steps: as one step(steps) call (balanced cycles, none
+    of depth tb once steps > tb), or as the step() calls of `calls`
+    (tests/cycles.py calls(tb, steps, full): `full` cycles of depth tb, then
+    the remainder) — then every solver's cycle_hist() must show those `full`
+    cycles of depth tb. With stats the last call is step_stats() (these
+    boundary conditions take the unfused statistics path: n - 1 steps, then
+    one step with the statistics)."""
     p = problem(n, steps, sigma)
     T0 = rough_field(n, dtype, lo=lo, hi=hi) if T0 is None else T0
     dev = dict(device=0) if backend == "hip" else {}
+    sizes = [steps] if calls is None else list(calls)
+    assert sum(sizes) == steps
+    full = 0 if calls is None else sum(1 for m in sizes if m == tb)
     if ranks > 1:
         s = LoopbackGroup(p, ranks, dtype=dtype, backend=backend, tb=tb, arith=arith, bc_x=bc_x, bc_y=bc_y, **dev, **kw)
         s.upload(T0)
-        s.step(steps)
+        for m in sizes:
+            s.step(m)
         out = s.download()
+        hists = [s.cycle_hist(i) for i in range(ranks)]
         s.close()
+        for h in hists:
+            assert full == 0 or (Y.ran(h, tb, full) and max(h) == tb), (tb, sizes, hists)
         return out
     s = HeatSolver(p, dtype=dtype, backend=backend, tb=tb, arith=arith, bc_x=bc_x, bc_y=bc_y, **dev, **kw)
     s.upload(T0)
-    if prepare:
-        s.prepare(steps)
-    st = s.step_stats(steps) if stats else s.step(steps)
-    out = s.download()
+    st = None
+    for i, m in enumerate(sizes):
+        if prepare:
+            s.prepare(m)
+        if stats and i == len(sizes) - 1:
+            st = s.step_stats(m)
+        else:
+            s.step(m)
+    out, hist = s.download(), s.cycle_hist()
     s.close()
+    assert full == 0 or (Y.ran(hist, tb, full) and max(hist) == tb), (tb, sizes, hist)
     return (out, st) if stats else out
 
 
@@ -331,7 +352,19 @@ def test_raw_op_cpu(native):
 @pytest.mark.parametrize("dtype", ["fp64", "fp32"])
 @pytest.mark.parametrize("bc_x,bc_y", COMBOS, ids=IDS)
 def test_hip_bitwise(native, gpu, bc_x, bc_y, dtype, tb):
-    got = run(261, dtype, "hip", tb, bc_x, bc_y, prepare=True)
+    """Two cycles of depth tb and the remainder (tb 24: 24, 24, 9), asserted
+    from cycle_hist() in run(): one step(57) call at tb 24 runs 19, 19, 19."""
+    got = run(261, dtype, "hip", tb, bc_x, bc_y, prepare=True, calls=Y.calls(tb, STEPS, 2))
+    assert np.array_equal(got, gold(261, dtype, bc_x, bc_y))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["fp64", "fp32"])
+@pytest.mark.parametrize("bc_x,bc_y", COMBOS, ids=IDS)
+def test_hip_single_call(native, gpu, bc_x, bc_y, dtype):
+    """ONE step(57) call at tb 16: balanced cycles (15, 14, 14, 14) with insulated walls."""
+    assert Y.balanced(16, STEPS) == [15, 14, 14, 14]
+    got = run(261, dtype, "hip", 16, bc_x, bc_y, prepare=True)
     assert np.array_equal(got, gold(261, dtype, bc_x, bc_y))
 
 
@@ -344,16 +377,19 @@ def test_hip_frame_images(native, gpu, dtype):
         T0 = rough_field(261, dtype)
         s.upload(T0)
         assert np.array_equal(s.download_field(), R.wrap_frame(T0, bc_x, bc_y)), (bc_x, bc_y)
-        s.step(STEPS)
+        for m in Y.calls(20, STEPS, 2):
+            s.step(m)
         assert np.array_equal(s.download_field(), gold(261, dtype, bc_x, bc_y, framed=True)), (bc_x, bc_y)
+        hist = s.cycle_hist()
         s.close()
+        Y.assert_ran(hist, 20, 2)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", ["fp64", "fp32"])
 def test_hip_jacobi(native, gpu, dtype):
     """Hot-spot-like data at sigma = 0.25, against the jacobi golden."""
-    got = run(261, dtype, "hip", 20, *II.values(), sigma=0.25, arith="jacobi", prepare=True)
+    got = run(261, dtype, "hip", 20, *II.values(), sigma=0.25, arith="jacobi", prepare=True, calls=Y.calls(20, STEPS, 2))
     assert np.array_equal(got, gold(261, dtype, *II.values(), sigma=0.25, arith="jacobi"))
 
 
@@ -361,7 +397,7 @@ def test_hip_jacobi(native, gpu, dtype):
 @pytest.mark.parametrize("arith", ["fma", "auto"])
 def test_hip_fma_and_auto(native, gpu, arith):
     """The contracted form against its CPU twin at r = 0.2371; auto resolves to exact there."""
-    got = run(261, "fp64", "hip", 20, *II.values(), arith=arith, prepare=True)
+    got = run(261, "fp64", "hip", 20, *II.values(), arith=arith, prepare=True, calls=Y.calls(20, STEPS, 2))
     if arith == "auto":
         assert np.array_equal(got, gold(261, "fp64", *II.values()))
     else:
@@ -415,7 +451,7 @@ def test_hip_narrow_last_strip(native, gpu, dtype, n):
     """Depth 20 with a last strip of 5 columns (fp64: 88 useful columns per
     strip, fp32: 208): narrower than the strip halo, so the strip before it
     reaches the frame column too and must not stay on the interior kernel."""
-    got = run(n, dtype, "hip", 20, *II.values(), prepare=True)
+    got = run(n, dtype, "hip", 20, *II.values(), prepare=True, calls=Y.calls(20, STEPS, 2))
     assert np.array_equal(got, gold(n, dtype, *II.values()))
 
 
@@ -434,14 +470,14 @@ def test_hip_forced_pipe(native, gpu, tmp_path):
 @pytest.mark.parametrize("ranks", [2, 3])
 def test_hip_loopback(native, gpu, ranks, overlap):
     for dtype in ("fp64", "fp32"):
-        got = run(262, dtype, "hip", 20, *II.values(), ranks=ranks, overlap=overlap)
+        got = run(262, dtype, "hip", 20, *II.values(), ranks=ranks, overlap=overlap, calls=Y.calls(20, STEPS, 2))
         assert np.array_equal(got, gold(262, dtype, *II.values())), dtype
 
 
 @pytest.mark.gpu
 def test_hip_loopback_insulated_x_only(native, gpu):
     """3 ranks, x insulated and y Dirichlet: the first and last slab differ from the middle one."""
-    got = run(262, "fp64", "hip", 20, "insulated", "dirichlet", ranks=3)
+    got = run(262, "fp64", "hip", 20, "insulated", "dirichlet", ranks=3, calls=Y.calls(20, STEPS, 2))
     assert np.array_equal(got, gold(262, "fp64", "insulated", "dirichlet"))
 
 
@@ -453,9 +489,11 @@ def test_hip_guard_nan_beyond_frame(native, gpu, dtype):
     p = dataclasses.replace(p, ic=dataclasses.replace(p.ic, pad=float("nan")))
     s = HeatSolver(p, dtype=dtype, backend="hip", tb=20, arith="exact", device=0, **II)
     s.upload(rough_field(261, dtype))
-    s.prepare(STEPS)
-    s.step(STEPS)
-    got = s.download()
+    for m in Y.calls(20, STEPS, 2):
+        s.prepare(m)
+        s.step(m)
+    got, hist = s.download(), s.cycle_hist()
+    Y.assert_ran(hist, 20, 2)
     L = s.layout
     out = np.empty((L.nrows + 2 * L.halo, L.pitch), dtype=NP[dtype])
     N.call("heat2d_solver_download_region", s._h, -L.halo, L.nrows + L.halo, -L.cpad, L.pitch - L.cpad,
@@ -471,7 +509,7 @@ def test_hip_guard_nan_beyond_frame(native, gpu, dtype):
 @pytest.mark.parametrize("dtype", ["fp64", "fp32"])
 def test_hip_step_stats(native, gpu, dtype):
     lo, hi = 0.0, float(np.log10(2.0))
-    got, st = run(261, dtype, "hip", 20, *II.values(), lo=lo, hi=hi, stats=True, prepare=True)
+    got, st = run(261, dtype, "hip", 20, *II.values(), lo=lo, hi=hi, stats=True, prepare=True, calls=Y.calls(20, STEPS, 2))
     g = gold(261, dtype, *II.values(), lo=lo, hi=hi)
     g1 = gold(261, dtype, *II.values(), steps=STEPS - 1, lo=lo, hi=hi)
     assert np.array_equal(got, g)

@@ -13,6 +13,8 @@ Oracles:
 GPU cases cover every edge kind, the split schedule + autotuner, the fused
 statistics, the hipRTC engine and multi-rank slabs."""
 import dataclasses
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -20,6 +22,9 @@ import pytest
 import heat2d
 from heat2d.models import reference as R
 from heat2d.models.heat2d import HeatSolver, LoopbackGroup
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cycles as Y  # noqa: E402
 
 
 def prob(n, steps, conv="ghost", ic="sine", sigma=0.25, dom=1.0):
@@ -38,13 +43,20 @@ def golden(p, npdt, T0=None, arith="jacobi", steps=None):
     return R.owned(R.ftcs(p, steps, dtype=npdt, T0=full, arith=arith))
 
 
-def run(p, backend, dtype, tb, arith="jacobi", upload=None, steps=None, **kw):
+def run(p, backend, dtype, tb, arith="jacobi", upload=None, steps=None, full=0, **kw):
+    """full > 0: the steps as tests/cycles.py calls(tb, steps, full) — `full`
+    cycles of depth tb, asserted from cycle_hist(), then the remainder — and
+    not as one step() call, whose balanced cycles are all shallower than tb."""
     s = HeatSolver(p, dtype=dtype, backend=backend, tb=tb, arith=arith, device=0 if backend == "hip" else None, **kw)
     if upload is not None:
         s.upload(upload)
-    s.step(p.ntime if steps is None else steps)
-    out = s.download()
+    steps = p.ntime if steps is None else steps
+    for m in Y.calls(tb, steps, full) if full else [steps]:
+        s.step(m)
+    out, hist = s.download(), s.cycle_hist()
     s.close()
+    if full:
+        Y.assert_ran(hist, tb, full)
     return out
 
 
@@ -112,11 +124,12 @@ def test_hip_jacobi_equals_golden(gpu, native, dtype, tb):
                                         ("fp32", 16, 1300), ("fp32", 20, 1300), ("fp32", 17, 1500),
                                         ("fp32", 24, 1300), ("fp32", 21, 1500)])
 def test_hip_jacobi_split_schedule(gpu, native, dtype, tb, n):
-    """Split (MAIN + EDGE) schedule with the autotuner, rough data."""
+    """Split (MAIN + EDGE) schedule with the autotuner, rough data: step(tb),
+    step(tb), step(3) — two cycles of depth tb (no prepare(): no measured schedule)."""
     p = prob(n, 2 * tb + 3)
     npdt = np.float64 if dtype == "fp64" else np.float32
     T0 = rough(p, npdt)
-    got = run(p, "hip", dtype, tb, upload=T0, autotune=1)
+    got = run(p, "hip", dtype, tb, upload=T0, autotune=1, full=2)
     assert np.array_equal(got, golden(p, npdt, T0))
 
 
@@ -188,10 +201,12 @@ def test_hip_jacobi_single_launch_frame_rects(gpu, native, monkeypatch, dtype, t
     T0 = rough(p, npdt)
     s = HeatSolver(p, dtype=dtype, backend="hip", tb=tb, device=0, autotune=0, arith="jacobi")
     s.upload(T0)
-    s.step(p.ntime)
-    got = s.download()
+    for m in Y.calls(tb, p.ntime, 2):
+        s.step(m)
+    got, hist = s.download(), s.cycle_hist()
     pl = s.plan(tb)
     s.close()
+    Y.assert_ran(hist, tb, 2)  # the plan asserted on is the one that ran
     assert pl["order"] == "single" and len(pl["main_rects"]) == 5, pl
     top, bot = pl["main_rects"][1], pl["main_rects"][3]
     assert top[0] == 0 and top[4] == 1 and bot[1] == p.n_owned and bot[4] == 1, pl
@@ -213,10 +228,12 @@ def test_hip_ring8_single_launch(gpu, native, monkeypatch, dtype, ring, arith, t
     T0 = rough(p, npdt)
     s = HeatSolver(p, dtype=dtype, backend="hip", tb=tb, device=0, autotune=0, arith=arith)
     s.upload(T0)
-    s.step(p.ntime)
-    got = s.download()
+    for m in Y.calls(tb, p.ntime, 2):
+        s.step(m)
+    got, hist = s.download(), s.cycle_hist()
     pl = s.plan(tb)
     s.close()
+    Y.assert_ran(hist, tb, 2)  # the plan asserted on is the one that ran
     assert pl["order"] == "single" and pl["ring"] == ring, pl
     assert np.array_equal(got, golden(p, npdt, T0, arith=arith))
 
@@ -240,9 +257,14 @@ def test_hip_dynamic_queue(gpu, native, monkeypatch, dtype, tb, order, nseg, gra
     T0 = rough(p, npdt)
     s = HeatSolver(p, dtype=dtype, backend="hip", tb=tb, device=0, autotune=0, arith="jacobi", graph=graph)
     s.upload(T0)
-    s.step(p.ntime)
-    got = s.download()
+    # graph: one call, whose pair branch replays two cycles of depth tb; eager: step(tb), step(tb), the rest
+    sizes = [p.ntime] if graph else Y.calls(tb, p.ntime, 2)
+    assert Y.depths(tb, sizes, graph=graph)[:2] == [tb, tb]
+    for m in sizes:
+        s.step(m)
+    got, hist = s.download(), s.cycle_hist()
     pl = s.plan(tb)
     s.close()
+    Y.assert_ran(hist, tb, 2)  # the queue's reset between two launches of the plan asserted on
     assert pl["dynamic"] == 1 and pl["main_items"] > pl["main_waves"], pl
     assert np.array_equal(got, golden(p, npdt, T0))

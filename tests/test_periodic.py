@@ -36,6 +36,7 @@ from heat2d.utils import io
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import cycles as Y  # noqa: E402
 from periodic_worker import problem, rough_field  # noqa: E402
 
 NP = {"fp64": np.float64, "fp32": np.float32}
@@ -69,24 +70,44 @@ def rolled(T0, shift):
 
 
 def run(n, dtype, backend, tb, bc_x, bc_y, steps=STEPS, sigma=0.2371, arith="exact", T0=None, ranks=1, prepare=False,
-        lo=-1.0, hi=1.0, stats=False, **kw):
+        lo=-1.0, hi=1.0, stats=False, calls=None, **kw):
+    """One run of `steps` steps: as one step(steps) call (balanced cycles, none
+    of depth tb once steps > tb), or as the step() calls of `calls`
+    (tests/cycles.py calls(tb, steps, full): `full` cycles of depth tb, then
+    the remainder) — then every solver's cycle_hist() must show those `full`
+    cycles of depth tb. With stats the last call is step_stats() (these
+    boundary conditions take the unfused statistics path: n - 1 steps, then
+    one step with the statistics)."""
     p = problem(n, steps, sigma)
     T0 = rough_field(n, dtype, lo=lo, hi=hi) if T0 is None else T0
     dev = dict(device=0) if backend == "hip" else {}
+    sizes = [steps] if calls is None else list(calls)
+    assert sum(sizes) == steps
+    full = 0 if calls is None else sum(1 for m in sizes if m == tb)
     if ranks > 1:
         s = LoopbackGroup(p, ranks, dtype=dtype, backend=backend, tb=tb, arith=arith, bc_x=bc_x, bc_y=bc_y, **dev, **kw)
         s.upload(T0)
-        s.step(steps)
+        for m in sizes:
+            s.step(m)
         out = s.download()
+        hists = [s.cycle_hist(i) for i in range(ranks)]
         s.close()
+        for h in hists:
+            assert full == 0 or (Y.ran(h, tb, full) and max(h) == tb), (tb, sizes, hists)
         return out
     s = HeatSolver(p, dtype=dtype, backend=backend, tb=tb, arith=arith, bc_x=bc_x, bc_y=bc_y, **dev, **kw)
     s.upload(T0)
-    if prepare:
-        s.prepare(steps)
-    st = s.step_stats(steps) if stats else s.step(steps)
-    out = s.download()
+    st = None
+    for i, m in enumerate(sizes):
+        if prepare:
+            s.prepare(m)
+        if stats and i == len(sizes) - 1:
+            st = s.step_stats(m)
+        else:
+            s.step(m)
+    out, hist = s.download(), s.cycle_hist()
     s.close()
+    assert full == 0 or (Y.ran(hist, tb, full) and max(hist) == tb), (tb, sizes, hist)
     return (out, st) if stats else out
 
 
@@ -112,6 +133,18 @@ def test_golden_frame_is_wrap_image():
 @pytest.mark.parametrize("bc_x,bc_y", COMBOS, ids=IDS)
 def test_cpu_twin_bitwise(native, bc_x, bc_y, dtype, tb):
     assert np.array_equal(run(77, dtype, "cpu", tb, bc_x, bc_y), gold(77, dtype, bc_x, bc_y))
+
+
+@pytest.mark.parametrize("tb", [20, 24])
+@pytest.mark.parametrize("bc_x,bc_y", COMBOS[:2], ids=IDS[:2])
+def test_cpu_twin_deep_calls(native, bc_x, bc_y, tb):
+    """The GPU tests' call sequences (step(tb), step(tb), the remainder) on the
+    CPU twin at depths 20 and 24 — 24: as many levels as there are ghost
+    columns — against the same golden: the oracle of test_hip_bitwise is
+    exercised without a GPU. run() asserts the depth from cycle_hist()."""
+    assert Y.calls(tb, STEPS, 2) == [tb, tb, STEPS - 2 * tb]
+    got = run(261, "fp64", "cpu", tb, bc_x, bc_y, calls=Y.calls(tb, STEPS, 2))
+    assert np.array_equal(got, gold(261, "fp64", bc_x, bc_y))
 
 
 @pytest.mark.parametrize("ranks", [2, 3])
@@ -316,11 +349,25 @@ def test_raw_wrap_ops_cpu(native):
 # ------------------------------------------------------------------ GPU
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("tb", [1, 4, 16, 17, 20, 24])
+@pytest.mark.parametrize("tb", [1, 4, 16, 17, 20, 21, 23, 24])
 @pytest.mark.parametrize("dtype", ["fp64", "fp32"])
 @pytest.mark.parametrize("bc_x,bc_y", COMBOS, ids=IDS)
 def test_hip_bitwise(native, gpu, bc_x, bc_y, dtype, tb):
-    got = run(261, dtype, "hip", tb, bc_x, bc_y, prepare=True)
+    """Two cycles of depth tb and the remainder (tb 24: 24, 24, 9), asserted
+    from cycle_hist() in run(): one step(57) call at tb 24 runs 19, 19, 19.
+    21 and 23: odd depths whose strip halo rounds up to whole lanes; 24: the
+    24 ghost columns of periodic y are crossed in exactly 24 levels."""
+    got = run(261, dtype, "hip", tb, bc_x, bc_y, prepare=True, calls=Y.calls(tb, STEPS, 2))
+    assert np.array_equal(got, gold(261, dtype, bc_x, bc_y))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["fp64", "fp32"])
+@pytest.mark.parametrize("bc_x,bc_y", COMBOS, ids=IDS)
+def test_hip_single_call(native, gpu, bc_x, bc_y, dtype):
+    """ONE step(57) call at tb 16: balanced cycles (15, 14, 14, 14) under the periodic views."""
+    assert Y.balanced(16, STEPS) == [15, 14, 14, 14]
+    got = run(261, dtype, "hip", 16, bc_x, bc_y, prepare=True)
     assert np.array_equal(got, gold(261, dtype, bc_x, bc_y))
 
 
@@ -347,14 +394,14 @@ def test_hip_split_orders(native, gpu, tmp_path, order):
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", ["fp64", "fp32"])
 def test_hip_jacobi(native, gpu, dtype):
-    got = run(261, dtype, "hip", 20, "periodic", "periodic", sigma=0.25, arith="jacobi", prepare=True)
+    got = run(261, dtype, "hip", 20, "periodic", "periodic", sigma=0.25, arith="jacobi", prepare=True, calls=Y.calls(20, STEPS, 2))
     assert np.array_equal(got, gold(261, dtype, "periodic", "periodic", sigma=0.25, arith="jacobi"))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype", ["fp64", "fp32"])
 def test_hip_fast_within_bound(native, gpu, dtype):
-    got = run(261, dtype, "hip", 20, "periodic", "periodic", arith="fast", prepare=True)
+    got = run(261, dtype, "hip", 20, "periodic", "periodic", arith="fast", prepare=True, calls=Y.calls(20, STEPS, 2))
     ref = gold(261, dtype, "periodic", "periodic")
     tmax = float(np.abs(rough_field(261, dtype)).max())
     err = float(np.abs(got.astype(np.float64) - ref.astype(np.float64)).max())
@@ -366,8 +413,9 @@ def test_hip_fast_within_bound(native, gpu, dtype):
 @pytest.mark.parametrize("n,ranks", [(261, 1), (262, 3)])
 def test_hip_roll_identity(native, gpu, n, ranks):
     shift = (37, 130)
-    base = run(n, "fp64", "hip", 20, "periodic", "periodic", ranks=ranks)
-    got = run(n, "fp64", "hip", 20, "periodic", "periodic", ranks=ranks, T0=rolled(rough_field(n, "fp64"), shift))
+    base = run(n, "fp64", "hip", 20, "periodic", "periodic", ranks=ranks, calls=Y.calls(20, STEPS, 2))
+    got = run(n, "fp64", "hip", 20, "periodic", "periodic", ranks=ranks, T0=rolled(rough_field(n, "fp64"), shift),
+              calls=Y.calls(20, STEPS, 2))
     assert np.array_equal(got, np.roll(base, shift, axis=(0, 1)))
     assert np.array_equal(base, gold(n, "fp64", "periodic", "periodic"))
 
@@ -381,7 +429,7 @@ def test_hip_loopback(native, gpu, ranks, overlap):
         assert [nr for _, nr in g.slabs()] == [88, 87, 87]
         g.close()
     for dtype in ("fp64", "fp32"):
-        got = run(262, dtype, "hip", 20, "periodic", "periodic", ranks=ranks, overlap=overlap)
+        got = run(262, dtype, "hip", 20, "periodic", "periodic", ranks=ranks, overlap=overlap, calls=Y.calls(20, STEPS, 2))
         assert np.array_equal(got, gold(262, dtype, "periodic", "periodic")), dtype
 
 
@@ -394,14 +442,17 @@ def test_hip_guard_nan_beyond_ghosts(native, gpu, dtype):
     p = dataclasses.replace(p, ic=dataclasses.replace(p.ic, pad=float("nan")))
     s = HeatSolver(p, dtype=dtype, backend="hip", tb=20, arith="exact", device=0, **PP)
     s.upload(rough_field(261, dtype))
-    s.prepare(STEPS)
-    s.step(STEPS)
-    got = s.download()
+    for m in Y.calls(20, STEPS, 2):
+        s.prepare(m)
+        s.step(m)
+    got, hist = s.download(), s.cycle_hist()
     L = s.layout
     out = np.empty((L.nrows + 2 * L.halo, L.pitch), dtype=NP[dtype])
     N.call("heat2d_solver_download_region", s._h, -L.halo, L.nrows + L.halo, -L.cpad, L.pitch - L.cpad,
            out.ctypes.data, L.pitch)
     s.close()
+    Y.assert_ran(hist, 20, 2)
+    assert max(hist) == 20, hist
     assert np.isnan(out[:L.halo - 20, :]).all() and np.isnan(out[:, :L.cpad - 24]).all()  # the guard was in place
     assert not np.isnan(got).any()
     assert np.array_equal(got, gold(261, dtype, "periodic", "periodic"))
@@ -411,7 +462,7 @@ def test_hip_guard_nan_beyond_ghosts(native, gpu, dtype):
 @pytest.mark.parametrize("dtype", ["fp64", "fp32"])
 def test_hip_fused_stats(native, gpu, dtype):
     lo, hi = 0.0, float(np.log10(2.0))
-    got, st = run(261, dtype, "hip", 20, "periodic", "periodic", lo=lo, hi=hi, stats=True, prepare=True)
+    got, st = run(261, dtype, "hip", 20, "periodic", "periodic", lo=lo, hi=hi, stats=True, prepare=True, calls=Y.calls(20, STEPS, 2))
     g = gold(261, dtype, "periodic", "periodic", lo=lo, hi=hi)
     g1 = gold(261, dtype, "periodic", "periodic", steps=STEPS - 1, lo=lo, hi=hi)
     assert np.array_equal(got, g)

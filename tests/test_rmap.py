@@ -36,6 +36,7 @@ from heat2d.ops import _native as N
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import cycles as Y  # noqa: E402
 from rmap_worker import problem, rough_field, rough_map  # noqa: E402
 
 NP = {"fp64": np.float64, "fp32": np.float32}
@@ -70,7 +71,10 @@ def gold(n, dtype, steps, arith="exact", rows=None, seed=1, framed=False):
     return _GOLD[key] if framed else R.owned(_GOLD[key])
 
 
-def run(n, dtype, backend, tb, steps, arith="exact", ranks=1, rows=None, prepare=False, **kw):
+def run(n, dtype, backend, tb, steps, arith="exact", ranks=1, rows=None, prepare=False, full=0, **kw):
+    """full > 0: the steps as tests/cycles.py calls(tb, steps, full) — `full`
+    cycles of depth tb, asserted from cycle_hist(), then the remainder — and
+    not as one step() call, whose balanced cycles are all shallower than tb."""
     p = problem(n, steps)
     T0, M = rough_field(n, dtype, rows=rows), rough_map(n, dtype, rows=rows)
     dev = dict(device=0) if backend == "hip" else {}
@@ -80,14 +84,18 @@ def run(n, dtype, backend, tb, steps, arith="exact", ranks=1, rows=None, prepare
         s.step(steps)
         out = s.download()
         s.close()
+        assert not full
         return out
     s = HeatSolver(p, dtype=dtype, backend=backend, tb=tb, arith=arith, rmap=M, rows=rows, **dev, **kw)
     s.upload(T0)
-    if prepare:
-        s.prepare(steps)
-    s.step(steps)
-    out = s.download()
+    for m in Y.calls(tb, steps, full) if full else [steps]:
+        if prepare:
+            s.prepare(m)
+        s.step(m)
+    out, hist = s.download(), s.cycle_hist()
     s.close()
+    if full:
+        Y.assert_ran(hist, tb, full)
     return out
 
 
@@ -502,12 +510,13 @@ def _depths():
 @pytest.mark.parametrize("arith", ["exact", "fma"])
 @pytest.mark.parametrize("dtype", ["fp64", "fp32"])
 def test_hip_one_strip(native, gpu, dtype, arith, tb):
-    """n = 77: one strip; 2 * tb + 3 steps: two full passes and a shallower one."""
+    """n = 77: one strip; 2 * tb + 3 steps: two full passes and a shallower one
+    (step(tb), step(tb), step(3): one step(2 tb + 3) call runs none of depth tb)."""
     if tb == 13 and depth_max() < 13:
         tb = "D"  # (13 only if <= D: the deepest pass then runs twice)
     tb = depth(tb)
     steps = 2 * tb + 3
-    got = run(77, dtype, "hip", tb, steps, arith)
+    got = run(77, dtype, "hip", tb, steps, arith, full=2)
     assert np.array_equal(got, gold(77, dtype, steps, arith))
 
 
@@ -539,8 +548,10 @@ def test_hip_split_plans(native, gpu, tmp_path, dtype, env):
     map: one-wave strips) — every launch on the map kernel."""
     tb = depth_max() if "HEAT2D_PIPE" in env else 8
     a = {"n": 2897, "rows": 301, "steps": 37, "tb": tb, "dtype": dtype, "sigma": 0.2, "arith": "exact"}
+    a["calls"] = Y.calls(tb, 37, 2)  # two cycles of depth tb (the queue's reset between them), then the rest
     info, got = worker(tmp_path, a, **env)
     plan = info["plan"]
+    Y.assert_ran(info["cycle_hist"], tb, 2)  # the plan asserted on is the one that ran
     print(f"{dtype} {env}: plan {plan}")
     if "HEAT2D_SPLIT_ORDER" in env:
         assert plan["valid"] == 2

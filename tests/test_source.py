@@ -40,6 +40,7 @@ from heat2d.ops import _native as N
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import cycles as Y  # noqa: E402
 from source_worker import problem, rough_field, rough_source  # noqa: E402
 
 NP = {"fp64": np.float64, "fp32": np.float32}
@@ -74,7 +75,10 @@ def gold(n, dtype, steps, sigma=0.2, arith="exact", rows=None, seed=1, framed=Fa
     return _GOLD[key] if framed else R.owned(_GOLD[key])
 
 
-def run(n, dtype, backend, tb, steps, sigma=0.2, arith="exact", ranks=1, rows=None, prepare=False, source="rough", **kw):
+def run(n, dtype, backend, tb, steps, sigma=0.2, arith="exact", ranks=1, rows=None, prepare=False, source="rough", full=0, **kw):
+    """full > 0: the steps as tests/cycles.py calls(tb, steps, full) — `full`
+    cycles of depth tb, asserted from cycle_hist(), then the remainder — and
+    not as one step() call, whose balanced cycles are all shallower than tb."""
     p = problem(n, steps, sigma)
     T0 = rough_field(n, dtype, rows=rows)
     S = rough_source(n, dtype, rows=rows) if isinstance(source, str) else source
@@ -85,14 +89,18 @@ def run(n, dtype, backend, tb, steps, sigma=0.2, arith="exact", ranks=1, rows=No
         s.step(steps)
         out = s.download()
         s.close()
+        assert not full
         return out
     s = HeatSolver(p, dtype=dtype, backend=backend, tb=tb, arith=arith, source=S, rows=rows, **dev, **kw)
     s.upload(T0)
-    if prepare:
-        s.prepare(steps)
-    s.step(steps)
-    out = s.download()
+    for m in Y.calls(tb, steps, full) if full else [steps]:
+        if prepare:
+            s.prepare(m)
+        s.step(m)
+    out, hist = s.download(), s.cycle_hist()
     s.close()
+    if full:
+        Y.assert_ran(hist, tb, full)
     return out
 
 
@@ -512,10 +520,11 @@ DEPTHS = [1, 2, 7, 8, 13, 16, "D"]
 @pytest.mark.parametrize("arith", ["exact", "fma"])
 @pytest.mark.parametrize("dtype", ["fp64", "fp32"])
 def test_hip_one_strip(native, gpu, dtype, arith, tb):
-    """n = 77: one strip; 2 * tb + 3 steps: two full passes and a shallower one."""
+    """n = 77: one strip; 2 * tb + 3 steps: two full passes and a shallower one
+    (step(tb), step(tb), step(3): one step(2 tb + 3) call runs none of depth tb)."""
     tb = depth(tb)
     steps = 2 * tb + 3
-    got = run(77, dtype, "hip", tb, steps, 0.2, arith)
+    got = run(77, dtype, "hip", tb, steps, 0.2, arith, full=2)
     assert np.array_equal(got, gold(77, dtype, steps, 0.2, arith))
 
 
@@ -548,8 +557,10 @@ def test_hip_split_plans(native, gpu, tmp_path, dtype, env):
     source: one-wave strips) — every launch on the source kernel."""
     tb = 16 if "HEAT2D_PIPE" in env else 8
     a = {"n": 2897, "rows": 301, "steps": 37, "tb": tb, "dtype": dtype, "sigma": 0.2, "arith": "exact"}
+    a["calls"] = Y.calls(tb, 37, 2)  # two cycles of depth tb (the queue's reset between them), then the rest
     info, got = worker(tmp_path, a, **env)
     plan = info["plan"]
+    Y.assert_ran(info["cycle_hist"], tb, 2)  # the plan asserted on is the one that ran
     print(f"{dtype} {env}: plan {plan}")
     if "HEAT2D_SPLIT_ORDER" in env:
         assert plan["valid"] == 2
