@@ -232,6 +232,22 @@ int heat2d_cpu_tb_var(int dtype, const void* src, void* dst, const heat2d_layout
   });
 }
 
+int heat2d_tb_div(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                  void* stream, int64_t tile_rows, int arith, const void* rx, const void* ry) {
+  return guarded([&] {
+    HEAT2D_REQUIRE(rx != nullptr && ry != nullptr, "heat2d_tb_div needs both face-coefficient buffers");
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, as_stream(stream), tile_rows, 0, arith, 0, nullptr, nullptr, rx, ry);
+  });
+}
+
+int heat2d_cpu_tb_div(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                      int arith, const void* rx, const void* ry) {
+  return guarded([&] {
+    HEAT2D_REQUIRE(rx != nullptr && ry != nullptr, "heat2d_cpu_tb_div needs both face-coefficient buffers");
+    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, arith, 0, nullptr, nullptr, rx, ry);
+  });
+}
+
 int heat2d_wrap_cols(int dtype, void* field, const heat2d_layout* L, int64_t r0, int64_t r1, void* stream,
                      int on_device) {
   return guarded([&] {
@@ -383,6 +399,10 @@ int heat2d_plan_max_grid_ext(int dtype, int nranks, int64_t budget_bytes, int so
   return guarded([&] { *n = plan_max_grid(dtype, nranks, budget_bytes, 0, source != 0, rmap != 0); });
 }
 
+int heat2d_plan_max_grid_faces(int dtype, int nranks, int64_t budget_bytes, int source, int rmap, int faces, int64_t* n) {
+  return guarded([&] { *n = plan_max_grid(dtype, nranks, budget_bytes, 0, source != 0, rmap != 0, faces != 0); });
+}
+
 int heat2d_mem_info(int device, int64_t* free_bytes, int64_t* total_bytes) {
   return guarded([&] {
     if (hipSetDevice(device) != hipSuccess) fail(__FILE__, __LINE__, "hipSetDevice failed");
@@ -450,6 +470,18 @@ int heat2d_solver_rmap(void* s, int32_t* out3) {
     out3[0] = static_cast<Solver*>(s)->config().rmap;
     out3[1] = static_cast<Solver*>(s)->has_rmap() ? 1 : 0;
     out3[2] = kMaxTBVar;
+  });
+}
+
+int heat2d_solver_set_faces(void* s, const void* rx, const void* ry, int64_t ld) {
+  return guarded([&] { static_cast<Solver*>(s)->set_faces(rx, ry, ld); });
+}
+
+int heat2d_solver_faces(void* s, int32_t* out3) {
+  return guarded([&] {
+    out3[0] = static_cast<Solver*>(s)->config().faces;
+    out3[1] = static_cast<Solver*>(s)->has_faces() ? 1 : 0;
+    out3[2] = kMaxTBDiv;
   });
 }
 
@@ -570,6 +602,10 @@ int heat2d_group_set_source(void* g, const void* host, int64_t ld) {
 
 int heat2d_group_set_rmap(void* g, const void* host, int64_t ld) {
   return guarded([&] { static_cast<LoopbackGroup*>(g)->set_rmap(host, ld); });
+}
+
+int heat2d_group_set_faces(void* g, const void* rx, const void* ry, int64_t ld) {
+  return guarded([&] { static_cast<LoopbackGroup*>(g)->set_faces(rx, ry, ld); });
 }
 
 int heat2d_group_member(void* g, int i, void** solver) {

@@ -88,6 +88,9 @@ struct Args {
   // --rmap FILE.npy: diffusivity map, the frame-inclusive (n+2) x (n+2) per-point diffusion number
   // nu(x, y) dt / dx^2 (SolverConfig::rmap; converted to the run's dtype, a wrong shape fails)
   std::string rmap;
+  // --faces FILE.npy: the conservative form's per-face diffusion numbers, shape (2, n+2, n+2): RX then RY,
+  // already multiplied by dt / dx^2 (SolverConfig::faces; converted to the run's dtype, a wrong shape fails)
+  std::string faces;
 };
 
 void usage() {
@@ -100,7 +103,7 @@ void usage() {
       "              [--checkpoint DIR [--checkpoint-every N]] [--restart DIR]\n"
       "              [--transport auto|rccl|peer] [--share-gpu] [--autotune auto|on|off] [--edge-shift N]\n"
       "              [--bc-x dirichlet|periodic|insulated] [--bc-y dirichlet|periodic|insulated]\n"
-      "              [--source FILE.npy] [--rmap FILE.npy]\n");
+      "              [--source FILE.npy] [--rmap FILE.npy] [--faces FILE.npy]\n");
 }
 
 Args parse_args(int argc, char** argv) {
@@ -147,6 +150,7 @@ Args parse_args(int argc, char** argv) {
     else if (s == "--share-gpu") a.share_gpu = true;
     else if (s == "--source") a.source = need("--source");
     else if (s == "--rmap") a.rmap = need("--rmap");
+    else if (s == "--faces") a.faces = need("--faces");
     else if (s == "--bc-x" || s == "--bc-y") {
       const std::string v = need(s.c_str());
       if (v != "dirichlet" && v != "periodic" && v != "insulated") {
@@ -207,6 +211,9 @@ struct Shared {
   // --rmap: the same for the diffusivity map
   std::vector<char> rmap;
   std::string rmap_sha256;
+  // --faces: the same for the face coefficients (RX, then RY)
+  std::vector<char> faces;
+  std::string faces_sha256;
 };
 
 // Collective checkpoint (every rank its slab, then rank 0 publishes meta.json).
@@ -236,6 +243,7 @@ void save_checkpoint(Shared& sh, Solver& s, Transport& tr, int rank, int64_t ste
     m.bc_y = bc_names[s.config().bc_y];
     m.source_sha256 = sh.source_sha256;  // (empty: no source, written as null)
     m.rmap_sha256 = sh.rmap_sha256;      // (empty: no map, the key is not written)
+    m.faces_sha256 = sh.faces_sha256;    // (empty: no face coefficients, the key is not written)
     ckpt::write_meta(a.checkpoint, name, m);
   }
   tr.barrier();
@@ -328,6 +336,25 @@ void run_rank(Shared& sh, int rank) {
         if (rmax > 0.25 + 1e-12) std::fprintf(stderr, "warning: max r = %.6g > 0.25: FTCS is unstable in 2-D\n", rmax);
       }
     }
+    if (!a.faces.empty()) {
+      cfg.faces = 1;
+      std::lock_guard<std::mutex> g(sh.mu);
+      if (sh.faces.empty()) {
+        const int64_t m = sh.prob.n_owned + 2;
+        sh.faces = ckpt::read_faces(a.faces, m, m, cfg.dtype, &sh.faces_sha256);
+        auto at = [&](int w, int64_t i, int64_t j) {
+          const size_t k = (size_t)((w * m + i) * m + j);
+          return cfg.dtype == 0 ? (double)reinterpret_cast<const float*>(sh.faces.data())[k]
+                                : reinterpret_cast<const double*>(sh.faces.data())[k];
+        };
+        double smax = 0;  // the stability warning of the scalar r (4r > 1), on the largest face sum of an owned point
+        for (int64_t i = 1; i < m - 1; ++i)
+          for (int64_t j = 1; j < m - 1; ++j)
+            smax = std::max(smax, at(0, i, j) + at(0, i, j - 1) + at(1, i, j) + at(1, i - 1, j));
+        if (smax > 1.0 + 1e-12)
+          std::fprintf(stderr, "warning: max face sum = %.6g > 1: FTCS is unstable in 2-D\n", smax);
+      }
+    }
     // boundary conditions: the flags, or a restart's checkpointed settings (a
     // flag that says otherwise fails: the resumed run would not be the saved one)
     std::string bc_x = a.bc_x.empty() ? "dirichlet" : a.bc_x, bc_y = a.bc_y.empty() ? "dirichlet" : a.bc_y;
@@ -356,6 +383,17 @@ void run_rank(Shared& sh, int rank) {
                                      " != " + m0.rmap_sha256 + ")");
       }
     }
+    if (!a.restart.empty()) {
+      // ... and the face coefficients the checkpointed run had (not saved either), and no others
+      const ckpt::Meta mf = ckpt::read_meta(a.restart);
+      if (mf.faces_sha256 != sh.faces_sha256) {
+        HEAT2D_REQUIRE(!mf.faces_sha256.empty(), "the checkpoint was written without face coefficients, this run has them (--faces)");
+        HEAT2D_REQUIRE(!sh.faces_sha256.empty(), "the checkpoint was written with face coefficients: give the restart the same "
+                                                 "--faces (sha256 " + mf.faces_sha256 + ")");
+        fail(__FILE__, __LINE__, "the restart's face coefficients differ from the checkpoint's (sha256 " + sh.faces_sha256 +
+                                     " != " + mf.faces_sha256 + ")");
+      }
+    }
     auto bc_code = [](const std::string& v) { return v == "periodic" ? kBcPeriodic : v == "insulated" ? kBcInsulated : kBcDirichlet; };
     cfg.bc_x = bc_code(bc_x);
     cfg.bc_y = bc_code(bc_y);
@@ -370,20 +408,25 @@ void run_rank(Shared& sh, int rank) {
       // the whole run — the IC in [m, 2m] (the reference's: 1 and 2) keeps
       // every sum - 4c exact; a restart's data is not known to be
       // (with a source auto stays with the solver: fma or exact, never jacobi)
-      if (sh.prob.r == 0.25 && ic_sterbenz_safe(sh.prob.ic) && a.restart.empty() && cfg.engine == 0 && !cfg.source && !cfg.rmap) {
+      if (sh.prob.r == 0.25 && ic_sterbenz_safe(sh.prob.ic) && a.restart.empty() && cfg.engine == 0 && !cfg.source && !cfg.rmap && !cfg.faces) {
         cfg.arith = 2;
         arith_used = "jacobi (auto)";
       } else {
         int e = 0;
         const bool pow2 = sh.prob.r > 0 && std::frexp(sh.prob.r, &e) == 0.5;
         // (with a diffusivity map the solver's auto is exact: the multipliers are no one power of two)
-        arith_used = pow2 && !cfg.rmap ? "fma (auto)" : "exact (auto)";
+        // (and with face coefficients)
+        arith_used = pow2 && !cfg.rmap && !cfg.faces ? "fma (auto)" : "exact (auto)";
       }
     }
     if (root) sh.arith_used = arith_used;
     Solver s(cfg, tr);
     if (cfg.source) s.set_source(sh.source.data(), sh.prob.n_owned + 2);
     if (cfg.rmap) s.set_rmap(sh.rmap.data(), sh.prob.n_owned + 2);
+    if (cfg.faces) {
+      const int64_t m = sh.prob.n_owned + 2;
+      s.set_faces(sh.faces.data(), sh.faces.data() + (size_t)(m * m) * (cfg.dtype == 0 ? 4 : 8), m);
+    }
     s.init(sh.prob.ic, sh.prob.x.data(), sh.prob.x.data());
     const bool inclusive = sh.prob.conv == Convention::Inclusive;
     int64_t start = 0;

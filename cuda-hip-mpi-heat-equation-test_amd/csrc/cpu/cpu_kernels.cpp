@@ -90,6 +90,39 @@ void row_var_fma_sw(const T* up, const T* mid, const T* dn, T* out, int64_t n, c
     out[j] = std::fma(rm[j], std::fma(T(-4), mid[j], sum), mid[j]);
   }
 }
+// ... the conservative form from per-face diffusion numbers: xe = RX[row] (xe[j - 1] the west
+// face), ys = RY[row], yn = RY[row - 1]; operands in the march's order S, E, N, W
+template <typename T>
+void row_div_exact(const T* up, const T* mid, const T* dn, T* out, int64_t n, const T* xe, const T* ys, const T* yn) {
+  for (int64_t j = 0; j < n; ++j) {
+    const T c = mid[j];
+    const T flux = ((ys[j] * (dn[j] - c) + xe[j] * (mid[j + 1] - c)) + yn[j] * (up[j] - c)) + xe[j - 1] * (mid[j - 1] - c);
+    out[j] = c + flux;
+  }
+}
+template <typename T>
+__attribute__((target("fma"))) void row_div_fma_hw(const T* up, const T* mid, const T* dn, T* out, int64_t n, const T* xe,
+                                                   const T* ys, const T* yn) {
+  for (int64_t j = 0; j < n; ++j) {
+    const T c = mid[j];
+    T p = ys[j] * (dn[j] - c);
+    p = std::fma(xe[j], mid[j + 1] - c, p);
+    p = std::fma(yn[j], up[j] - c, p);
+    p = std::fma(xe[j - 1], mid[j - 1] - c, p);
+    out[j] = c + p;
+  }
+}
+template <typename T>
+void row_div_fma_sw(const T* up, const T* mid, const T* dn, T* out, int64_t n, const T* xe, const T* ys, const T* yn) {
+  for (int64_t j = 0; j < n; ++j) {
+    const T c = mid[j];
+    T p = ys[j] * (dn[j] - c);
+    p = std::fma(xe[j], mid[j + 1] - c, p);
+    p = std::fma(yn[j], up[j] - c, p);
+    p = std::fma(xe[j - 1], mid[j - 1] - c, p);
+    out[j] = c + p;
+  }
+}
 // arith 2 (r == 1/4): the centre weight 1 - 4r is zero, r * sum (r*x exact)
 template <typename T>
 void row_jacobi(const T* up, const T* mid, const T* dn, T* out, int64_t n, T r) {
@@ -135,9 +168,12 @@ void ins_cols_impl(T* f, const SlabLayout& L, int64_t r0, int64_t r1) {
 // rm (a diffusivity map in the field's layout, Dirichlet axes only): the
 // multiplier of an owned point's update is its element of rm instead of r (the
 // device march's tb_impl.hpp March VAR); pinned points are copied.
+// fx, fy (per-face diffusion numbers in the field's layout, Dirichlet axes only):
+// the conservative form, an owned point's flux from its four faces (the device
+// march's tb_impl.hpp March DIV); pinned points are copied.
 template <typename T>
 void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re, int k, T r, int arith, int bc,
-             const T* q = nullptr, const T* rm = nullptr) {
+             const T* q = nullptr, const T* rm = nullptr, const T* fx = nullptr, const T* fy = nullptr) {
   const SlabLayout L = kern::bc_layout(L0, bc & kern::kBcPeriodicX);  // (the columns: free_cols below)
   const bool free_cols = (bc & kern::kBcPeriodicY) != 0;
   const bool ins_x = (bc & kern::kBcInsulatedX) != 0, ins_y = (bc & kern::kBcInsulatedY) != 0;
@@ -177,6 +213,12 @@ void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re,
         T* out = b + li * P + c - g;
         if (row < fixed_lo || row >= fixed_hi) {
           std::memcpy(out, mid, sizeof(T) * (size_t)(L.ncols + 2 * g));
+          continue;
+        }
+        if (fx) {
+          const T *xe = fx + L.offset(row, 0), *ys = fy + L.offset(row, 0), *yn = fy + L.offset(row - 1, 0);
+          if (arith == 1) (host_has_fma() ? row_div_fma_hw<T> : row_div_fma_sw<T>)(up, mid, dn, out, L.ncols, xe, ys, yn);
+          else row_div_exact<T>(up, mid, dn, out, L.ncols, xe, ys, yn);
           continue;
         }
         if (rm) {
@@ -282,7 +324,7 @@ int num_threads() {
 }
 
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end,
-        int k, double r, int arith, int bc, const void* source, const void* rmap) {
+        int k, double r, int arith, int bc, const void* source, const void* rmap, const void* rx, const void* ry) {
   HEAT2D_REQUIRE(k >= 1 && k <= L.halo, "k out of range");
   HEAT2D_REQUIRE(arith >= 0 && arith <= 3, "arith must be 0, 1, 2 or 3");
   HEAT2D_REQUIRE(arith != 2 || r == 0.25, "arith 2 (jacobi) needs r == 1/4 exactly");
@@ -295,14 +337,20 @@ void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_b
                  "a heat source needs arith 0 (exact) or 1 (fma) and Dirichlet boundaries on both axes");
   HEAT2D_REQUIRE(!rmap || ((arith == 0 || arith == 1) && bc == 0 && !source),
                  "a diffusivity map needs arith 0 (exact) or 1 (fma), Dirichlet boundaries on both axes and no heat source");
+  HEAT2D_REQUIRE((rx != nullptr) == (ry != nullptr), "face coefficients need both buffers (rx and ry)");
+  HEAT2D_REQUIRE(!rx || ((arith == 0 || arith == 1) && bc == 0 && !source && !rmap),
+                 "face coefficients need arith 0 (exact) or 1 (fma), Dirichlet boundaries on both axes, no heat source and "
+                 "no diffusivity map");
   if (arith == 3) arith = 1;
   if (row_end <= row_begin) return;
   if (dt == DType::F32)
     tb_impl<float>(static_cast<const float*>(src), static_cast<float*>(dst), L, row_begin, row_end, k, (float)r, arith, bc,
-                   static_cast<const float*>(source), static_cast<const float*>(rmap));
+                   static_cast<const float*>(source), static_cast<const float*>(rmap), static_cast<const float*>(rx),
+                   static_cast<const float*>(ry));
   else
     tb_impl<double>(static_cast<const double*>(src), static_cast<double*>(dst), L, row_begin, row_end, k, r, arith, bc,
-                    static_cast<const double*>(source), static_cast<const double*>(rmap));
+                    static_cast<const double*>(source), static_cast<const double*>(rmap), static_cast<const double*>(rx),
+                    static_cast<const double*>(ry));
 }
 
 void init(DType dt, void* field, const SlabLayout& L, const kern::IcParams& ic, const double* xc,

@@ -38,6 +38,8 @@ typedef struct heat2d_config {
   int32_t bc_x, bc_y; /* boundary condition of the row / column axis: 0 dirichlet, 1 periodic, 2 insulated */
   int32_t source; /* 1: the solver carries a heat source (heat2d_solver_set_source) */
   int32_t rmap;   /* 1: the solver carries a diffusivity map (heat2d_solver_set_rmap) */
+  int32_t faces;  /* 1: the solver carries per-face diffusion numbers (heat2d_solver_set_faces) */
+  int32_t pad1;
 } heat2d_config;
 
 typedef struct heat2d_tb_plan {
@@ -200,6 +202,23 @@ int heat2d_tb_var(int dtype, const void* src, void* dst, const heat2d_layout* L,
                   void* stream, int64_t tile_rows, int arith, const void* rmap);
 int heat2d_cpu_tb_var(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                       int arith, const void* rmap);
+/* The per-face diffusion numbers of a solver created with config.faces = 1 (the conservative form
+   u_t = div(k grad u)): `rx`, `ry` are the GLOBAL frame-inclusive arrays (nrows_global + 2) x (ncols + 2)
+   in the field's dtype, already multiplied by dt / dx^2: rx[i][j] the face between (i, j) and (i, j+1)
+   (used for i = 1..n, j = 0..n), ry[i][j] the face between (i, j) and (i+1, j) (used for i = 0..n,
+   j = 1..n); used entries finite and >= 0; the rank copies its own rows. One step is
+   T' = C + (((ry[i][j]*(S-C) + rx[i][j]*(E-C)) + ry[i-1][j]*(N-C)) + rx[i][j-1]*(W-C)) at every fused
+   level; a zero face is a wall. rx = ry = NULL returns to the scalar r. Between steps. */
+int heat2d_solver_set_faces(void* s, const void* rx, const void* ry, int64_t ld);
+/* out3 = {config.faces, faces are set, the deepest pass with faces (kMaxTBDiv)} */
+int heat2d_solver_faces(void* s, int32_t* out3);
+/* heat2d_tb / heat2d_cpu_tb with face-coefficient buffers in the field's layout (+0.0 in pad entries and
+   rows outside the grid; the faces next to the frame kept in frame column -1 of rx and frame row -1 of
+   ry): Dirichlet axes, arith 0 / 1, k <= kMaxTBDiv on the device */
+int heat2d_tb_div(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                  void* stream, int64_t tile_rows, int arith, const void* rx, const void* ry);
+int heat2d_cpu_tb_div(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                      int arith, const void* rx, const void* ry);
 /* any rectangle of the current field, local rows [r0, r1) x columns [c0, c1), ghost / frame included */
 int heat2d_solver_download_region(void* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, void* host, int64_t ld);
 // memory-fit planner (runtime.hpp solver_footprint / plan_max_grid): out3 =
@@ -211,6 +230,8 @@ int heat2d_plan_max_grid(int dtype, int nranks, int64_t budget_bytes, int64_t* n
 int heat2d_plan_max_grid_src(int dtype, int nranks, int64_t budget_bytes, int source, int64_t* n);
 /* ... and / or a diffusivity map (rmap = 1: one more field buffer) */
 int heat2d_plan_max_grid_ext(int dtype, int nranks, int64_t budget_bytes, int source, int rmap, int64_t* n);
+/* ... and / or face coefficients (faces = 1: two more field buffers) */
+int heat2d_plan_max_grid_faces(int dtype, int nranks, int64_t budget_bytes, int source, int rmap, int faces, int64_t* n);
 // hipMemGetInfo of device
 int heat2d_mem_info(int device, int64_t* free_bytes, int64_t* total_bytes);
 // s's current field, local rows [r0, r0 + nrows), against other's, rows
@@ -252,6 +273,8 @@ int heat2d_group_upload_field(void* g, const void* host, int64_t ld);
 int heat2d_group_set_source(void* g, const void* host, int64_t ld);
 /* heat2d_solver_set_rmap on every member */
 int heat2d_group_set_rmap(void* g, const void* host, int64_t ld);
+/* heat2d_solver_set_faces on every member */
+int heat2d_group_set_faces(void* g, const void* rx, const void* ry, int64_t ld);
 /* whole global owned region -> the members' slabs, then a loopback halo exchange */
 int heat2d_group_upload(void* g, const void* host, int64_t ld);
 /* member i's solver (borrowed handle: valid while the group lives; plan / info / hist queries) */

@@ -25,12 +25,17 @@ struct Meta {
   std::string source_sha256;
   // the run's diffusivity map, recorded the same way; empty: none (the key is absent)
   std::string rmap_sha256;
+  // the run's face coefficients (both arrays, RX then RY), recorded the same way; empty: none (the key is absent)
+  std::string faces_sha256;
   std::string dir;  // read_meta: the directory holding this step's files
 };
 // A heat source file (--source FILE.npy): a 2-D little-endian f4 / f8 array of exactly rows x cols
 // (the frame-inclusive grid; another shape fails), converted to `dtype` (0 fp32, 1 fp64). *sha256
 // receives the digest of the converted bytes (Meta::source_sha256).
 std::vector<char> read_source(const std::string& path, int64_t rows, int64_t cols, int dtype, std::string* sha256);
+// A face-coefficient file (--faces FILE.npy): a 3-D little-endian f4 / f8 array of exactly 2 x rows x cols
+// (RX, then RY), converted to `dtype`; *sha256 receives the digest of the converted bytes (Meta::faces_sha256).
+std::vector<char> read_faces(const std::string& path, int64_t rows, int64_t cols, int dtype, std::string* sha256);
 // SHA-256 of a byte range, lower-case hex
 std::string sha256_hex(const void* data, size_t bytes);
 

@@ -60,6 +60,9 @@ constexpr int kMaxTBSrc = 16;
 // Deepest pass with a diffusivity map (tb_kernel_var: depths 1..kMaxTBVar, both
 // dtypes, exact and fma, none with scratch; a solver with a map clamps to it).
 constexpr int kMaxTBVar = 16;
+// Deepest pass of the conservative form (tb_kernel_div: depths 1..kMaxTBDiv, both
+// dtypes, exact and fma, none with scratch; a solver with face coefficients clamps to it).
+constexpr int kMaxTBDiv = 16;
 // Default halo depth (ghost rows per side). Must be >= temporal depth used.
 constexpr int64_t kDefaultHalo = kMaxTB;
 

@@ -119,13 +119,24 @@ void launch_ins_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool h
 // pinning, and a 0 at an owned point holds that point. With a map every rect of
 // the launch runs tb_kernel_var (tb_impl.hpp): Dirichlet on both axes, arith
 // 0 / 1, depths 1..kMaxTBVar, no wave-pair plans, not together with a source.
+// rx, ry (optional, after rmap; both or neither): the per-face diffusion numbers
+// of the conservative form div(k grad u) in the field's layout and dtype — rx at
+// (i, j) the face between (i, j) and (i, j+1), ry the face between (i, j) and
+// (i+1, j) —, T' = C + (((ry*(S-C) + rx*(E-C)) + ry[i-1]*(N-C)) + rx[j-1]*(W-C))
+// at every fused level; `r` is then not used. They hold +0.0 in every pad entry
+// and row outside the grid and keep the faces next to the frame (frame column
+// -1 of rx, frame row -1 of ry). With faces every rect of the launch runs
+// tb_kernel_div (tb_impl.hpp): Dirichlet on both axes, arith 0 / 1, depths
+// 1..kMaxTBDiv, no wave-pair plans, not together with a source or a map.
 void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
                int64_t row_end, int k, double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0,
-               int arith = 0, int bc = 0, const void* source = nullptr, const void* rmap = nullptr);
+               int arith = 0, int bc = 0, const void* source = nullptr, const void* rmap = nullptr,
+               const void* rx = nullptr, const void* ry = nullptr);
 // Same for TWO disjoint row ranges [rb0, re0) and [rb1, re1) in one launch.
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
                 int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0,
-                int arith = 0, int bc = 0, const void* source = nullptr, const void* rmap = nullptr);
+                int arith = 0, int bc = 0, const void* source = nullptr, const void* rmap = nullptr,
+                const void* rx = nullptr, const void* ry = nullptr);
 
 // Split schedule of one cycle (k steps over the whole slab) into two launches
 // on two streams:
@@ -203,11 +214,12 @@ bool edges_on_main(const SlabLayout& L, const SplitPlan& p);
 bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i);
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
                       hipStream_t stream, int arith = 0, int bc = 0, const void* source = nullptr,
-                      const void* rmap = nullptr);
+                      const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr);
 // queue: 2 device counters (zeroed once) for plans with flags & kPlanDynamic (dynamic items)
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
                   double r, hipStream_t stream, int arith = 0, uint32_t* queue = nullptr, int bc = 0,
-                  const void* source = nullptr, const void* rmap = nullptr);
+                  const void* source = nullptr, const void* rmap = nullptr, const void* rx = nullptr,
+                  const void* ry = nullptr);
 
 // Initial / boundary condition kinds (covers every IC of the reference
 // variants, see models/presets.py for the mapping).

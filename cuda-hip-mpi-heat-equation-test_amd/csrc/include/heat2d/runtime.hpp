@@ -77,6 +77,13 @@ struct SolverConfig {
   // (auto resolves to exact), engine "tb", no copy_swap, no source; the depth
   // is clamped to kMaxTBVar. 0: one r, today's solver.
   int32_t rmap;
+  // 1: the solver carries per-face diffusion numbers (u_t = div(k grad u), the
+  // conservative form): two more buffers in the field's layout, filled by
+  // Solver::set_faces (kernels.hpp launch_tb `rx`, `ry`). Dirichlet on both
+  // axes, arith exact / fma (auto resolves to exact), engine "tb", no
+  // copy_swap, no source, no rmap; the depth is clamped to kMaxTBDiv. 0: today's solver.
+  int32_t faces;
+  int32_t pad1;
 };
 constexpr int32_t kBcDirichlet = 0, kBcPeriodic = 1, kBcInsulated = 2;
 // the kernels' bit set (kernels.hpp kBcPeriodicX / ... / kBcInsulatedY) of a config
@@ -261,7 +268,7 @@ std::shared_ptr<Transport> make_ipc_loop_transport(int device);
 namespace cpu {
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
         int64_t row_end, int k, double r, int arith = 0, int bc = 0, const void* source = nullptr,
-        const void* rmap = nullptr);
+        const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr);
 void wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1);
 void wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k);
 // insulated frame images (kern::launch_ins_cols / launch_ins_rows)
@@ -344,8 +351,9 @@ Footprint solver_footprint(const SolverConfig& cfg, int rank, int nranks);
 // on the device, so only the two device fields count (three with a heat
 // source: SolverConfig::source).
 // (or a diffusivity map: SolverConfig::rmap)
+// (or face coefficients, two more: SolverConfig::faces)
 int64_t plan_max_grid(int dtype, int nranks, int64_t budget_bytes, int64_t halo = 0, bool source = false,
-                      bool rmap = false);
+                      bool rmap = false, bool faces = false);
 
 class Solver {
  public:
@@ -453,6 +461,18 @@ class Solver {
   // to the scalar-r kernels. Between step() calls; drops the captured graphs.
   void set_rmap(const void* host, int64_t ld);
   bool has_rmap() const { return rmap_on_; }
+  // The per-face diffusion numbers (SolverConfig::faces = 1): `rx` and `ry` are
+  // the GLOBAL frame-inclusive arrays, (nrows_global + 2) x (ncols + 2) in the
+  // field's dtype, leading dimension ld, already multiplied by dt / dx^2:
+  // rx[i][j] the face between (i, j) and (i, j+1) (used for i = 1..n, j = 0..n),
+  // ry[i][j] the face between (i, j) and (i+1, j) (used for i = 0..n, j = 1..n).
+  // This rank copies its rows, ghost rows included (never exchanged). Used
+  // entries must be finite and >= 0; the others are ignored: the solver's
+  // copies hold +0.0 in every pad entry and row outside the grid and keep the
+  // faces next to the frame. Both nullptr returns to the scalar-r kernels.
+  // Between step() calls; drops the captured graphs.
+  void set_faces(const void* rx, const void* ry, int64_t ld);
+  bool has_faces() const { return faces_on_; }
   // Cycles launched by step() since the last reset, by depth: hist[k] for
   // k = 0..kMaxTB (graph replays count their two cycles each).
   void cycle_hist(int64_t out[kMaxTB + 1], bool reset);
@@ -556,6 +576,10 @@ class Solver {
   void* rmap_buf_ = nullptr;  // the diffusivity map (cfg_.rmap), in L_'s layout
   bool rmap_on_ = false;      // set_rmap has filled it
   const void* rmap() const { return rmap_on_ ? rmap_buf_ : nullptr; }
+  void* face_buf_[2] = {nullptr, nullptr};  // the face coefficients rx, ry (cfg_.faces), in L_'s layout
+  bool faces_on_ = false;                   // set_faces has filled them
+  const void* face_rx() const { return faces_on_ ? face_buf_[0] : nullptr; }
+  const void* face_ry() const { return faces_on_ ? face_buf_[1] : nullptr; }
   void drop_graphs();         // captured graphs hold the kernels of the run with / without a source or map
   int cur_ = 0;
   int64_t steps_ = 0;
@@ -640,6 +664,7 @@ class LoopbackGroup {
   void upload_field(const void* host, int64_t ld);
   void set_source(const void* host, int64_t ld);  // Solver::set_source on every member (the global array)
   void set_rmap(const void* host, int64_t ld);    // Solver::set_rmap on every member (the global array)
+  void set_faces(const void* rx, const void* ry, int64_t ld);  // Solver::set_faces on every member (the global arrays)
   int nranks() const { return (int)members_.size(); }
   Solver& member(int i) { return *members_[i]; }
 

@@ -305,6 +305,13 @@ int occupancy_var(DType dt, int k, int arith) {
   return dt == DType::F32 ? occupancy_waves_var<float, 0>(k) : occupancy_waves_var<double, 0>(k);
 }
 
+// Conservative form (tb_kernel_div): resident waves per CU (one-wave workgroups)
+int occupancy_div(DType dt, int k, int arith) {
+  HEAT2D_REQUIRE(arith == 0 || arith == 1, "face coefficients need arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 assume one r");
+  if (arith == 1) return dt == DType::F32 ? occupancy_waves_div<float, 1>(k) : occupancy_waves_div<double, 1>(k);
+  return dt == DType::F32 ? occupancy_waves_div<float, 0>(k) : occupancy_waves_div<double, 0>(k);
+}
+
 // The frame entries the launchers keep behind a stencil launch over `rects`:
 // periodic y the ghost columns, insulated y the frame columns, insulated x the
 // frame row of a slab at the wall — one fill per run of rows the rects cover
@@ -355,7 +362,20 @@ void fill_frames(DType dt, void* dst, const SlabLayout& L0, const TbRect* rects,
 int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
                        const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
                        double* partials, uint32_t* queue, int bc, bool pipe, const void* source = nullptr,
-                       const void* rmap = nullptr) {
+                       const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr) {
+  // rx / ry != nullptr (the per-face diffusion numbers in the field's layout; Dirichlet axes only):
+  // every launch, interior ones too, runs tb_kernel_div (ring 4, the general kernel's four edge kinds)
+  // on at most as many waves as that kernel keeps resident; `r` is not used.
+  const bool faces = rx || ry;
+  if (faces) {
+    HEAT2D_REQUIRE(rx && ry, "face coefficients need both buffers (rx and ry)");
+    HEAT2D_REQUIRE(!source && !rmap, "face coefficients with a heat source or a diffusivity map: no kernel carries them together");
+    HEAT2D_REQUIRE(bc == 0, "face coefficients need Dirichlet boundaries on both axes");
+    HEAT2D_REQUIRE(!partials && !pipe, "face coefficients have no fused-statistics and no wave-pair kernel");
+    HEAT2D_REQUIRE(k <= kMaxTBDiv, "temporal depth exceeds the conservative-form kernels' deepest pass (kMaxTBDiv)");
+    nwaves = std::min<int64_t>(nwaves, (int64_t)cu_count() * occupancy_div(dt, k, arith));
+    main = false;
+  }
   // rmap != nullptr (the per-point diffusion number in the field's layout, +0.0 at every pinned
   // point; Dirichlet axes only): every launch, interior ones too, runs tb_kernel_var (ring 4) on at
   // most as many waves as that kernel keeps resident; `r` is not used.
@@ -416,7 +436,7 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
   a.partials = partials;
   // (the pair kernel and the heat-source kernel record no wave times: HEAT2D_WAVE_TIMES keeps
   // the last other launch's)
-  a.wtimes = (pipe || source || rmap) ? nullptr : wave_times_buf(a.nwaves);  // (nor the diffusivity-map kernel)
+  a.wtimes = (pipe || source || rmap || faces) ? nullptr : wave_times_buf(a.nwaves);  // (nor the map / face kernels)
   if (arith == 3) {  // scaled levels (tb_impl.hpp AR 3): coefficients of this depth, in double
     HEAT2D_REQUIRE(r > 0.0, "arith 3 (fast) needs r > 0");
     a.fb = (1.0 - 4.0 * r) / r;
@@ -435,6 +455,18 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
       dispatch_pipe<decltype(ar)::value>(k, (unsigned)((a.nwaves + 1) / 2), static_cast<const double*>(src) + o,
                                          static_cast<double*>(dst) + o, a, r, status, stream);
     });
+  } else if (faces) {
+    if (dt == DType::F32) {
+      const float *s32 = static_cast<const float*>(src) + o, *x32 = static_cast<const float*>(rx) + o,
+                  *y32 = static_cast<const float*>(ry) + o;
+      if (arith == 1) dispatch_div<float, 1>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, x32, y32, stream);
+      else dispatch_div<float, 0>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, x32, y32, stream);
+    } else {
+      const double *s64 = static_cast<const double*>(src) + o, *x64 = static_cast<const double*>(rx) + o,
+                   *y64 = static_cast<const double*>(ry) + o;
+      if (arith == 1) dispatch_div<double, 1>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, x64, y64, stream);
+      else dispatch_div<double, 0>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, x64, y64, stream);
+    }
   } else if (rmap) {
     if (dt == DType::F32) {
       const float *s32 = static_cast<const float*>(src) + o, *m32 = static_cast<const float*>(rmap) + o;
@@ -499,17 +531,19 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
 int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
                      const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
                      double* partials = nullptr, uint32_t* queue = nullptr, int bc = 0, bool pipe = false,
-                     const void* source = nullptr, const void* rmap = nullptr) {
+                     const void* source = nullptr, const void* rmap = nullptr, const void* rx = nullptr,
+                     const void* ry = nullptr) {
   HEAT2D_REQUIRE((bc & ~kBcAll) == 0, "bc must be a set of kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY");
   HEAT2D_REQUIRE(!((bc & kBcPeriodicX) && (bc & kBcInsulatedX)) && !((bc & kBcPeriodicY) && (bc & kBcInsulatedY)),
                  "an axis is periodic or insulated, not both");
   if (!(main && (bc & kBcInsulatedY))) {
     const int64_t nw = launch_rects_1(dt, src, dst, L0, k, ring, main, rects, nrect, nwaves, r, stream, arith, partials,
-                                      queue, bc, pipe, source, rmap);
+                                      queue, bc, pipe, source, rmap, rx, ry);
     fill_frames(dt, dst, L0, rects, nrect, bc, stream);
     return nw;
   }
-  HEAT2D_REQUIRE(!source && !rmap, "a heat source / diffusivity map needs Dirichlet boundaries on both axes");
+  HEAT2D_REQUIRE(!source && !rmap && !rx && !ry,
+                 "a heat source / diffusivity map / face coefficients need Dirichlet boundaries on both axes");
   HEAT2D_REQUIRE(!pipe, "insulated y: the wave-pair kernel's wide strips are not carved (no pipe plans)");
   HEAT2D_REQUIRE(nrect >= 1 && nrect <= kMainRects, "bad rect count");
   const int64_t U = useful_width(dt, k);
@@ -595,13 +629,13 @@ TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end
 
 void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end, int k,
                double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc, const void* source,
-               const void* rmap) {
-  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith, bc, source, rmap);
+               const void* rmap, const void* rx, const void* ry) {
+  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith, bc, source, rmap, rx, ry);
 }
 
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
                 int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc,
-                const void* source, const void* rmap) {
+                const void* source, const void* rmap, const void* rx, const void* ry) {
   check_layout(dt, L, k);
   const int64_t n0 = std::max<int64_t>(0, re0 - rb0), n1 = std::max<int64_t>(0, re1 - rb1);
   if (n0 + n1 == 0) return;
@@ -616,7 +650,7 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
     if (n0 > 0) rects[nr++] = TbRect{rb0, re0, 0, p.nstrips, -std::min<int64_t>(s0, n0 * p.nstrips)};
     if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, -std::min<int64_t>(std::max<int64_t>(1, ns - s0), n1 * p.nstrips)};
     launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, p.nwaves, r, stream, arith, nullptr, nullptr, bc,
-                 false, source, rmap);
+                 false, source, rmap, rx, ry);
     return;
   }
   const int64_t nb = std::max<int64_t>(p.ntiles, (n0 > 0) + (n1 > 0));
@@ -625,7 +659,7 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
   if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, std::min<int64_t>(nb - nb0, n1)};
   const int64_t slots = (int64_t)(cus > 0 ? cus : cu_count()) * p.blocks_per_cu * 4;
   launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, slots, r, stream, arith, nullptr, nullptr, bc, false,
-               source, rmap);
+               source, rmap, rx, ry);
 }
 
 // r = 1/4 kernels (arith 2): an interior item costs 3 adds + 2 DPP moves per
@@ -899,19 +933,21 @@ bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i) {
 }
 
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
-                      hipStream_t stream, int arith, int bc, const void* source, const void* rmap) {
+                      hipStream_t stream, int arith, int bc, const void* source, const void* rmap, const void* rx,
+                      const void* ry) {
   HEAT2D_REQUIRE(i >= 0 && i < p.nedge, "edge rect index");
   const TbRect& R = p.edge[i];
   const bool on_main = edges_on_main(bc_layout(L, bc), p.k, &R, 1);
   const int64_t items = R.nb > 0 ? R.nb * (R.s1 - R.s0) : -R.nb;
   const int64_t slots = (int64_t)cu_count() * occupancy(dt, p.ring, on_main, p.k, arith) * 4;
   launch_rects(dt, src, dst, L, p.k, p.ring, on_main, &R, 1, std::min<int64_t>(items, slots), r, stream, arith,
-               nullptr, nullptr, bc, false, source, rmap);
+               nullptr, nullptr, bc, false, source, rmap, rx, ry);
 }
 
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
                   double r, hipStream_t stream, int arith, uint32_t* queue, int bc, const void* source,
-                  const void* rmap) {
+                  const void* rmap, const void* rx, const void* ry) {
+  HEAT2D_REQUIRE(!(rx || ry) || !(p.flags & kPlanPipe), "face coefficients have no wave-pair kernel (no pipe plans)");
   HEAT2D_REQUIRE(!source || !(p.flags & kPlanPipe), "a heat source has no wave-pair kernel (no pipe plans)");
   HEAT2D_REQUIRE(!rmap || !(p.flags & kPlanPipe), "a diffusivity map has no wave-pair kernel (no pipe plans)");
   // (SplitPlan::flags & kPlanDynamic: the main part takes its items from the dynamic queue)
@@ -923,15 +959,15 @@ void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, con
   if (p.valid == 2) {  // single general launch over the whole slab (no edge part)
     if (main_part)
       launch_rects(dt, src, dst, L, p.k, p.ring, false, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc, false,
-                   source, rmap);
+                   source, rmap, rx, ry);
     return;
   }
   if (main_part)
     launch_rects(dt, src, dst, L, p.k, p.ring, true, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc,
-                 (p.flags & kPlanPipe) != 0, source, rmap);
+                 (p.flags & kPlanPipe) != 0, source, rmap, rx, ry);
   else
     launch_rects(dt, src, dst, L, p.k, p.ring, edges_on_main(bc_layout(L, bc), p.k, p.edge, p.nedge), p.edge, p.nedge,
-                 p.edge_waves, r, stream, arith, nullptr, nullptr, bc, false, source, rmap);
+                 p.edge_waves, r, stream, arith, nullptr, nullptr, bc, false, source, rmap, rx, ry);
 }
 
 }  // namespace kern

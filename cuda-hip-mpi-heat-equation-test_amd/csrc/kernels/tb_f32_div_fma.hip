@@ -1,0 +1,11 @@
+// Instantiation unit: the general temporal-blocked stencil of the conservative form div(k grad u)
+// (float, ring 4, contracted fma arithmetic AR = 1; see tb_impl.hpp tb_kernel_div / March DIV).
+#include "tb_impl.hpp"
+
+namespace heat2d {
+namespace kern {
+namespace tbimpl {
+H2D_DIV_UNIT(float, 1)
+}  // namespace tbimpl
+}  // namespace kern
+}  // namespace heat2d

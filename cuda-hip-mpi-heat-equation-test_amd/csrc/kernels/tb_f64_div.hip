@@ -1,0 +1,11 @@
+// Instantiation unit: the general temporal-blocked stencil of the conservative form div(k grad u)
+// (double, ring 4, reference arithmetic AR = 0; see tb_impl.hpp tb_kernel_div / March DIV).
+#include "tb_impl.hpp"
+
+namespace heat2d {
+namespace kern {
+namespace tbimpl {
+H2D_DIV_UNIT(double, 0)
+}  // namespace tbimpl
+}  // namespace kern
+}  // namespace heat2d

@@ -390,9 +390,69 @@ struct SrcState<K, RING, true> {
 // (and a dead priming row loads as 0), and r = 0 is what the edge kinds select
 // at those points, so every kind of item runs the one march (EK 0) and has the
 // bits of the scalar kernels' kinds. A VAR march has no source (one ring).
+// DIV (tb_kernel_div, the conservative form u_t = div(k grad u) from per-face
+// diffusion numbers: RX[i,j] the face between (i,j) and (i,j+1), RY[i,j] the
+// face between (i,j) and (i+1,j), two more fields in the field's layout):
+//   flux = ((RY[i,j]*(S-C) + RX[i,j]*(E-C)) + RY[i-1,j]*(N-C)) + RX[i,j-1]*(W-C),  T' = C + flux
+// (AR 1: the three sums contracted, p = fma(face, diff, p); C + p stays an add).
+// The rows of both maps take the way the source rows take, in two wave-private
+// LDS rings of K rows each: every refill of a level-0 ring slot also loads that
+// row of RX and of RY (two more 16-B loads per march row at the same fixed
+// place) into the slot's twins Qx / Qy; the centre row m + 1 is pushed into the
+// rings. Level s on row rho = m + s needs RX[rho], RY[rho] (its partial, formed
+// while level s - 1 is updated) and RY[rho - 1] (its north face): the rows read
+// for a partial are carried in registers to the update one and two levels on,
+// so a level costs two LDS reads; level 1's RY[m] is the register twin of the
+// north slot. RX[rho, j-1] is the west lane's last element, by the DPP path
+// that brings W. Pinning is the edge kinds' with r = 1: the `re` of a point is 1
+// or 0 (x * 1 is exact; kind 0 has no multiply). The solver's copies hold +0.0
+// in every pad entry and every allocated row outside the grid (and a dead
+// priming row loads as 0) and keep the faces next to the frame. A lane reads
+// only what it wrote; one wave per workgroup: no barrier, no counter.
+// (The state lives in a base that is empty unless DIV, as WallState / SrcState.)
+template <int K, int WHICH>
+__device__ __forceinline__ char* div_ring() {
+  __shared__ unsigned int __attribute__((ext_vector_type(4))) ring[(K > 1 ? K : 1) * 64];
+  return reinterpret_cast<char*>(ring);
+}
+template <int K, int RING, bool DIV>
+struct DivState {};
+template <int K, int RING>
+struct DivState<K, RING, true> {
+  using Q4 = unsigned int __attribute__((ext_vector_type(4)));
+  static constexpr int NR = K > 1 ? K : 1;  // LDS ring rows (each ring)
+  int64_t dxdelta, dydelta;  // RX / RY row of a level-0 row pointer: its byte distance from srow
+  Q4 Qx[RING], Qy[RING];     // RX / RY rows of the level-0 ring's rows (same slots)
+  int32_t dlane;             // this lane's byte offset in an LDS row
+  int32_t dw;                // ring slot of the newest row (m + 1), in bytes  [wave-uniform]
+  __device__ __forceinline__ void d_reset(int lane) {
+    dlane = lane * 16;
+    dw = 0;
+#pragma unroll
+    for (int q = 0; q < RING; ++q) Qx[q] = Qy[q] = Q4{0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      *reinterpret_cast<Q4*>(div_ring<K, 0>() + i * 1024 + dlane) = Q4{0u, 0u, 0u, 0u};
+      *reinterpret_cast<Q4*>(div_ring<K, 1>() + i * 1024 + dlane) = Q4{0u, 0u, 0u, 0u};
+    }
+  }
+  // row m + 1 enters both rings (the slot of row m + K + 1, read last one march row ago)
+  __device__ __forceinline__ void d_push(const Q4& x, const Q4& y) {
+    dw = (dw == 0 ? NR * 1024 : dw) - 1024;
+    *reinterpret_cast<Q4*>(div_ring<K, 0>() + dw + dlane) = x;
+    *reinterpret_cast<Q4*>(div_ring<K, 1>() + dw + dlane) = y;
+  }
+  // row m + s of RX (WHICH 0) / RY (1): pushed s - 1 march rows ago
+  template <int WHICH>
+  __device__ __forceinline__ Q4 d_level(int s) const {
+    int32_t o = dw + (s - 1) * 1024;
+    o = o >= NR * 1024 ? o - NR * 1024 : o;
+    return *reinterpret_cast<const Q4*>(div_ring<K, WHICH>() + o + dlane);
+  }
+};
 template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false,
-          bool SRC = false, bool VAR = false>
-struct March : WallState<INS>, SrcState<K, RING, SRC || VAR> {
+          bool SRC = false, bool VAR = false, bool DIV = false>
+struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, DIV> {
   using S = TbShape<T, NV, K>;
   static constexpr int V = S::V;
   static constexpr int VM = S::VM;
@@ -405,6 +465,9 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR> {
   static_assert(!VAR || (NV == 1 && CL == K && (AR == 0 || AR == 1) && !ST && !SRC && !INS && EK == 0),
                 "diffusivity map: 16 B per lane, one chain, unscaled arithmetic, no statistics, source or insulated "
                 "edges; the map pins (EK 0)");
+  static_assert(!DIV || (NV == 1 && CL == K && (AR == 0 || AR == 1) && !ST && !SRC && !VAR && !INS),
+                "face coefficients: 16 B per lane, one chain, unscaled arithmetic, no statistics, source, map or "
+                "insulated edges");
 
   const char* srow;  // byte address of (row 0, column -cpad) in src   [wave-uniform]
   char* drow;        // same in dst                                      [wave-uniform]
@@ -470,6 +533,11 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR> {
     return __builtin_amdgcn_raw_buffer_load_b128(row_rsrc(p + this->qdelta, live ? nrec : 0u), ld_off, 0, 0);
   }
 
+  // DIV: the RX / RY row (delta = dxdelta / dydelta) of the level-0 row at p (same lanes; see DivState)
+  __device__ __forceinline__ U4 load_d(const char* p, bool live, int64_t delta) const {
+    return __builtin_amdgcn_raw_buffer_load_b128(row_rsrc(p + delta, live ? nrec : 0u), ld_off, 0, 0);
+  }
+
   __device__ __forceinline__ void unpack(const VT (&x)[NV], T (&out)[V]) const {
 #pragma unroll
     for (int v = 0; v < NV; ++v)
@@ -480,9 +548,20 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR> {
   // part = S + E(C): the first partial sum of the reference order, from the
   // level's oldest row S and the east neighbours of its centre row C.
   // (row: the row the sum belongs to — INS only)
-  __device__ __forceinline__ void partial(const T (&Sx)[V], const T (&C)[V], T (&part)[V], int32_t row = 0) const {
+  // (rx, ry — DIV only: the row's east and south faces; part = ry*(S-C) + rx*(E-C))
+  __device__ __forceinline__ void partial(const T (&Sx)[V], const T (&C)[V], T (&part)[V], int32_t row = 0,
+                                          const VT* rx = nullptr, const VT* ry = nullptr) const {
     const T eastL = from_upper(C[0]);
-    if constexpr (INS) {
+    if constexpr (DIV) {
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        const T ds = Sx[e] - C[e];
+        const T de = (e < V - 1 ? C[e + 1] : eastL) - C[e];
+        const T p = (*ry)[e] * ds;
+        if constexpr (AR == 1) part[e] = fma_t((*rx)[e], de, p);
+        else part[e] = p + (*rx)[e] * de;
+      }
+    } else if constexpr (INS) {
       const bool swall = (EK & 1) && row == this->wall_hi;  // wave-uniform
 #pragma unroll
       for (int e = 0; e < V; ++e) {
@@ -499,10 +578,29 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR> {
   // ((part + N) + W) then C + r*(sum - 4C), pinned columns / rows kept.
   // (rv — VAR only: the map's elements of this row, the r of each element)
   __device__ __forceinline__ void update(const T (&part)[V], const T (&C)[V], const T (&N)[V], int32_t row,
-                                         T (&out)[V], const VT* rv = nullptr) const {
+                                         T (&out)[V], const VT* rv = nullptr, const VT* ryn = nullptr) const {
     const T west0 = from_lower(C[V - 1]);
     const bool frame_row = (EK & 1) && ((uint32_t)(row - fixed_lo) >= (uint32_t)(fixed_hi - fixed_lo));  // wave-uniform
     const T rs = frame_row ? T(0) : r;                                      // EK 1: scalar select
+    if constexpr (DIV) {
+      // rv: the row's east faces RX[row] (the west face of element 0 is the west lane's last
+      // element), ryn: the north faces RY[row - 1]; r is 1, so re is 1 or 0
+      const T xw0 = from_lower((*rv)[V - 1]);
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        const T dn = N[e] - C[e];
+        const T dw = (e > 0 ? C[e - 1] : west0) - C[e];
+        const T xw = e > 0 ? (*rv)[e - 1] : xw0;
+        T flux;
+        if constexpr (AR == 1) flux = fma_t(xw, dw, fma_t((*ryn)[e], dn, part[e]));
+        else flux = (part[e] + (*ryn)[e] * dn) + xw * dw;
+        if constexpr (EK == 0) out[e] = C[e] + flux;
+        else if constexpr (EK == 1) out[e] = C[e] + rs * flux;
+        else if constexpr (EK == 2) out[e] = C[e] + rl[e] * flux;
+        else out[e] = C[e] + (frame_row ? T(0) : rl[e]) * flux;
+      }
+      return;
+    }
 #pragma unroll
     for (int e = 0; e < V; ++e) {
       T west = e > 0 ? C[e - 1] : west0;
@@ -551,11 +649,21 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR> {
     T part[V];
     T C0[V], N0[V];
     if constexpr (SRC || VAR) this->q_push(this->Qb[sC]);  // source / map row m + 1 (loaded beside the centre row)
+    // DIV: faces carried from a level's partial to its update: RX / RY of the level's row, RY of the row above
+    VT fx_c = VT{}, fy_c = VT{}, fy_p = VT{};
+    if constexpr (DIV) {
+      // (PRIME skips only the deepest levels, the tail of the carry chain)
+      this->d_push(this->Qx[sC], this->Qy[sC]);  // rows m + 1 of RX / RY
+      fx_c = __builtin_bit_cast(VT, this->Qx[sC]);
+      fy_c = __builtin_bit_cast(VT, this->Qy[sC]);
+      fy_p = __builtin_bit_cast(VT, this->Qy[sN]);  // RY[m]: level 1's north faces
+    }
     {
       T S0[V];
       unpack(Lb[sS], S0);
       unpack(Lb[sC], C0);
-      partial(S0, C0, part, m + Ch::off(1));  // level 1's S+E
+      if constexpr (DIV) partial(S0, C0, part, m + Ch::off(1), &fx_c, &fy_c);
+      else partial(S0, C0, part, m + Ch::off(1));  // level 1's S+E
     }
     {  // row m+2 is dead: refill its slot with row m+2-RING (clamped: a harmless re-read).
       // The scheduling fence keeps the load below the slot's last use: hoisted
@@ -566,10 +674,15 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR> {
       if constexpr (kIncPtr) {
         load_row_p(lp, nxt >= mload, Lb[sS]);
         if constexpr (SRC || VAR) this->Qb[sS] = load_q(lp, nxt >= mload);
+        if constexpr (DIV) {
+          this->Qx[sS] = load_d(lp, nxt >= mload, this->dxdelta);
+          this->Qy[sS] = load_d(lp, nxt >= mload, this->dydelta);
+        }
         lp -= pitch_b;
       } else {
         load_row(nxt >= mload ? nxt : mload, Lb[sS]);
         if constexpr (SRC || VAR) this->Qb[sS] = load_q(srow + (int64_t)(nxt >= mload ? nxt : mload) * pitch_b, true);
+        static_assert(!DIV || kIncPtr, "the face march keeps the stepped row pointers (depths <= 16)");
       }
     }
     unpack(Lb[sN], N0);
@@ -590,8 +703,20 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR> {
       }
       const int ps = Ch::slot(PH, 0, s < K ? s : 1);  // this level's slot of this iteration
       // level s+1's S+E from level s's S (the slot about to be overwritten) and C
-      if (s < K) partial(X[ps][s - 1], X[Ch::slot(PH, Ch::delta(s + 1), s)][s - 1], nxtpart, m + Ch::off(s + 1));
-      if constexpr (VAR) {  // R(row m + off(s)) is this level's multiplier
+      VT fx_n = VT{}, fy_n = VT{};
+      if constexpr (DIV) {
+        if (s < K) {  // rows m + s + 1 of RX / RY: the next level's partial, then its update
+          fx_n = __builtin_bit_cast(VT, this->template d_level<0>(s + 1));
+          fy_n = __builtin_bit_cast(VT, this->template d_level<1>(s + 1));
+          partial(X[ps][s - 1], X[Ch::slot(PH, Ch::delta(s + 1), s)][s - 1], nxtpart, m + Ch::off(s + 1), &fx_n, &fy_n);
+        }
+        update(part, C, N, m + Ch::off(s), out, &fx_c, &fy_p);
+        fy_p = fy_c;
+        fx_c = fx_n;
+        fy_c = fy_n;
+      } else if (s < K) partial(X[ps][s - 1], X[Ch::slot(PH, Ch::delta(s + 1), s)][s - 1], nxtpart, m + Ch::off(s + 1));
+      if constexpr (DIV) {
+      } else if constexpr (VAR) {  // R(row m + off(s)) is this level's multiplier
         const VT rv = __builtin_bit_cast(VT, this->q_level(s));
         update(part, C, N, m + Ch::off(s), out, &rv);
       } else {
@@ -668,6 +793,14 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR> {
 #pragma unroll
       for (int q = 0; q < RING - 2; ++q)
         this->Qb[q] = load_q(srow + (int64_t)(mtop - q >= mload ? mtop - q : mload) * pitch_b, true);
+    }
+    if constexpr (DIV) {
+#pragma unroll
+      for (int q = 0; q < RING - 2; ++q) {
+        const char* p = srow + (int64_t)(mtop - q >= mload ? mtop - q : mload) * pitch_b;
+        this->Qx[q] = load_d(p, true, this->dxdelta);
+        this->Qy[q] = load_d(p, true, this->dydelta);
+      }
     }
 #pragma unroll
     for (int p = 0; p < 3; ++p)
@@ -1040,10 +1173,10 @@ constexpr bool kPackedF32 = false;
 constexpr int kInsRowLo = 1, kInsRowHi = 2, kInsColLo = 4, kInsColHi = 8;
 
 template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, bool PS = false, int CLX = 0,
-          bool INS = false, bool SRC = false, bool VAR = false>
+          bool INS = false, bool SRC = false, bool VAR = false, bool DIV = false>
 __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r, int64_t strip, int64_t t0,
                                       int64_t t1, int lane, StatAcc* acc = nullptr, int ins = 0,
-                                      const T* qsrc = nullptr) {
+                                      const T* qsrc = nullptr, const T* qsrc2 = nullptr) {
   using S = TbShape<T, NV, K>;
   constexpr int V = S::V;
   constexpr int ES = (int)sizeof(T);
@@ -1055,8 +1188,10 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
   // the chains' extra rows spill at fp64 K >= 21
   // (CLX > 0: an explicit chain length — the boundary-band kernel)
   constexpr int CL = CLX > 0 ? (CLX < K ? CLX : K) : (ST ? K : chain_len<T, K>());
-  using W = typename std::conditional<kPackedF32<T, NV>, MarchF32<K, EK, RING, AR, ST, CL, INS, SRC, VAR>,
-                                      March<T, NV, K, EK, RING, AR, ST, CL, INS, SRC, VAR>>::type;
+  // (DIV: the element-wise march in both dtypes)
+  constexpr bool kPacked = kPackedF32<T, NV> && !DIV;
+  using W = typename std::conditional<kPacked, MarchF32<K, EK, RING, AR, ST, CL, INS, SRC, VAR>,
+                                      March<T, NV, K, EK, RING, AR, ST, CL, INS, SRC, VAR, DIV>>::type;
   W w;
   // row base = column col_lo (= -cpad) of row 0; offsets are relative to it
   w.srow = reinterpret_cast<const char*>(src + a.col_lo);
@@ -1087,7 +1222,7 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
   w.st_off = useful && in_alloc ? off : kOob;
   if constexpr ((EK & 2) != 0) {
     auto rcol = [&](int e) { return (mycol + e < 0 || mycol + e >= a.ncols) ? T(0) : r; };
-    if constexpr (kPackedF32<T, NV>) {
+    if constexpr (kPacked) {
       w.rl.a = {rcol(0), rcol(2)};
       w.rl.b = {rcol(1), rcol(3)};
     } else {
@@ -1110,6 +1245,11 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
     w.qrow = reinterpret_cast<const char*>(qsrc + a.col_lo);
     w.qdelta = w.qrow - w.srow;
     w.q_reset(lane);
+  }
+  if constexpr (DIV) {  // RX (qsrc) and RY (qsrc2) have the field's layout
+    w.dxdelta = reinterpret_cast<const char*>(qsrc + a.col_lo) - w.srow;
+    w.dydelta = reinterpret_cast<const char*>(qsrc2 + a.col_lo) - w.srow;
+    w.d_reset(lane);
   }
   if constexpr (ST) {
     uint32_t mask = 0;
@@ -1427,6 +1567,43 @@ __global__ __launch_bounds__(64) void tb_kernel_var(const T* __restrict__ src, T
   queue_exit(a);
 }
 
+// The general kernel of the conservative form (`rx`, `ry`: the per-face
+// diffusion numbers in the field's layout, arguments of this kernel only —
+// TbArgs and every other kernel stay as they are; the scalar r is not an
+// argument: the marches run with r = 1, the `re` of a point 1 or 0). The same
+// items and kinds as the general kernel (March DIV). One wave per workgroup:
+// the wave's two rings of K face rows in LDS (2 K KiB) are the workgroup's
+// whole allocation; nothing waits on another wave.
+template <typename T, int NV, int K, int RING, int AR>
+__global__ __launch_bounds__(64) void tb_kernel_div(const T* __restrict__ src, T* __restrict__ dst, TbArgs a,
+                                                    const T* __restrict__ rx, const T* __restrict__ ry) {
+  using S = TbShape<T, NV, K>;
+  const int lane = threadIdx.x;
+  const int64_t wid = (int64_t)blockIdx.x;
+  if (wid >= a.nwaves) return;
+  int64_t it = wid;
+  int32_t lin = tb_span<kMaxRects>(a, it).lin;
+  while (it < a.nitems) {
+    int64_t strip, t0, t1;
+    if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {
+      it = next_item(a, it);
+      if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;
+      continue;
+    }
+    lin += (int32_t)(t1 - t0);
+    const int64_t c0 = strip * S::U - S::KA;
+    const int ek = (((t0 - K < a.fixed_lo) || (t1 + K > a.fixed_hi)) ? 1 : 0) |
+                   (((c0 < 0) || (c0 + S::W > a.ncols)) ? 2 : 0);
+    switch (ek) {
+      case 0: march<T, NV, K, 0, RING, AR, false, false, K, false, false, false, true>(src, dst, a, T(1), strip, t0, t1, lane, nullptr, 0, rx, ry); break;
+      case 1: march<T, NV, K, 1, RING, AR, false, false, K, false, false, false, true>(src, dst, a, T(1), strip, t0, t1, lane, nullptr, 0, rx, ry); break;
+      case 2: march<T, NV, K, 2, RING, AR, false, false, K, false, false, false, true>(src, dst, a, T(1), strip, t0, t1, lane, nullptr, 0, rx, ry); break;
+      default: march<T, NV, K, 3, RING, AR, false, false, K, false, false, false, true>(src, dst, a, T(1), strip, t0, t1, lane, nullptr, 0, rx, ry); break;
+    }
+  }
+  queue_exit(a);
+}
+
 template <typename T, int NV, int K, int RING, bool MAIN, int AR, int VAR = kVarPlain>
 constexpr auto kernel_ptr() {
   return &tb_kernel<T, NV, K, RING, MAIN, AR, VAR>;
@@ -1477,6 +1654,11 @@ template <typename T, int AR>
 void dispatch_var(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, const T* rmap, hipStream_t s);
 template <typename T, int AR>
 int occupancy_waves_var(int k);
+// conservative-form kernels: ring 4, depths 1..kMaxTBDiv (tb_<dtype>_div[_fma].hip)
+template <typename T, int AR>
+void dispatch_div(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, const T* rx, const T* ry, hipStream_t s);
+template <typename T, int AR>
+int occupancy_waves_div(int k);
 #define H2D_TB_CASE(T, RING, MAIN, AR, KK)                                                                    \
   case KK:                                                                                                    \
     hipLaunchKernelGGL((tb_kernel<T, 1, KK, RING, MAIN, AR>), dim3(nblocks), dim3(256), 0, s, src, dst, a, r); \
@@ -1691,6 +1873,52 @@ int waves_per_cu_var() {
   int occupancy_waves_var<T, AR>(int k) {                                                                     \
     switch (k) {                                                                                              \
       H2D_TB_CASES(H2D_VAR_OCC_CASE, T, 4, false, AR)                                                         \
+      default:                                                                                                \
+        break;                                                                                                \
+    }                                                                                                         \
+    return 4;                                                                                                 \
+  }
+
+// resident waves (one-wave workgroups) per CU of one tb_kernel_div instance
+template <typename T, int K, int AR>
+int waves_per_cu_div() {
+  static std::mutex mu;
+  static std::map<int, int> cache;  // device -> waves/CU
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> g(mu);
+  auto it = cache.find(dev);
+  if (it != cache.end()) return it->second;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tb_kernel_div<T, 1, K, 4, AR>), 64,
+                                                   0) != hipSuccess ||
+      nb <= 0)
+    nb = 4;
+  cache[dev] = nb;
+  return nb;
+}
+#define H2D_DIV_CASE(T, RING, MAIN, AR, KK)                                                                   \
+  case KK:                                                                                                    \
+    hipLaunchKernelGGL((tb_kernel_div<T, 1, KK, 4, AR>), dim3(nwaves), dim3(64), 0, s, src, dst, a, rx, ry);  \
+    return;
+#define H2D_DIV_OCC_CASE(T, RING, MAIN, AR, KK) \
+  case KK:                                      \
+    return waves_per_cu_div<T, KK, AR>();
+#define H2D_DIV_UNIT(T, AR)                                                                                   \
+  template <>                                                                                                 \
+  void dispatch_div<T, AR>(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, const T* rx,        \
+                           const T* ry, hipStream_t s) {                                                      \
+    switch (k) {                                                                                              \
+      H2D_TB_CASES(H2D_DIV_CASE, T, 4, false, AR)                                                             \
+      default:                                                                                                \
+        break;                                                                                                \
+    }                                                                                                         \
+    HEAT2D_REQUIRE(false, "temporal depth not instantiated for the conservative-form kernel");                \
+  }                                                                                                           \
+  template <>                                                                                                 \
+  int occupancy_waves_div<T, AR>(int k) {                                                                     \
+    switch (k) {                                                                                              \
+      H2D_TB_CASES(H2D_DIV_OCC_CASE, T, 4, false, AR)                                                         \
       default:                                                                                                \
         break;                                                                                                \
     }                                                                                                         \

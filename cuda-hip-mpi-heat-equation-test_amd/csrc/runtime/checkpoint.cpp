@@ -123,6 +123,7 @@ std::string json_value(const std::string& js, const std::string& key) {
 
 struct NpyInfo {
   int64_t rows = 0, cols = 0;
+  int64_t planes = 0;  // 3-D arrays: the first extent (rows / cols the other two); 0: 2-D
   int dtype = 1;       // 0 fp32, 1 fp64
   long data_off = 0;   // byte offset of the array data
 };
@@ -159,6 +160,12 @@ NpyInfo npy_header(FILE* f, const std::string& path) {
                  path + ": expected a 2-D shape");
   info.rows = r;
   info.cols = c;
+  long long a3 = 0, b3 = 0, c3 = 0;
+  if (std::sscanf(h.c_str() + sp, "'shape': (%lld, %lld, %lld)", &a3, &b3, &c3) == 3) {
+    info.planes = a3;
+    info.rows = b3;
+    info.cols = c3;
+  }
   return info;
 }
 
@@ -231,7 +238,9 @@ void write_meta(const std::string& dir, const std::string& name, const Meta& m) 
                 m.bc_x.c_str(), m.bc_y.c_str(),
                 m.source_sha256.empty() ? "null" : ("\"" + m.source_sha256 + "\"").c_str(),
                 // (the key only with a diffusivity map: saves without one keep their key set)
-                m.rmap_sha256.empty() ? "" : (" \"rmap_sha256\": \"" + m.rmap_sha256 + "\",\n").c_str());
+                ((m.rmap_sha256.empty() ? "" : " \"rmap_sha256\": \"" + m.rmap_sha256 + "\",\n") +
+                 // (and the key of the face coefficients only with them)
+                 (m.faces_sha256.empty() ? "" : " \"faces_sha256\": \"" + m.faces_sha256 + "\",\n")).c_str());
   write_atomic(join(join(dir, name), "meta.json"), buf);  // + fsync of the step directory (rank files' entries)
   write_atomic(join(dir, "latest"), name + "\n");  // the commit point
   // prune: keep the two newest complete saves, ordered by (step, generation)
@@ -296,6 +305,11 @@ Meta read_meta(const std::string& dir) {
     while (!m.rmap_sha256.empty() && (m.rmap_sha256.back() == ' ' || m.rmap_sha256.back() == '\r')) m.rmap_sha256.pop_back();
     if (m.rmap_sha256 == "null") m.rmap_sha256.clear();
   }
+  if (js.find("\"faces_sha256\"") != std::string::npos) {
+    m.faces_sha256 = json_value(js, "faces_sha256");
+    while (!m.faces_sha256.empty() && (m.faces_sha256.back() == ' ' || m.faces_sha256.back() == '\r')) m.faces_sha256.pop_back();
+    if (m.faces_sha256 == "null") m.faces_sha256.clear();
+  }
   auto bc_ok = [](const std::string& v) { return v == "dirichlet" || v == "periodic" || v == "insulated"; };
   HEAT2D_REQUIRE(bc_ok(m.bc_x) && bc_ok(m.bc_y), dir + ": meta.json: bc_x / bc_y must be dirichlet, periodic or insulated");
   HEAT2D_REQUIRE(m.nranks >= 1 && m.step >= 0 && m.n_owned >= 1, dir + ": inconsistent meta.json");
@@ -346,13 +360,21 @@ std::string sha256_hex(const void* data, size_t bytes) {
   return std::string(out, 64);
 }
 
-std::vector<char> read_source(const std::string& path, int64_t rows, int64_t cols, int dtype, std::string* sha256) {
+namespace {
+// planes 0: a 2-D rows x cols array; else a 3-D planes x rows x cols one
+std::vector<char> read_array(const std::string& path, int64_t planes, int64_t rows, int64_t cols, int dtype,
+                             std::string* sha256) {
   File file(path, "rb");
   const NpyInfo info = npy_header(file.f, path);
-  HEAT2D_REQUIRE(info.rows == rows && info.cols == cols,
+  if (planes > 0)
+    HEAT2D_REQUIRE(info.planes == planes && info.rows == rows && info.cols == cols,
+                   path + ": shape (" + (info.planes ? std::to_string(info.planes) + ", " : "") + std::to_string(info.rows) +
+                       ", " + std::to_string(info.cols) + "), the face coefficients of this grid are (" +
+                       std::to_string(planes) + ", " + std::to_string(rows) + ", " + std::to_string(cols) + ")");
+  HEAT2D_REQUIRE(info.planes == planes && info.rows == rows && info.cols == cols,
                  path + ": shape (" + std::to_string(info.rows) + ", " + std::to_string(info.cols) +
                      "), the frame-inclusive grid is (" + std::to_string(rows) + ", " + std::to_string(cols) + ")");
-  const size_t n = (size_t)(rows * cols), es_in = info.dtype == 0 ? 4 : 8, es = dtype == 0 ? 4 : 8;
+  const size_t n = (size_t)((planes > 0 ? planes : 1) * rows * cols), es_in = info.dtype == 0 ? 4 : 8, es = dtype == 0 ? 4 : 8;
   std::vector<char> raw(n * es_in);
   HEAT2D_REQUIRE(std::fseek(file.f, info.data_off, SEEK_SET) == 0 && std::fread(raw.data(), es_in, n, file.f) == n,
                  path + ": truncated data");
@@ -373,6 +395,15 @@ std::vector<char> read_source(const std::string& path, int64_t rows, int64_t col
   }
   if (sha256) *sha256 = sha256_hex(out.data(), out.size());
   return out;
+}
+}  // namespace
+
+std::vector<char> read_source(const std::string& path, int64_t rows, int64_t cols, int dtype, std::string* sha256) {
+  return read_array(path, 0, rows, cols, dtype, sha256);
+}
+
+std::vector<char> read_faces(const std::string& path, int64_t rows, int64_t cols, int dtype, std::string* sha256) {
+  return read_array(path, 2, rows, cols, dtype, sha256);
 }
 
 void read_rows(const Meta& m, int64_t row0, int64_t nrows, int64_t ncols, int dtype, void* out) {

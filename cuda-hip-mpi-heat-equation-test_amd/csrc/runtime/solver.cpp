@@ -74,14 +74,14 @@ SlabLayout solver_layout(const SolverConfig& cfg, int rank, int nranks) {
 Footprint solver_footprint(const SolverConfig& cfg, int rank, int nranks) {
   const SlabLayout L = solver_layout(cfg, rank, nranks);
   Footprint f{};
-  f.field_bytes = (2 + (cfg.source ? 1 : 0) + (cfg.rmap ? 1 : 0)) * L.elems() * (int64_t)dtype_size((DType)cfg.dtype);
+  f.field_bytes = (2 + (cfg.source ? 1 : 0) + (cfg.rmap ? 1 : 0) + (cfg.faces ? 2 : 0)) * L.elems() * (int64_t)dtype_size((DType)cfg.dtype);
   if (cfg.backend == (int32_t)Backend::Hip)
     f.work_bytes = (kern::stats_work_elems() + 8) * 8 + 6 * kern::max_stats_waves() * 8 + 2 * 4;
   f.total_bytes = f.field_bytes + f.work_bytes;
   return f;
 }
 
-int64_t plan_max_grid(int dtype, int nranks, int64_t budget_bytes, int64_t halo, bool source, bool rmap) {
+int64_t plan_max_grid(int dtype, int nranks, int64_t budget_bytes, int64_t halo, bool source, bool rmap, bool faces) {
   HEAT2D_REQUIRE(nranks >= 1 && budget_bytes > 0, "plan_max_grid needs nranks >= 1 and a positive budget");
   SolverConfig c{};
   c.dtype = dtype;
@@ -89,6 +89,7 @@ int64_t plan_max_grid(int dtype, int nranks, int64_t budget_bytes, int64_t halo,
   c.halo = halo;
   c.source = source ? 1 : 0;
   c.rmap = rmap ? 1 : 0;
+  c.faces = faces ? 1 : 0;
   // the largest slab is rank 0's (decompose() gives the remainder to the first ranks)
   auto fits = [&](int64_t n) {
     c.n_rows = c.n_cols = n;
@@ -153,6 +154,22 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
     K = std::min<int>(K, kMaxTBVar);  // the map kernels' deepest pass
     // auto: exact (fma has the reference's bits only where every multiplier is a power of two)
     if (cfg_.arith < 0) cfg_.arith = 0;
+  }
+  HEAT2D_REQUIRE(cfg_.faces == 0 || cfg_.faces == 1, "faces must be 0 or 1");
+  if (cfg_.faces) {
+    HEAT2D_REQUIRE(!cfg_.source && !cfg_.rmap,
+                   "face coefficients together with a heat source or a diffusivity map: no kernel carries them together "
+                   "(a known limit)");
+    HEAT2D_REQUIRE(cfg_.arith != 2 && cfg_.arith != 3,
+                   "face coefficients have no arith jacobi / fast: their scaled levels assume one r for the whole grid "
+                   "(use exact, fma or auto)");
+    HEAT2D_REQUIRE(cfg_.bc_x == kBcDirichlet && cfg_.bc_y == kBcDirichlet,
+                   "face coefficients need Dirichlet boundaries on both axes (no periodic or insulated conservative-form "
+                   "kernels; a zero face is a wall)");
+    HEAT2D_REQUIRE(cfg_.engine == 0, "face coefficients need the temporal-blocked engine (engine \"jit\" takes one r)");
+    HEAT2D_REQUIRE(!cfg_.copy_swap, "face coefficients have no copy-swap mode");
+    K = std::min<int>(K, kMaxTBDiv);  // the conservative-form kernels' deepest pass
+    if (cfg_.arith < 0) cfg_.arith = 0;  // auto: exact
   }
   if (cfg_.arith < 0) {
     // auto: the contracted form when it is bitwise identical to the reference
@@ -228,6 +245,8 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
     }
     if (cfg_.source) H2D_HIP(hipMalloc(&src_buf_, bytes));
     if (cfg_.rmap) H2D_HIP(hipMalloc(&rmap_buf_, bytes));
+    if (cfg_.faces)
+      for (auto& b : face_buf_) H2D_HIP(hipMalloc(&b, bytes));
     // (solver_footprint() counts exactly these allocations: keep them in step)
     H2D_HIP(hipMalloc(reinterpret_cast<void**>(&d_work_), (size_t)(kern::stats_work_elems() + 8) * sizeof(double)));
     H2D_HIP(hipMalloc(reinterpret_cast<void**>(&d_part_), (size_t)(6 * kern::max_stats_waves()) * sizeof(double)));
@@ -283,6 +302,8 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
     for (int b = 0; b < 2; ++b) buf_[b] = host_alloc(bytes);
     if (cfg_.source) src_buf_ = host_alloc(bytes);
     if (cfg_.rmap) rmap_buf_ = host_alloc(bytes);
+    if (cfg_.faces)
+      for (auto& b : face_buf_) b = host_alloc(bytes);
     cfg_.overlap = 0;
     cfg_.use_graph = 0;
   }
@@ -300,6 +321,8 @@ Solver::~Solver() {
       if (b) (void)hipFree(b);
     if (src_buf_) (void)hipFree(src_buf_);
     if (rmap_buf_) (void)hipFree(rmap_buf_);
+    for (auto& b : face_buf_)
+      if (b) (void)hipFree(b);
     if (d_work_) (void)hipFree(d_work_);
     if (d_part_) (void)hipFree(d_part_);
     if (d_queue_) (void)hipFree(d_queue_);
@@ -318,6 +341,7 @@ Solver::~Solver() {
     for (auto& b : buf_) std::free(b);
     std::free(src_buf_);
     std::free(rmap_buf_);
+    for (auto& b : face_buf_) std::free(b);
   }
 }
 
@@ -370,15 +394,16 @@ void Solver::wrap_cols_all(void* field) {
 bool Solver::pipe_ok(int k) const {
   // (nor with a heat source: the source kernel is the one-wave general one)
   // (nor with a diffusivity map, for the same reason)
-  return kern::pipe_available(dtype(), k, cfg_.arith) && !(bc_ & kern::kBcInsulatedY) && !cfg_.source && !cfg_.rmap;
+  return kern::pipe_available(dtype(), k, cfg_.arith) && !(bc_ & kern::kBcInsulatedY) && !cfg_.source && !cfg_.rmap &&
+         !cfg_.faces;  // (nor with face coefficients)
 }
 
 void Solver::launch_tb(const void* src, void* dst, int64_t rb, int64_t re, int k) {
   if (re <= rb) return;
   if (hip_)
-    kern::launch_tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, s_compute_, cfg_.tile_rows, compute_cus_, cfg_.arith, bc_, source(), rmap());
+    kern::launch_tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, s_compute_, cfg_.tile_rows, compute_cus_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry());
   else
-    cpu::tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, cfg_.arith, bc_, source(), rmap());
+    cpu::tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry());
 }
 
 void Solver::exchange_on(void* field, int64_t k, hipStream_t s) {
@@ -505,7 +530,7 @@ void Solver::cycle_finish() {
     if (pe) H2D_HIP(hipEventRecord(pe->ev[5], s_comm_));
     if (pend_frame_ >= 0) {  // the edge rank's frame-side band (launch_overlap), after the exchange
       kern::launch_edge_rect(dtype(), buf_[cur_], dst, L_, split_plan_banded(pend_k_, pend_frame_b_), pend_frame_, cfg_.r,
-                             s_comm_, cfg_.arith, bc_, source(), rmap());
+                             s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry());
       // the next cycle's compute-stream work waits for it (and so for the
       // exchange ahead of it); ev_bnd_, posted to the transport, is left alone
       H2D_HIP(hipEventRecord(ev_frame_, s_comm_));
@@ -768,8 +793,8 @@ void Solver::trial_cycle(const kern::SplitPlan& c) {
   last_k_ = 0;  // the other buffer no longer holds T_{n-1}: stats(residual) reports NaN
   if (c.valid == 3) {  // edge-first: both parts in order on the compute stream
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
-    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap());
-    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
+    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
+    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
     return;
@@ -777,15 +802,15 @@ void Solver::trial_cycle(const kern::SplitPlan& c) {
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
   H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));
   if (c.flags & kern::kPlanLead) {  // lead: the band launch issued first
-    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap());
-    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
+    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
+    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
     return;
   }
-  kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
+  kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
   H2D_HIP(hipEventRecord(ev_int_, s_compute_));
-  kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap());
+  kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
   H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
 }
 
@@ -851,7 +876,8 @@ std::string Solver::cache_ctx() const {
                 tr_->name().c_str(), (int)cfg_.bc_x, (int)cfg_.bc_y, (unsigned long long)plan_env_hash());
   // (plans tuned with the source kernels are another family; keys without a source stay as they were)
   // (and so are plans tuned with the diffusivity-map kernels)
-  return std::string(b) + (cfg_.source ? "|src1" : "") + (cfg_.rmap ? "|rmap1" : "");
+  // (and with the conservative-form kernels)
+  return std::string(b) + (cfg_.source ? "|src1" : "") + (cfg_.rmap ? "|rmap1" : "") + (cfg_.faces ? "|faces1" : "");
 }
 
 // The cached autotuned plan of depth k for this slab, re-validated by one
@@ -1188,9 +1214,9 @@ void Solver::launch_overlap(int k, int64_t B) {
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));  // edge part c-1
     H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));     // main part c-1
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_comm_));
-    kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, cfg_.arith, bc_, source(), rmap());
+    kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_comm_));
@@ -1206,12 +1232,12 @@ void Solver::launch_overlap(int k, int64_t B) {
     // comm stream (cycle_finish) = [bands(c) done] exchange(c), beside the interior.
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_comm_, 0));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
     if (tr_->exchanges()) tr_->post(dst, L_, ev_bnd_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     pend_ = Pending::EdgeFirst;
@@ -1222,23 +1248,23 @@ void Solver::launch_overlap(int k, int64_t B) {
   if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_comm_));
   if (lead) {
     // lead: the band launch first (comm stream), then the interior beside it
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
   } else if (sp.valid) {
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
   } else {  // slab too thin / narrow to split: all of it beside the exchange
     if (pe) {
       H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
       H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     }
-    kern::launch_tb(dtype(), src, dst, L_, 0, L_.nrows, k, cfg_.r, s_comm_, 0, 0, cfg_.arith, bc_, source(), rmap());
+    kern::launch_tb(dtype(), src, dst, L_, 0, L_.nrows, k, cfg_.r, s_comm_, 0, 0, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry());
   }
   if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_comm_));
   H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
@@ -1934,7 +1960,7 @@ void Solver::step_stats(int64_t n, double out[6]) {
   // (periodic y: the fused-statistics march would count its ghost columns;
   // insulated axes: the fused-statistics kernel has no insulated edges)
   // (a heat source: the fused-statistics kernel has no source term)
-  if (!hip_ || jit_ || cfg_.copy_swap || cfg_.bc_y || cfg_.bc_x == kBcInsulated || cfg_.source || cfg_.rmap) {
+  if (!hip_ || jit_ || cfg_.copy_swap || cfg_.bc_y || cfg_.bc_x == kBcInsulated || cfg_.source || cfg_.rmap || cfg_.faces) {
     step(n - 1);
     step(1);
     stats(out, true);
@@ -2161,6 +2187,54 @@ void Solver::set_rmap(const void* host, int64_t ld) {
   rmap_on_ = true;
 }
 
+void Solver::set_faces(const void* rx, const void* ry, int64_t ld) {
+  HEAT2D_REQUIRE((rx == nullptr) == (ry == nullptr), "set_faces: give both arrays (rx and ry) or neither");
+  HEAT2D_REQUIRE(rx == nullptr || cfg_.faces,
+                 "this solver was built without face coefficients (SolverConfig::faces = 0): pass faces= when it is created");
+  if (!rx) {
+    drop_graphs();
+    faces_on_ = false;
+    return;
+  }
+  HEAT2D_REQUIRE(ld >= L_.ncols + 2, "set_faces: leading dimension below ncols + 2");
+  // this rank's copies: +0.0 everywhere (pad entries, allocated rows outside the
+  // grid, the unused last column of rx / last row of ry), then the used faces of
+  // every allocated row: rx the owned rows, columns -1 (the frame column's east
+  // face) .. ncols - 1; ry rows -1 (the frame row's south face) .. nrows_global - 1,
+  // the owned columns
+  const size_t es = dtype_size(dtype());
+  std::vector<char> stage[2];
+  bool ok = true;
+  auto check = [&](const char* p, int64_t n) {
+    if (dtype() == DType::F32) {
+      const float* v = reinterpret_cast<const float*>(p);
+      for (int64_t j = 0; j < n; ++j) ok = ok && std::isfinite(v[j]) && v[j] >= 0.f;
+    } else {
+      const double* v = reinterpret_cast<const double*>(p);
+      for (int64_t j = 0; j < n; ++j) ok = ok && std::isfinite(v[j]) && v[j] >= 0.0;
+    }
+  };
+  for (int w = 0; w < 2; ++w) {
+    stage[w].assign((size_t)L_.elems() * es, 0);
+    const char* host = static_cast<const char*>(w == 0 ? rx : ry);
+    for (int64_t i = -L_.halo; i < L_.nrows + L_.halo; ++i) {
+      const int64_t g = L_.row0 + i;  // global owned-row index; the frame-inclusive row is g + 1
+      if (g < (w == 0 ? 0 : -1) || g >= L_.nrows_global) continue;
+      const int64_t c0 = w == 0 ? -1 : 0, n = w == 0 ? L_.ncols + 1 : L_.ncols;
+      char* to = stage[w].data() + (size_t)L_.offset(i, c0) * es;
+      std::memcpy(to, host + (size_t)((g + 1) * ld + c0 + 1) * es, (size_t)n * es);
+      check(to, n);
+    }
+  }
+  HEAT2D_REQUIRE(ok, "set_faces: the used face coefficients must be finite and >= 0");
+  drop_graphs();
+  for (int w = 0; w < 2; ++w) {
+    if (hip_) H2D_HIP(hipMemcpy(face_buf_[w], stage[w].data(), stage[w].size(), hipMemcpyHostToDevice));
+    else std::memcpy(face_buf_[w], stage[w].data(), stage[w].size());
+  }
+  faces_on_ = true;
+}
+
 void Solver::upload_field(const void* host, int64_t ld) {
   upload_framed(host, ld);
   exchange_post();
@@ -2257,6 +2331,10 @@ void LoopbackGroup::set_source(const void* host, int64_t ld) {
 
 void LoopbackGroup::set_rmap(const void* host, int64_t ld) {
   for (auto& m : members_) m->set_rmap(host, ld);
+}
+
+void LoopbackGroup::set_faces(const void* rx, const void* ry, int64_t ld) {
+  for (auto& m : members_) m->set_faces(rx, ry, ld);
 }
 
 void LoopbackGroup::upload_field(const void* host, int64_t ld) {

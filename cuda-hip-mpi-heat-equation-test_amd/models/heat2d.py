@@ -116,6 +116,78 @@ def rmap_from_nu(problem: Problem, nu_xy) -> np.ndarray:
     return np.float64(problem.r) * np.asarray(nu_xy, dtype=np.float64) / np.float64(problem.nu)
 
 
+def _faces_arrays(faces, nrows_global: int, ncols: int, np_dtype) -> tuple:
+    """The two global frame-inclusive face arrays in the field's dtype (a wrong
+    shape, or a used face that is negative or not finite, fails). Used: RX[i, j]
+    for i = 1..n, j = 0..n; RY[i, j] for i = 0..n, j = 1..n."""
+    try:
+        rx, ry = faces
+    except (TypeError, ValueError):
+        raise ValueError("faces must be a pair (RX, RY) of frame-inclusive arrays") from None
+    rx = np.ascontiguousarray(rx, dtype=np_dtype)
+    ry = np.ascontiguousarray(ry, dtype=np_dtype)
+    want = (nrows_global + 2, ncols + 2)
+    if rx.shape != want or ry.shape != want:
+        raise ValueError(f"faces must be two frame-inclusive global arrays {want}, got {rx.shape} and {ry.shape}")
+    for used in (rx[1:-1, :-1], ry[:-1, 1:-1]):
+        if not (np.isfinite(used).all() and (used >= 0).all()):
+            raise ValueError("the used face coefficients must be finite and >= 0")
+    return rx, ry
+
+
+def faces_sum_max(rx, ry) -> float:
+    """max over the owned points of RX[i,j] + RX[i,j-1] + RY[i,j] + RY[i-1,j]: the
+    4r of the scalar case (above 1 FTCS is unstable)."""
+    rx = np.asarray(rx, dtype=np.float64)
+    ry = np.asarray(ry, dtype=np.float64)
+    return float((rx[1:-1, 1:-1] + rx[1:-1, :-2] + ry[1:-1, 1:-1] + ry[:-2, 1:-1]).max())
+
+
+def _faces_sha256(rx: np.ndarray, ry: np.ndarray) -> str:
+    """What a checkpoint records of the faces: the digest of the converted arrays' bytes, RX then RY."""
+    return hashlib.sha256(rx.tobytes() + ry.tobytes()).hexdigest()
+
+
+def _faces_info(h) -> dict:
+    """info()["faces"]: whether the solver was built for face coefficients,
+    whether they are set, and the depth clamp that then applies (0: none)."""
+    v = (C.c_int32 * 3)()
+    N.call("heat2d_solver_faces", h, v)
+    return {"enabled": bool(v[0]), "set": bool(v[1]), "max_tb": int(v[2]) if v[0] else 0}
+
+
+def faces_from_k(problem: Problem, k_xy, mean: str = "harmonic") -> tuple:
+    """The per-face diffusion numbers (RX, RY) of a cell conductivity
+    (diffusivity) field ``k_xy`` on the frame-inclusive grid, in float64:
+    ``dt / dx^2`` (= problem.r / problem.nu) times the mean of the two cells a
+    face separates. ``mean``: "harmonic" (2ab / (a + b), conductors in series —
+    the default) or "arithmetic"; the mean of a 0 and anything is 0 (a wall).
+    RX[i, j] is the face between (i, j) and (i, j+1), RY[i, j] the one between
+    (i, j) and (i+1, j); the unused last column / row is 0."""
+    if mean not in ("harmonic", "arithmetic"):
+        raise ValueError(f"mean must be 'harmonic' or 'arithmetic', got {mean!r}")
+    k = np.asarray(k_xy, dtype=np.float64)
+    m = problem.n_owned + 2
+    if k.shape != (m, m):
+        raise ValueError(f"k_xy must be the frame-inclusive grid {(m, m)}, got {k.shape}")
+    scale = np.float64(problem.r) / np.float64(problem.nu)
+
+    def face(a, b):
+        zero = (a == 0) | (b == 0)
+        if mean == "arithmetic":
+            v = 0.5 * (a + b)
+        else:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                v = 2.0 * a * b / (a + b)
+        return np.where(zero, 0.0, v)
+
+    rx = np.zeros((m, m), dtype=np.float64)
+    ry = np.zeros((m, m), dtype=np.float64)
+    rx[:, :-1] = scale * face(k[:, :-1], k[:, 1:])
+    ry[:-1, :] = scale * face(k[:-1, :], k[1:, :])
+    return rx, ry
+
+
 def _arith(h) -> int:
     """The arithmetic form (ops._native.ARITH code) a native solver runs: "auto" resolved."""
     v = C.c_int32()
@@ -205,6 +277,21 @@ class HeatSolver:
             / "fma" ("auto" is exact); the depth is clamped to the map kernels'
             deepest pass (info()["rmap"]). :meth:`set_rmap` replaces it, or
             returns to the scalar r, between steps.
+        faces: the conservative form u_t = div(k grad u): a pair (RX, RY) of
+            GLOBAL frame-inclusive arrays (rows + 2) x (n + 2) of per-face
+            diffusion numbers, already multiplied by dt / dx^2
+            (:func:`faces_from_k`; the solver does no scaling; converted to the
+            field's dtype). RX[i, j] is the face between (i, j) and (i, j+1)
+            (used for j = 0..n), RY[i, j] the one between (i, j) and (i+1, j)
+            (used for i = 0..n); used faces finite and >= 0. One step is
+            T' = C + (((RY[i,j]*(S-C) + RX[i,j]*(E-C)) + RY[i-1,j]*(N-C)) +
+            RX[i,j-1]*(W-C)) ("fma": the sums contracted), bitwise equal to
+            models.reference.ftcs(faces=) at any depth, plan and rank count.
+            What a face takes from one cell it gives the other; a zero face is
+            a wall. Dirichlet axes, engine "tb", no copy_swap, no source, no
+            rmap, arith "exact" / "fma" ("auto" is exact); the depth is clamped
+            to info()["faces"]["max_tb"]. :meth:`set_faces` replaces them, or
+            returns to the scalar r, between steps.
     """
 
     def __init__(self, problem: Problem, *, dtype: str = "fp64", backend: str = "auto", tb: int = 0,
@@ -213,7 +300,7 @@ class HeatSolver:
                  device: Optional[int] = None, init: bool = True, rows: Optional[int] = None,
                  comm_cus: int = 0, autotune: int = -1, engine: str = "tb", arith: str = "auto",
                  slab_row0: Optional[int] = None, edge_shift: int = 0, bc_x: str = "dirichlet",
-                 bc_y: str = "dirichlet", source=None, rmap=None):
+                 bc_y: str = "dirichlet", source=None, rmap=None, faces=None):
         self.problem = problem
         self.edge_shift = 0 if bc_x == "periodic" else int(edge_shift)  # (periodic x: no edge slabs)
         self.bc_x, self.bc_y = bc_x, bc_y
@@ -264,6 +351,10 @@ class HeatSolver:
         self.rmap_sha256 = None
         if rmap is not None and arith == "auto":
             self.arith = "exact"  # (the native solver resolves it the same way)
+        cfg.faces = int(faces is not None)
+        self.faces_sha256 = None
+        if faces is not None and arith == "auto":
+            self.arith = "exact"
         self._cfg = cfg
         h = C.c_void_p()
         N.call("heat2d_solver_create", C.byref(cfg), self.transport.handle, C.byref(h))
@@ -274,8 +365,24 @@ class HeatSolver:
             self.set_source(source)
         if rmap is not None:
             self.set_rmap(rmap)
+        if faces is not None:
+            self.set_faces(faces)
         if init:
             self.init()
+
+    def set_faces(self, faces) -> None:
+        """Replace the face coefficients (the pair of global frame-inclusive
+        arrays, see the class docstring) or drop them (None: the solver then
+        runs the scalar-r kernels), between step() calls. The solver must have
+        been created with faces; nothing but captured graphs is invalidated."""
+        if faces is None:
+            N.call("heat2d_solver_set_faces", self._h, None, None, 0)
+            self.faces_sha256 = None
+            return
+        rx, ry = _faces_arrays(faces, int(self.layout.nrows_global), self.ncols, self.np_dtype)
+        N.call("heat2d_solver_set_faces", self._h, rx.ctypes.data_as(C.c_void_p), ry.ctypes.data_as(C.c_void_p),
+               rx.shape[1])
+        self.faces_sha256 = _faces_sha256(rx, ry)
 
     def set_rmap(self, rmap) -> None:
         """Replace the diffusivity map (the global frame-inclusive array, see
@@ -337,6 +444,7 @@ class HeatSolver:
                 "bc_x": self._bc()[0], "bc_y": self._bc()[1],  # "dirichlet" | "periodic" | "insulated", as the native solver runs
                 "source": _source_info(self._h),
                 "rmap": _rmap_info(self._h),
+                "faces": _faces_info(self._h),
                 "rank": self.rank, "size": self.size, "layout": self.layout.as_dict()}
 
     def _bc(self) -> tuple:
@@ -574,7 +682,7 @@ class LoopbackGroup:
     def __init__(self, problem: Problem, nranks: int, *, dtype: str = "fp64", backend: str = "auto",
                  tb: int = 0, tile_rows: int = 0, device: Optional[int] = None, arith: str = "auto",
                  overlap: bool = True, autotune: int = -1, comm_cus: int = 0, edge_shift: int = 0,
-                 bc_x: str = "dirichlet", bc_y: str = "dirichlet", source=None, rmap=None):
+                 bc_x: str = "dirichlet", bc_y: str = "dirichlet", source=None, rmap=None, faces=None):
         self.problem = problem
         self.bc_x, self.bc_y = bc_x, bc_y
         self.backend = resolve_backend(backend)
@@ -600,6 +708,7 @@ class LoopbackGroup:
         cfg.bc_y = N.bc_code(bc_y, "bc_y")
         cfg.source = int(source is not None)  # a heat source (HeatSolver source=): each member slices its rows
         cfg.rmap = int(rmap is not None)  # a diffusivity map (HeatSolver rmap=): likewise
+        cfg.faces = int(faces is not None)  # face coefficients (HeatSolver faces=): likewise
         self.nranks = nranks
         h = C.c_void_p()
         N.call("heat2d_group_create", C.byref(cfg), nranks, C.byref(h))
@@ -608,6 +717,8 @@ class LoopbackGroup:
             self.set_source(source)
         if rmap is not None:
             self.set_rmap(rmap)
+        if faces is not None:
+            self.set_faces(faces)
         x = np.ascontiguousarray(problem.x, dtype=np.float64)
         ic = problem.ic.to_native()
         N.call("heat2d_group_init", self._h, C.byref(ic), x.ctypes.data_as(C.c_void_p),
@@ -635,6 +746,16 @@ class LoopbackGroup:
         m = self.problem.n_owned
         a = _rmap_array(rmap, m, m, NP_DTYPES[self.dtype])
         N.call("heat2d_group_set_rmap", self._h, a.ctypes.data_as(C.c_void_p), m + 2)
+
+    def set_faces(self, faces) -> None:
+        """Replace (the pair of global frame-inclusive arrays) or drop (None) the
+        face coefficients of every member, between step() calls (HeatSolver.set_faces)."""
+        if faces is None:
+            N.call("heat2d_group_set_faces", self._h, None, None, 0)
+            return
+        m = self.problem.n_owned
+        rx, ry = _faces_arrays(faces, m, m, NP_DTYPES[self.dtype])
+        N.call("heat2d_group_set_faces", self._h, rx.ctypes.data_as(C.c_void_p), ry.ctypes.data_as(C.c_void_p), m + 2)
 
     def upload(self, arr: np.ndarray) -> None:
         """Whole owned grid -> the members' slabs, then a loopback halo exchange."""

@@ -166,8 +166,40 @@ def _ftcs_step_rmap(T: np.ndarray, arith: str, rmap: np.ndarray) -> np.ndarray:
     return out
 
 
+def _ftcs_step_faces(T: np.ndarray, arith: str, faces) -> np.ndarray:
+    """One step of the conservative (divergence) form u_t = div(k grad u) from
+    per-face diffusion numbers ``faces = (RX, RY)``, two frame-inclusive arrays
+    already multiplied by dt / dx^2: RX[i,j] is the face between (i,j) and
+    (i,j+1) (used for j = 0..n), RY[i,j] the face between (i,j) and (i+1,j)
+    (used for i = 0..n). At every owned point, operands in the march's order
+    S, E, N, W,
+        exact: T' = C + (((RY[i,j]*(S-C) + RX[i,j]*(E-C)) + RY[i-1,j]*(N-C)) + RX[i,j-1]*(W-C))
+        fma:   p = RY[i,j]*(S-C); p = fma(RX[i,j], E-C, p); p = fma(RY[i-1,j], N-C, p);
+               p = fma(RX[i,j-1], W-C, p); T' = C + p     (:func:`fma`: one rounding each)
+    The frame stays pinned. The product a face contributes to a point is the
+    exact negative of the one it contributes to the neighbour (E-C and C-E
+    differ in sign only), so what leaves one cell enters the other; a zero
+    face is a wall, and a point whose four faces are zero keeps its bits."""
+    if arith not in ("exact", "fma"):
+        raise ValueError("face coefficients need arith 'exact' or 'fma' (jacobi assumes one r == 1/4)")
+    RX, RY = faces
+    if RX.shape != T.shape or RY.shape != T.shape:
+        raise ValueError(f"faces must be two frame-inclusive arrays like the field, {T.shape}, got {RX.shape} and {RY.shape}")
+    RX = np.ascontiguousarray(RX, dtype=T.dtype)
+    RY = np.ascontiguousarray(RY, dtype=T.dtype)
+    c = T[1:-1, 1:-1]
+    ds, de, dn, dw = T[2:, 1:-1] - c, T[1:-1, 2:] - c, T[:-2, 1:-1] - c, T[1:-1, :-2] - c
+    ys, xe, yn, xw = RY[1:-1, 1:-1], RX[1:-1, 1:-1], RY[:-2, 1:-1], RX[1:-1, :-2]
+    out = T.copy()
+    if arith == "fma":
+        out[1:-1, 1:-1] = c + fma(xw, dw, fma(yn, dn, fma(xe, de, ys * ds)))
+    else:
+        out[1:-1, 1:-1] = c + (((ys * ds + xe * de) + yn * dn) + xw * dw)
+    return out
+
+
 def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
-              source: np.ndarray | None = None, rmap: np.ndarray | None = None) -> np.ndarray:
+              source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None) -> np.ndarray:
     """One FTCS step of a frame-inclusive field. On a Dirichlet axis the frame
     is kept fixed; on a periodic or insulated one it is refreshed from the
     owned points before the step (:func:`wrap_frame`) — the update and its
@@ -183,7 +215,16 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
     one, "fma" keeps taking the exact expression as it always has here (equal
     bits only where r is a power of two). So at such an r as 0.2,
     ``ftcs(arith="fma", source=None)`` and ``ftcs(arith="fma", source=<all -0.0>)``
-    differ, while with "exact" they are bitwise equal."""
+    differ, while with "exact" they are bitwise equal.
+    faces ((RX, RY), per-face diffusion numbers; Dirichlet axes, arith "exact" or
+    "fma", no source, no rmap): the conservative form (:func:`_ftcs_step_faces`);
+    ``r`` is then not used. None: today's function."""
+    if faces is not None:
+        if rmap is not None or source is not None:
+            raise ValueError("face coefficients together with rmap= or source= are not offered")
+        if bc_x != "dirichlet" or bc_y != "dirichlet":
+            raise ValueError("face coefficients need Dirichlet boundaries on both axes")
+        return _ftcs_step_faces(T, arith, faces)
     if rmap is not None:
         # rmap (frame-inclusive, the per-point diffusion number; Dirichlet axes, arith "exact" or
         # "fma", no source): replaces r (:func:`_ftcs_step_rmap`). None: today's function.
@@ -216,13 +257,18 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
 
 def ftcs(problem: Problem, nsteps: int | None = None, dtype=np.float64, T0: np.ndarray | None = None,
          arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
-         source: np.ndarray | None = None, rmap: np.ndarray | None = None) -> np.ndarray:
+         source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None) -> np.ndarray:
     """Run FTCS; returns the frame-inclusive field (frame entries on periodic
     / insulated axes: wrap / edge images of the returned owned points).
     source: a heat source added at every step (:func:`ftcs_step`).
-    rmap: a diffusivity map in place of problem.r (:func:`ftcs_step`)."""
+    rmap: a diffusivity map in place of problem.r (:func:`ftcs_step`).
+    faces: (RX, RY) per-face diffusion numbers, the conservative form (:func:`ftcs_step`)."""
     T = initial_field(problem, dtype) if T0 is None else T0.astype(dtype)
     n = problem.ntime if nsteps is None else nsteps
+    if faces is not None:
+        for _ in range(n):
+            T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source, rmap, faces)
+        return T
     if rmap is not None:
         for _ in range(n):
             T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source, rmap)

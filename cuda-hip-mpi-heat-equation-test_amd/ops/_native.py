@@ -101,6 +101,7 @@ class Config(C.Structure):
         ("bc_x", C.c_int32), ("bc_y", C.c_int32),
         ("source", C.c_int32),  # 1: the solver carries a heat source
         ("rmap", C.c_int32),  # 1: the solver carries a diffusivity map
+        ("faces", C.c_int32), ("pad1", C.c_int32),  # faces = 1: the solver carries per-face diffusion numbers
     ]
 
 
@@ -206,6 +207,12 @@ _SIGS = {
     "heat2d_solver_rmap": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "heat2d_tb_var": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, _P, _I64, C.c_int, _P]),
     "heat2d_cpu_tb_var": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_int, _P]),
+    "heat2d_solver_set_faces": (C.c_int, [_P, _P, _P, _I64]),
+    "heat2d_group_set_faces": (C.c_int, [_P, _P, _P, _I64]),
+    "heat2d_solver_faces": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "heat2d_tb_div": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, _P, _I64, C.c_int, _P, _P]),
+    "heat2d_cpu_tb_div": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_int, _P, _P]),
+    "heat2d_plan_max_grid_faces": (C.c_int, [C.c_int, C.c_int, _I64, C.c_int, C.c_int, C.c_int, C.POINTER(_I64)]),
     "heat2d_solver_compare": (C.c_int, [_P, _P, _I64, _I64, _I64, _P]),
     "heat2d_solver_footprint": (C.c_int, [C.POINTER(Config), C.c_int, C.c_int, C.POINTER(_I64)]),
     "heat2d_plan_max_grid": (C.c_int, [C.c_int, C.c_int, _I64, C.POINTER(_I64)]),

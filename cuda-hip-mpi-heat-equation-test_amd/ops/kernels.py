@@ -87,7 +87,7 @@ def init_field(field: torch.Tensor, layout: N.Layout, ic, xcoord: np.ndarray,
 def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: float,
             rows: Optional[tuple[int, int]] = None, tile_rows: int = 0, arith: str = "exact",
             bc_x: str = "dirichlet", bc_y: str = "dirichlet", source: Optional[torch.Tensor] = None,
-            rmap: Optional[torch.Tensor] = None) -> None:
+            rmap: Optional[torch.Tensor] = None, faces: Optional[tuple] = None) -> None:
     """dst[rows] = k FTCS steps of src (temporal-blocked kernel). The k ghost rows
     around ``rows`` must be valid in ``src``; Dirichlet rows/cols are kept.
     ``arith``: "exact" (reference rounding), "fma" (contracted update) or
@@ -112,9 +112,36 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
     multiplier of every point's update at every fused level; ``r`` is then not
     used. Dirichlet axes, arith "exact" / "fma" ("auto" is exact), no
     ``source``; on the device k is at most ``kMaxTBVar``
-    (``HeatSolver.info()["rmap"]["max_tb"]``)."""
+    (``HeatSolver.info()["rmap"]["max_tb"]``).
+    ``faces``: ``(rx, ry)``, the per-face diffusion numbers of the conservative
+    form div(k grad u) in the field's layout, dtype and device
+    (:func:`faces_field`); ``r`` is then not used. Dirichlet axes, arith
+    "exact" / "fma" ("auto" is exact), no ``source`` and no ``rmap``; on the
+    device k is at most ``kMaxTBDiv`` (``HeatSolver.info()["faces"]["max_tb"]``)."""
     _check_field(src, layout)
     _check_field(dst, layout)
+    if faces is not None:
+        rx, ry = faces
+        for f in (rx, ry):
+            _check_field(f, layout)
+            if f.dtype != src.dtype or f.device != src.device:
+                raise ValueError("faces dtype/device mismatch")
+        if source is not None or rmap is not None:
+            raise ValueError("face coefficients together with a heat source or a diffusivity map: no kernel carries them")
+        if bc_x != "dirichlet" or bc_y != "dirichlet":
+            raise ValueError("face coefficients need Dirichlet boundaries on both axes")
+        if arith not in ("exact", "fma", "auto"):
+            raise ValueError("face coefficients need arith 'exact', 'fma' or 'auto'")
+        rb, re = (0, layout.nrows) if rows is None else rows
+        ar = N.ARITH["fma"] if arith == "fma" else N.ARITH["exact"]
+        if src.is_cuda:
+            N.call("heat2d_tb_div", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                   C.byref(layout), rb, re, k, _stream(src), tile_rows, ar, C.c_void_p(rx.data_ptr()),
+                   C.c_void_p(ry.data_ptr()))
+        else:
+            N.call("heat2d_cpu_tb_div", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                   C.byref(layout), rb, re, k, ar, C.c_void_p(rx.data_ptr()), C.c_void_p(ry.data_ptr()))
+        return
     if rmap is not None:
         _check_field(rmap, layout)
         if rmap.dtype != src.dtype or rmap.device != src.device:
@@ -195,6 +222,30 @@ def rmap_field(R: np.ndarray, layout: N.Layout, dtype: torch.dtype, device="cpu"
         if 0 <= g < layout.nrows_global:
             f[i + layout.halo, layout.cpad:layout.cpad + layout.ncols] = Rd[g + 1, 1:-1]
     return f.reshape(-1).to(device)
+
+
+def faces_field(RX: np.ndarray, RY: np.ndarray, layout: N.Layout, dtype: torch.dtype, device="cpu") -> tuple:
+    """The two face-coefficient buffers :func:`tb_step` takes, from the GLOBAL
+    frame-inclusive arrays ``RX``, ``RY`` ((nrows_global + 2) x (ncols + 2)):
+    +0.0 everywhere, then the used faces of every allocated row of the slab —
+    rx: the owned rows, columns -1 (the frame column's east face) .. ncols - 1;
+    ry: rows -1 (the frame row's south face) .. nrows_global - 1, the owned
+    columns."""
+    out = []
+    for w, A in enumerate((RX, RY)):
+        if A.shape != (layout.nrows_global + 2, layout.ncols + 2):
+            raise ValueError(f"faces must be {(layout.nrows_global + 2, layout.ncols + 2)}, got {A.shape}")
+        f = torch.zeros((layout.rows_alloc(), layout.pitch), dtype=dtype)
+        Ad = torch.as_tensor(np.ascontiguousarray(A)).to(dtype)
+        c = layout.cpad
+        for i in range(-layout.halo, layout.nrows + layout.halo):
+            g = layout.row0 + i
+            if w == 0 and 0 <= g < layout.nrows_global:
+                f[i + layout.halo, c - 1:c + layout.ncols] = Ad[g + 1, 0:-1]
+            if w == 1 and -1 <= g < layout.nrows_global:
+                f[i + layout.halo, c:c + layout.ncols] = Ad[g + 1, 1:-1]
+        out.append(f.reshape(-1).to(device))
+    return tuple(out)
 
 
 WRAP_COLS = 24  # ghost columns per side that wrap_cols fills (kernels.hpp kWrapCols)

@@ -70,6 +70,12 @@ def build_parser():
                          "wrong shape fails), used in place of r at every point; 0 holds a point. Dirichlet axes, engine "
                          "tb, arith exact / fma (auto is exact), not with --source. Checkpoints record its SHA-256; a "
                          "restart needs the same file again")
+    ap.add_argument("--faces", default=None, metavar="FILE.npy",
+                    help="conservative conduction u_t = div(k grad u): the (2, n+2, n+2) array of per-face diffusion "
+                         "numbers (RX, then RY; heat2d.faces_from_k), already multiplied by dt / dx^2 (converted to the "
+                         "run's dtype; a wrong shape fails); a zero face is a wall. Dirichlet axes, engine tb, arith "
+                         "exact / fma (auto is exact), not with --source or --rmap. Checkpoints record its SHA-256; a "
+                         "restart needs the same file again")
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--ntime", type=int, default=None)
     ap.add_argument("--print-every", type=int, default=0)
@@ -252,6 +258,20 @@ def run(argv=None) -> int:
             print(f"warning: max r = {rmax:.6g} > 0.25: FTCS is unstable in 2-D", file=sys.stderr)
         if arith == "auto":
             arith = "exact"  # (as the solver and the CLI resolve it with a map)
+    faces = None
+    if a.faces:
+        import numpy as np
+        from ..models.heat2d import faces_sum_max
+        fa = np.load(a.faces, allow_pickle=False)
+        m = prob.n_owned + 2
+        if fa.shape != (2, m, m):
+            raise SystemExit(f"heat2d: --faces {a.faces}: shape {fa.shape}, the face coefficients of this grid are {(2, m, m)}")
+        faces = (fa[0], fa[1])
+        smax = faces_sum_max(fa[0], fa[1])
+        if smax > 1.0 + 1e-12 and root:
+            print(f"warning: max face sum = {smax:.6g} > 1: FTCS is unstable in 2-D", file=sys.stderr)
+        if arith == "auto":
+            arith = "exact"  # (as the solver and the CLI resolve it with face coefficients)
     # (with a source auto stays with the solver: fma when r is a power of two, else exact — never jacobi)
     if arith == "auto" and prob.r == 0.25 and prob.ic.sterbenz_safe() and not a.restart and engine == "tb" \
             and source is None:
@@ -289,7 +309,7 @@ def run(argv=None) -> int:
     if a.edge_shift not in ("auto", "measure"):
         edge_shift = int(a.edge_shift)
     elif world >= 3 and (backend == "hip" or a.edge_shift == "measure") and engine == "tb" and \
-            bc["bc_x"] != "periodic" and source is None and rmap is None:  # (periodic x: no edge slabs; the probe slabs carry no source / map)
+            bc["bc_x"] != "periodic" and source is None and rmap is None and faces is None:  # (periodic x: no edge slabs; the probe slabs carry no source / map)
         edge_shift = _measure_edge_shift(prob, a, rank, world, local, backend, kinds[0], engine, arith,
                                          min(nsteps, 48), root and not a.quiet)
 
@@ -297,7 +317,7 @@ def run(argv=None) -> int:
         return HeatSolver(prob, dtype=a.dtype, backend=backend, tb=a.tb, overlap=not a.no_overlap,
                           copy_swap=a.copy_swap, managed=a.managed or var.managed, graph=a.graph, transport=tr,
                           device=local if backend == "hip" else None, engine=engine, arith=arith,
-                          edge_shift=edge_shift, source=source, rmap=rmap, **bc)
+                          edge_shift=edge_shift, source=source, rmap=rmap, faces=faces, **bc)
 
     tr, s, kind, fallback = _make_solver(kinds, make_transport, make_solver, world)
     if fallback and root and not a.quiet:

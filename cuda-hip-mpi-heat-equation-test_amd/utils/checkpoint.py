@@ -124,6 +124,9 @@ def save(solver, directory: str, step: Optional[int] = None, extra: Optional[dic
         # only when there is one, so saves without a map keep their key set
         if getattr(solver, "rmap_sha256", None) is not None:
             meta["rmap_sha256"] = solver.rmap_sha256
+        # ... and the face coefficients of the conservative form (HeatSolver.faces_sha256)
+        if getattr(solver, "faces_sha256", None) is not None:
+            meta["faces_sha256"] = solver.faces_sha256
         meta.update(extra or {})
         _write_atomic(os.path.join(sd, "meta.json"), json.dumps(meta, indent=1))
         _write_atomic(os.path.join(directory, "latest"), os.path.basename(sd) + "\n")  # the commit point
@@ -178,6 +181,14 @@ def load(solver, directory: str) -> dict:
             raise ValueError("the checkpoint was written with a diffusivity map: give the restart the same rmap "
                              f"(sha256 {saved})")
         raise ValueError(f"the restart's diffusivity map differs from the checkpoint's (sha256 {have} != {saved})")
+    have, saved = getattr(solver, "faces_sha256", None), meta.get("faces_sha256")  # (absent: none)
+    if saved != have:
+        if saved is None:
+            raise ValueError("the checkpoint was written without face coefficients, this run has them")
+        if have is None:
+            raise ValueError("the checkpoint was written with face coefficients: give the restart the same faces "
+                             f"(sha256 {saved})")
+        raise ValueError(f"the restart's face coefficients differ from the checkpoint's (sha256 {have} != {saved})")
     want = "fp64" if solver.np_dtype == np.float64 else "fp32"
     if meta["dtype"] != want:
         raise ValueError(f"checkpoint dtype {meta['dtype']} != solver dtype {want}")

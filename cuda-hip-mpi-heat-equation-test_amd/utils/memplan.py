@@ -43,24 +43,27 @@ def mem_info(device: int = 0) -> tuple:
 
 
 def footprint(n: int, nranks: int = 1, dtype: str = "fp32", rank: int = 0, backend: str = "hip",
-              source: bool = False, rmap: bool = False) -> dict:
+              source: bool = False, rmap: bool = False, faces: bool = False) -> dict:
     """Device bytes of one rank's solver for an n x n grid on nranks ranks:
     {"field_bytes", "work_bytes", "total_bytes"} (the constructor's allocations).
     source: a solver with a heat source (a third buffer in the field's layout);
-    rmap: one with a diffusivity map (one more)."""
+    rmap: one with a diffusivity map (one more); faces: one with per-face
+    diffusion numbers (two more)."""
     cfg = N.Config()
     cfg.n_rows = cfg.n_cols = int(n)
     cfg.dtype = DTYPES[dtype]
     cfg.backend = N.BACKEND_HIP if backend == "hip" else N.BACKEND_CPU
     cfg.source = int(bool(source))
     cfg.rmap = int(bool(rmap))
+    cfg.faces = int(bool(faces))
     out = (C.c_int64 * 3)()
     N.call("heat2d_solver_footprint", C.byref(cfg), int(rank), int(nranks), out)
     return {"field_bytes": out[0], "work_bytes": out[1], "total_bytes": out[2]}
 
 
 def plan_max_grid(dtype: str = "fp32", nranks: int = 1, free_bytes: Optional[int] = None, device: int = 0,
-                  reserve: Optional[int] = None, source: bool = False, rmap: bool = False) -> dict:
+                  reserve: Optional[int] = None, source: bool = False, rmap: bool = False,
+                  faces: bool = False) -> dict:
     """The largest n x n grid of ``dtype`` whose largest slab on ``nranks``
     ranks fits ``free_bytes`` (default: this device's hipMemGetInfo free
     memory) minus ``reserve`` (default: reserve_bytes(free)). Returns {"n",
@@ -69,8 +72,8 @@ def plan_max_grid(dtype: str = "fp32", nranks: int = 1, free_bytes: Optional[int
     free = mem_info(device)[0] if free_bytes is None else int(free_bytes)
     res = reserve_bytes(free) if reserve is None else int(reserve)
     n = C.c_int64()
-    N.call("heat2d_plan_max_grid_ext", DTYPES[dtype], int(nranks), int(free - res), int(bool(source)), int(bool(rmap)),
-           C.byref(n))
-    fp = footprint(n.value, nranks, dtype, source=source, rmap=rmap)["total_bytes"]
+    N.call("heat2d_plan_max_grid_faces", DTYPES[dtype], int(nranks), int(free - res), int(bool(source)),
+           int(bool(rmap)), int(bool(faces)), C.byref(n))
+    fp = footprint(n.value, nranks, dtype, source=source, rmap=rmap, faces=faces)["total_bytes"]
     return {"n": int(n.value), "nranks": int(nranks), "dtype": dtype, "free_bytes": free, "reserve_bytes": res,
             "footprint_bytes": fp, "fraction_of_free": fp / free if free > 0 else 0.0}
