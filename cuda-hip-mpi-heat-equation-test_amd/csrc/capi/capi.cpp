@@ -18,6 +18,7 @@
 
 #include "heat2d/config.hpp"
 #include "heat2d/plan_cache.hpp"
+#include "heat2d/probe.hpp"
 #include "heat2d/runtime.hpp"
 #include "heat2d/watchdog.hpp"
 
@@ -482,6 +483,64 @@ int heat2d_solver_faces(void* s, int32_t* out3) {
     out3[0] = static_cast<Solver*>(s)->config().faces;
     out3[1] = static_cast<Solver*>(s)->has_faces() ? 1 : 0;
     out3[2] = kMaxTBDiv;
+  });
+}
+
+int heat2d_solver_set_probes(void* s, const int64_t* points, int64_t count, int64_t capacity) {
+  return guarded([&] { static_cast<Solver*>(s)->set_probes(points, count, capacity); });
+}
+
+int heat2d_group_set_probes(void* g, const int64_t* points, int64_t count, int64_t capacity) {
+  return guarded([&] { static_cast<LoopbackGroup*>(g)->set_probes(points, count, capacity); });
+}
+
+int heat2d_solver_probes(void* s, int64_t* out4) {
+  return guarded([&] {
+    Solver* so = static_cast<Solver*>(s);
+    out4[0] = so->probe_count();
+    out4[1] = so->probe_capacity();
+    out4[2] = so->probe_recorded();
+    out4[3] = kMaxProbes;
+  });
+}
+
+int heat2d_solver_probe_index(void* s, int64_t* out) {
+  return guarded([&] {
+    const std::vector<int64_t>& idx = static_cast<Solver*>(s)->probe_index();
+    std::copy(idx.begin(), idx.end(), out);
+  });
+}
+
+int heat2d_solver_probe_history(void* s, void* host) {
+  return guarded([&] { static_cast<Solver*>(s)->probe_history(host); });
+}
+
+int heat2d_solver_clear_probe_history(void* s) {
+  return guarded([&] { static_cast<Solver*>(s)->clear_probe_history(); });
+}
+
+int heat2d_probe_cone(int dtype, const void* src, const heat2d_layout* L, int k, double r, int arith, int bc,
+                      const void* source, const void* rmap, const void* rx, const void* ry, const int64_t* pts,
+                      int64_t P, void* out, void* stream, int on_device) {
+  return guarded([&] {
+    HEAT2D_REQUIRE((source != nullptr) + (rmap != nullptr) + (rx != nullptr) <= 1,
+                   "heat2d_probe_cone: at most one of source, rmap and faces");
+    HEAT2D_REQUIRE(!(source || rmap || rx) || bc == 0, "heat2d_probe_cone: coefficient buffers need Dirichlet axes");
+    kern::ProbeArgs a{};
+    a.src = src;
+    a.source = source;
+    a.rmap = rmap;
+    a.rx = rx;
+    a.ry = ry;
+    a.pts = pts;
+    a.hist = out;
+    a.capacity = k;
+    a.P = P;
+    a.r = r;
+    a.k = k;
+    kern::probe_bounds(a, to_layout(L), bc);
+    if (on_device) kern::launch_probe_cone((DType)dtype, a, arith, as_stream(stream));
+    else cpu::probe_cone((DType)dtype, a, arith);
   });
 }
 

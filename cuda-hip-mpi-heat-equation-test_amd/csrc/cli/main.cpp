@@ -91,6 +91,11 @@ struct Args {
   // --faces FILE.npy: the conservative form's per-face diffusion numbers, shape (2, n+2, n+2): RX then RY,
   // already multiplied by dt / dx^2 (SolverConfig::faces; converted to the run's dtype, a wrong shape fails)
   std::string faces;
+  // --probes FILE: probe points, a .npy integer array (P, 2) or text with two integers per line ('#'
+  // comments): owned points (i, j), 1 <= i, j <= n, whose temperature after every step goes to
+  // --probes-out FILE.npy (default probes.npy), written by the root rank at the end of the run
+  std::string probes;
+  std::string probes_out = "probes.npy";
 };
 
 void usage() {
@@ -103,7 +108,8 @@ void usage() {
       "              [--checkpoint DIR [--checkpoint-every N]] [--restart DIR]\n"
       "              [--transport auto|rccl|peer] [--share-gpu] [--autotune auto|on|off] [--edge-shift N]\n"
       "              [--bc-x dirichlet|periodic|insulated] [--bc-y dirichlet|periodic|insulated]\n"
-      "              [--source FILE.npy] [--rmap FILE.npy] [--faces FILE.npy]\n");
+      "              [--source FILE.npy] [--rmap FILE.npy] [--faces FILE.npy]\n"
+      "              [--probes FILE [--probes-out FILE.npy]]\n");
 }
 
 Args parse_args(int argc, char** argv) {
@@ -151,6 +157,8 @@ Args parse_args(int argc, char** argv) {
     else if (s == "--source") a.source = need("--source");
     else if (s == "--rmap") a.rmap = need("--rmap");
     else if (s == "--faces") a.faces = need("--faces");
+    else if (s == "--probes") a.probes = need("--probes");
+    else if (s == "--probes-out") a.probes_out = need("--probes-out");
     else if (s == "--bc-x" || s == "--bc-y") {
       const std::string v = need(s.c_str());
       if (v != "dirichlet" && v != "periodic" && v != "insulated") {
@@ -214,7 +222,88 @@ struct Shared {
   // --faces: the same for the face coefficients (RX, then RY)
   std::vector<char> faces;
   std::string faces_sha256;
+  // --probes: the global point list (read by the first rank to need it, under mu) and the merged
+  // history, probe_rows x P in the run's dtype, every rank's columns at their place in the list
+  std::vector<int64_t> probes;
+  bool probes_read = false;
+  std::vector<char> probe_hist;
+  int64_t probe_rows = 0;
 };
+
+// --probes FILE: P pairs (i, j) from a .npy integer array of shape (P, 2) (little-endian or one-byte
+// integers, C order) or from text with two integers per line and '#' comments; every point an owned
+// point of the n x n grid, at most kMaxProbes of them.
+std::vector<int64_t> read_probes(const std::string& path, int64_t n) {
+  FILE* f = std::fopen(path.c_str(), "rb");
+  HEAT2D_REQUIRE(f != nullptr, "--probes " + path + ": cannot open");
+  std::string data;
+  char buf[1 << 16];
+  for (size_t got; (got = std::fread(buf, 1, sizeof(buf), f)) > 0;) data.append(buf, got);
+  std::fclose(f);
+  std::vector<int64_t> pts;
+  if (data.size() >= 10 && std::memcmp(data.data(), "\x93NUMPY", 6) == 0) {
+    const unsigned char* u = reinterpret_cast<const unsigned char*>(data.data());
+    const bool v1 = u[6] == 1;
+    HEAT2D_REQUIRE(v1 || data.size() >= 12, "--probes " + path + ": truncated header");
+    const size_t hlen = v1 ? (size_t)u[8] | ((size_t)u[9] << 8)
+                           : (size_t)u[8] | ((size_t)u[9] << 8) | ((size_t)u[10] << 16) | ((size_t)u[11] << 24);
+    const size_t off = (v1 ? 10 : 12) + hlen;
+    HEAT2D_REQUIRE(off <= data.size(), "--probes " + path + ": truncated header");
+    const std::string h = data.substr(v1 ? 10 : 12, hlen);
+    int bytes = 0;
+    bool sign = true;
+    for (const char* d : {"<i8", "<i4", "<i2", "|i1", "<u8", "<u4", "<u2", "|u1"})
+      if (h.find(std::string("'") + d + "'") != std::string::npos) {
+        bytes = d[2] - '0';
+        sign = d[1] == 'i';
+      }
+    HEAT2D_REQUIRE(bytes > 0, "--probes " + path + ": the array is not of an integer dtype");
+    HEAT2D_REQUIRE(h.find("'fortran_order': False") != std::string::npos, "--probes " + path + ": Fortran-ordered array");
+    const size_t sp = h.find("'shape':");
+    long long P = 0, two = 0;
+    char close = 0;
+    HEAT2D_REQUIRE(sp != std::string::npos && std::sscanf(h.c_str() + sp, "'shape': (%lld, %lld%c", &P, &two, &close) == 3 &&
+                       close == ')' && two == 2 && P >= 0,
+                   "--probes " + path + ": the array must have shape (P, 2)");
+    HEAT2D_REQUIRE(data.size() - off >= (size_t)(2 * P * bytes), "--probes " + path + ": truncated data");
+    for (long long k = 0; k < 2 * P; ++k) {
+      const unsigned char* q = u + off + (size_t)k * bytes;
+      uint64_t v = 0;
+      for (int b = 0; b < bytes; ++b) v |= (uint64_t)q[b] << (8 * b);
+      if (sign && bytes < 8 && (v >> (8 * bytes - 1))) v |= ~uint64_t(0) << (8 * bytes);  // sign-extend
+      pts.push_back((int64_t)v);
+    }
+  } else {
+    size_t pos = 0;
+    int line_no = 0;
+    while (pos < data.size()) {
+      size_t end = data.find('\n', pos);
+      if (end == std::string::npos) end = data.size();
+      std::string line = data.substr(pos, end - pos);
+      pos = end + 1;
+      ++line_no;
+      const size_t hash = line.find('#');
+      if (hash != std::string::npos) line.resize(hash);
+      if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+      const char* c = line.c_str();
+      char* e1 = nullptr;
+      char* e2 = nullptr;
+      const long long i = std::strtoll(c, &e1, 10);
+      const long long j = e1 != c ? std::strtoll(e1, &e2, 10) : 0;
+      HEAT2D_REQUIRE(e1 != c && e2 != e1 && std::string(e2).find_first_not_of(" \t\r") == std::string::npos,
+                     "--probes " + path + ": line " + std::to_string(line_no) + ": two integers per line");
+      pts.push_back(i);
+      pts.push_back(j);
+    }
+  }
+  HEAT2D_REQUIRE((int64_t)pts.size() / 2 <= kMaxProbes,
+                 "--probes " + path + ": " + std::to_string(pts.size() / 2) + " points, at most " + std::to_string(kMaxProbes));
+  for (size_t k = 0; k < pts.size(); ++k)
+    HEAT2D_REQUIRE(pts[k] >= 1 && pts[k] <= n, "--probes " + path + ": point " + std::to_string(k / 2) + " = (" +
+                                                   std::to_string(pts[k & ~size_t(1)]) + ", " + std::to_string(pts[k | 1]) +
+                                                   ") is not an owned point (1.." + std::to_string(n) + ")");
+  return pts;
+}
 
 // Collective checkpoint (every rank its slab, then rank 0 publishes meta.json).
 void save_checkpoint(Shared& sh, Solver& s, Transport& tr, int rank, int64_t step) {
@@ -448,6 +537,16 @@ void run_rank(Shared& sh, int rank) {
         if (!a.quiet) std::printf(" restarted from %s at step %lld\n", a.restart.c_str(), (long long)start);
       }
     }
+    if (!a.probes.empty()) {  // (after a restart's upload: the history is not checkpointed, it starts at `start`)
+      {
+        std::lock_guard<std::mutex> g(sh.mu);
+        if (!sh.probes_read) {
+          sh.probes = read_probes(a.probes, sh.prob.n_owned);
+          sh.probes_read = true;
+        }
+      }
+      s.set_probes(sh.probes.data(), (int64_t)sh.probes.size() / 2, std::max<int64_t>(1, sh.in.ntime - start));
+    }
     if (root && !a.quiet) {
       // (fortran/hip prints the decomposition line; fortran/mpi+cuda only nx / ny)
       if (P > 1 || sh.args.variant == "mpi") std::printf(" Automatic MPI decomposition: %12d  x 1\n", P);
@@ -565,6 +664,31 @@ void run_rank(Shared& sh, int rank) {
     }
 
     if (!a.checkpoint.empty()) save_checkpoint(sh, s, *tr, rank, done);  // final state (outside the timed region)
+
+    // --probes: every rank's columns merged at their place in the list; the root rank writes
+    // the file, whatever `soln` and --output say
+    if (!a.probes.empty() && !sh.probes.empty()) {
+      IoPhase io(*tr);
+      const size_t es = dtype_size(s.dtype());
+      const int64_t P = (int64_t)sh.probes.size() / 2, cnt = s.probe_count(), rec = s.probe_recorded();
+      std::vector<char> part((size_t)(rec * cnt) * es);
+      s.probe_history(part.data());
+      {
+        std::lock_guard<std::mutex> g(sh.mu);
+        if (sh.probe_hist.empty()) {
+          sh.probe_hist.assign((size_t)(rec * P) * es, 0);
+          sh.probe_rows = rec;
+        }
+        HEAT2D_REQUIRE(sh.probe_rows == rec, "the ranks recorded different numbers of probe rows");
+        const std::vector<int64_t>& idx = s.probe_index();
+        for (int64_t q = 0; q < rec; ++q)
+          for (int64_t c = 0; c < cnt; ++c)
+            std::memcpy(sh.probe_hist.data() + (size_t)(q * P + idx[(size_t)c]) * es, part.data() + (size_t)(q * cnt + c) * es, es);
+      }
+      tr->barrier();
+      if (root && heat2d_write_npy(a.probes_out.c_str(), (int)s.dtype(), sh.probe_hist.data(), sh.probe_rows, P, P))
+        fail(__FILE__, __LINE__, heat2d_last_error());
+    }
 
     // outputs (serial rank turns / per-rank files: ranks wait on each other's I/O)
     if (a.output != "none") {

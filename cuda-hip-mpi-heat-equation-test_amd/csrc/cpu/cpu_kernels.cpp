@@ -12,6 +12,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "heat2d/probe.hpp"
 #include "heat2d/runtime.hpp"
 
 namespace heat2d {
@@ -414,6 +415,59 @@ void unpack_rows(DType dt, void* field, const SlabLayout& L, int64_t row, int64_
   for (int64_t i = 0; i < nrows; ++i)
     std::memcpy(static_cast<char*>(field) + (size_t)L.offset(row + i, 0) * es,
                 static_cast<const char*>(buf) + (size_t)(i * L.ncols) * es, (size_t)L.ncols * es);
+}
+
+// Twin of kernels/probe_cone.hip: the same levels over the same two planes,
+// one probe after the other, through the shared probe_point (heat2d/probe.hpp).
+namespace {
+template <typename T, int MODE, int AR>
+void probe_cone_run(const kern::ProbeArgs& a) {
+  constexpr int S = kern::kProbeSide;
+  std::vector<T> planes((size_t)2 * S * S, T(0));
+  T* plane[2] = {planes.data(), planes.data() + S * S};
+  const T* src = static_cast<const T*>(a.src);
+  T* hist = static_cast<T*>(a.hist);
+  const int k = a.k, side = 2 * k + 1;
+  const int64_t base = (a.base ? *a.base : 0) + a.base0;
+  for (int64_t p = 0; p < a.P; ++p) {
+    const int64_t ci = a.pts[2 * p], cj = a.pts[2 * p + 1];
+    for (int idx = 0; idx < side * side; ++idx) {
+      const int u = idx / side, v = idx % side;
+      const int64_t row = ci - k + u, col = cj - k + v;
+      if (kern::probe_loads(a, row, col)) plane[0][u * S + v] = src[a.L.offset(row, col)];
+    }
+    for (int s = 1; s <= k; ++s) {
+      const int w = 2 * (k - s) + 1;
+      for (int idx = 0; idx < w * w; ++idx)
+        kern::probe_point<T, MODE, AR>(a, ci, cj, s, idx, plane[(s - 1) & 1], plane[s & 1]);
+      if (base + s - 1 < a.capacity) hist[(base + s - 1) * a.P + p] = plane[s & 1][k * S + k];
+    }
+  }
+}
+template <typename T, int MODE>
+void probe_cone_mode(const kern::ProbeArgs& a, int arith) {
+  if (arith == 0) probe_cone_run<T, MODE, 0>(a);
+  else if (arith == 1) probe_cone_run<T, MODE, 1>(a);
+  else if constexpr (MODE == kern::kProbePlain) probe_cone_run<T, MODE, 2>(a);
+  else fail(__FILE__, __LINE__, "probe_cone: a source, a map or faces take arith exact or fma");
+}
+template <typename T>
+void probe_cone_typed(const kern::ProbeArgs& a, int arith) {
+  if (a.source) probe_cone_mode<T, kern::kProbeSource>(a, arith);
+  else if (a.rmap) probe_cone_mode<T, kern::kProbeMap>(a, arith);
+  else if (a.rx) probe_cone_mode<T, kern::kProbeFaces>(a, arith);
+  else probe_cone_mode<T, kern::kProbePlain>(a, arith);
+}
+}  // namespace
+
+void probe_cone(DType dt, const kern::ProbeArgs& a, int arith) {
+  if (a.P <= 0) return;
+  HEAT2D_REQUIRE(a.P <= kMaxProbes, "probe_cone: more than kMaxProbes points");
+  HEAT2D_REQUIRE(a.k >= 1 && a.k <= kMaxTB && a.k <= a.L.halo, "probe_cone: depth outside [1, min(kMaxTB, halo)]");
+  HEAT2D_REQUIRE(arith >= 0 && arith <= 2, "probe_cone: arith exact (0), fma (1) or jacobi (2)");
+  HEAT2D_REQUIRE((a.rx == nullptr) == (a.ry == nullptr), "probe_cone: both face buffers or neither");
+  if (dt == DType::F64) probe_cone_typed<double>(a, arith);
+  else probe_cone_typed<float>(a, arith);
 }
 
 }  // namespace cpu

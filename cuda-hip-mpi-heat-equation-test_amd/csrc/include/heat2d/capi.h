@@ -219,6 +219,29 @@ int heat2d_tb_div(int dtype, const void* src, void* dst, const heat2d_layout* L,
                   void* stream, int64_t tile_rows, int arith, const void* rx, const void* ry);
 int heat2d_cpu_tb_div(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                       int arith, const void* rx, const void* ry);
+/* Probe points (runtime.hpp Solver::set_probes): the temperature at `count` owned points after EVERY
+   step, the levels inside a fused pass included. `points`: count pairs (i, j) of GLOBAL frame-inclusive
+   indices (1..n), duplicates allowed, count <= kMaxProbes; the rank keeps the points whose row it owns.
+   The history holds `capacity` steps; a step that would overflow it fails before it launches anything.
+   count = 0 clears the probes. Not with arith 3, engine 1 or copy_swap. Between steps. */
+int heat2d_solver_set_probes(void* s, const int64_t* points, int64_t count, int64_t capacity);
+int heat2d_group_set_probes(void* g, const int64_t* points, int64_t count, int64_t capacity);
+/* out4 = {this rank's probes, capacity, recorded steps, kMaxProbes} */
+int heat2d_solver_probes(void* s, int64_t* out4);
+/* positions of this rank's probes in the list heat2d_solver_set_probes was given (out: >= count entries) */
+int heat2d_solver_probe_index(void* s, int64_t* out);
+/* the recorded rows, recorded x count elements of the field's dtype, row q = after step q + 1 (synchronises) */
+int heat2d_solver_probe_history(void* s, void* host);
+/* recorded = 0 (the probes stay) */
+int heat2d_solver_clear_probe_history(void* s);
+/* The cone kernel alone (kernels/probe_cone.hip; on_device = 0: its CPU twin): k levels from the patches
+   of `src` (allocation base, layout L) around P points given as pairs (local row, column) of owned
+   points — device memory when on_device —, the centre after level s in out[(s - 1) * P + p] (k x P
+   elements of dtype). arith 0 / 1 / 2 (2: no coefficient buffer), bc as heat2d_tb_bc, at most one of
+   source / rmap / (rx, ry) in the field's layout; k <= L.halo ghost rows valid around every point. */
+int heat2d_probe_cone(int dtype, const void* src, const heat2d_layout* L, int k, double r, int arith, int bc,
+                      const void* source, const void* rmap, const void* rx, const void* ry, const int64_t* pts,
+                      int64_t P, void* out, void* stream, int on_device);
 /* any rectangle of the current field, local rows [r0, r1) x columns [c0, c1), ghost / frame included */
 int heat2d_solver_download_region(void* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, void* host, int64_t ld);
 // memory-fit planner (runtime.hpp solver_footprint / plan_max_grid): out3 =

@@ -63,6 +63,9 @@ constexpr int kMaxTBVar = 16;
 // Deepest pass of the conservative form (tb_kernel_div: depths 1..kMaxTBDiv, both
 // dtypes, exact and fma, none with scratch; a solver with face coefficients clamps to it).
 constexpr int kMaxTBDiv = 16;
+// Most probe points of one solver (Solver::set_probes: one probe_cone workgroup
+// per point and cycle).
+constexpr int kMaxProbes = 4096;
 // Default halo depth (ghost rows per side). Must be >= temporal depth used.
 constexpr int64_t kDefaultHalo = kMaxTB;
 

@@ -1,0 +1,151 @@
+// Probe points: the temperature at a few owned points after EVERY step of a
+// fused pass (kernels/probe_cone.hip, cpu::probe_cone).
+//
+// The value of a point after steps t+1 .. t+k depends only on the (2k+1)^2
+// patch around it at step t, and during the pass t -> t+k that patch sits
+// untouched in the pass's source buffer (the two fields ping-pong). The cone
+// code advances the patch k levels between two planes — level s updates the
+// points within radius k - s — with the golden's operations in the golden's
+// order (models/reference.py ftcs_step), and stores the centre after every
+// level. The march kernels are not involved.
+//
+// This header holds what the device kernel and its CPU twin share: the
+// argument block and the update of one point.
+#pragma once
+
+#include <cmath>
+
+#include "heat2d/kernels.hpp"
+
+namespace heat2d {
+namespace kern {
+
+// planes of (2 kMaxTB + 1)^2 elements
+constexpr int kProbeSide = 2 * kMaxTB + 1;
+
+enum ProbeMode : int { kProbePlain = 0, kProbeSource = 1, kProbeMap = 2, kProbeFaces = 3 };
+
+// One cone launch. Rows and columns are local indices of the slab layout L
+// (row -1 / column -1: the frame where the slab holds it).
+struct ProbeArgs {
+  const void* src;     // the cycle's source field (allocation base, layout L)
+  const void* source;  // MODE source: the per-step increment, in L's layout
+  const void* rmap;    // MODE map
+  const void* rx;      // MODE faces
+  const void* ry;
+  const int64_t* pts;  // P pairs (local row, column) of owned points
+  void* hist;          // H, capacity x P elements of the field's dtype
+  const int64_t* base; // history row of this cycle's first level (nullptr: 0)
+  int64_t base0;       // added to *base (the CPU twin passes the row here)
+  int64_t capacity;    // rows of H: a level at or beyond it is not stored
+  int64_t P;
+  SlabLayout L;
+  // the grid as the march sees it (bc_layout): the pinned frame rows / columns;
+  // out of the patch's reach on a periodic axis
+  int64_t frame_r0, frame_r1, frame_c0, frame_c1;
+  // insulated walls: the first / last owned row and column whose operand beyond
+  // the wall is the point's own value (INT64_MIN: none)
+  int64_t wall_r0, wall_r1, wall_c0, wall_c1;
+  double r;
+  int32_t k;
+};
+
+// The frame and wall lines of a slab under boundary bits `bc`.
+inline void probe_bounds(ProbeArgs& a, const SlabLayout& L, int bc) {
+  const SlabLayout Lk = bc_layout(L, bc);
+  const int64_t dc = L.cpad - Lk.cpad;  // the widened grid's column 0 is real column -dc
+  a.L = L;
+  a.frame_r0 = -1 - Lk.row0;
+  a.frame_r1 = Lk.nrows_global - Lk.row0;
+  a.frame_c0 = -1 - dc;
+  a.frame_c1 = Lk.ncols - dc;
+  const int64_t none = INT64_MIN;
+  a.wall_r0 = (bc & kBcInsulatedX) ? -L.row0 : none;
+  a.wall_r1 = (bc & kBcInsulatedX) ? L.nrows_global - 1 - L.row0 : none;
+  a.wall_c0 = (bc & kBcInsulatedY) ? 0 : none;
+  a.wall_c1 = (bc & kBcInsulatedY) ? L.ncols - 1 : none;
+}
+
+__host__ __device__ inline float probe_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__host__ __device__ inline double probe_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// One point's update (compiled with contraction off: every operation below
+// rounds on its own unless it is written as an fma). c: centre; s, e, n, w:
+// (i+1, j), (i, j+1), (i-1, j), (i, j-1); AR 0 exact, 1 fma, 2 jacobi.
+//   plain:  coef[0] = r
+//   source: coef[0] = r, coef[1] = S[i,j]
+//   map:    coef[0] = R[i,j]
+//   faces:  coef = RY[i,j], RX[i,j], RY[i-1,j], RX[i,j-1]
+template <typename T, int MODE, int AR>
+__host__ __device__ inline T probe_update(T c, T s, T e, T n, T w, const T* coef) {
+  if (MODE == kProbeFaces) {
+    const T ds = s - c, de = e - c, dn = n - c, dw = w - c;
+    if (AR == 1) return c + probe_fma(coef[3], dw, probe_fma(coef[2], dn, probe_fma(coef[1], de, coef[0] * ds)));
+    return c + (((coef[0] * ds + coef[1] * de) + coef[2] * dn) + coef[3] * dw);
+  }
+  const T sum = ((s + e) + n) + w;
+  const T r = coef[0];
+  T upd;
+  if (AR == 2) upd = r * sum;
+  else if (AR == 1) upd = probe_fma(r, probe_fma(T(-4), c, sum), c);
+  else upd = c + r * (sum - T(4) * c);
+  if (MODE == kProbeSource) upd = upd + coef[1];
+  return upd;
+}
+
+// Level s of one probe's cone, point `idx` of the (2 (k - s) + 1)^2 updated at
+// that level: from plane `in` into plane `out` (kProbeSide x kProbeSide).
+template <typename T, int MODE, int AR>
+__host__ __device__ inline void probe_point(const ProbeArgs& a, int64_t ci, int64_t cj, int s, int idx, const T* in,
+                                            T* out) {
+  const int w = 2 * (a.k - s) + 1;
+  const int u = s + idx / w, v = s + idx % w;  // plane coordinates
+  const int64_t row = ci - a.k + u, col = cj - a.k + v;
+  if (row < a.frame_r0 || row > a.frame_r1 || col < a.frame_c0 || col > a.frame_c1) return;  // off the grid
+  const int at = u * kProbeSide + v;
+  const T c = in[at];
+  if (row == a.frame_r0 || row == a.frame_r1 || col == a.frame_c0 || col == a.frame_c1) {
+    out[at] = c;  // a Dirichlet frame line (or the unread image line of an insulated axis)
+    return;
+  }
+  const T so = row == a.wall_r1 ? c : in[at + kProbeSide];
+  const T ea = col == a.wall_c1 ? c : in[at + 1];
+  const T no = row == a.wall_r0 ? c : in[at - kProbeSide];
+  const T we = col == a.wall_c0 ? c : in[at - 1];
+  T coef[4];
+  const int64_t o = a.L.offset(row, col);
+  if (MODE == kProbeFaces) {
+    const T* rx = static_cast<const T*>(a.rx);
+    const T* ry = static_cast<const T*>(a.ry);
+    coef[0] = ry[o];
+    coef[1] = rx[o];
+    coef[2] = ry[o - a.L.pitch];
+    coef[3] = rx[o - 1];
+  } else if (MODE == kProbeMap) {
+    coef[0] = static_cast<const T*>(a.rmap)[o];
+  } else {
+    coef[0] = (T)a.r;
+    if (MODE == kProbeSource) coef[1] = static_cast<const T*>(a.source)[o];
+  }
+  out[at] = probe_update<T, MODE, AR>(c, so, ea, no, we, coef);
+}
+
+// Whether patch point (row, col) is loaded: on the grid and inside the allocation.
+__host__ __device__ inline bool probe_loads(const ProbeArgs& a, int64_t row, int64_t col) {
+  return row >= a.frame_r0 && row <= a.frame_r1 && col >= a.frame_c0 && col <= a.frame_c1 && row >= -a.L.halo &&
+         row < a.L.nrows + a.L.halo && col >= -a.L.cpad && col < a.L.col_hi();
+}
+
+// The cone of every point, k levels from `src`, level s into H row base + s - 1.
+// mode: ProbeMode, from the buffers given (source, else rmap, else rx / ry).
+// Capture-safe; `base` is read on the device when the kernel runs.
+void launch_probe_cone(DType dt, const ProbeArgs& a, int arith, hipStream_t stream);
+// *base += k, one thread, behind a cone launch on the same stream.
+void launch_probe_advance(int64_t* base, int k, hipStream_t stream);
+
+}  // namespace kern
+
+namespace cpu {
+void probe_cone(DType dt, const kern::ProbeArgs& a, int arith);
+}  // namespace cpu
+}  // namespace heat2d

@@ -473,6 +473,33 @@ class Solver {
   // Between step() calls; drops the captured graphs.
   void set_faces(const void* rx, const void* ry, int64_t ld);
   bool has_faces() const { return faces_on_; }
+  // Probe points: the temperature at `count` owned points after EVERY step, the
+  // levels inside a fused pass included. `points` holds count pairs (i, j) of
+  // GLOBAL frame-inclusive indices, 1 <= i <= nrows_global, 1 <= j <= ncols
+  // (duplicates allowed, count <= kMaxProbes); this rank keeps those whose row
+  // it owns. The history H is (capacity x local count) in the field's dtype:
+  // row q holds the values after step q + 1 counted from this call. One row is
+  // written per step taken by step() / step_stats() (and a LoopbackGroup's
+  // step), however the call is cut into cycles — every cycle_launch issues one
+  // probe_cone launch (heat2d/probe.hpp) on its band launch's stream, reading
+  // the cycle's source buffer, and a one-thread launch that advances the
+  // device-resident row base, so eager cycles and replayed graphs record alike
+  // with no host work per cycle. prepare(), autotuning trials and schedule
+  // rehearsals record nothing. A step(n) that would pass `capacity` rows raises
+  // before it launches anything. count = 0 clears the probes. Not with arith 3
+  // (fast), the jit engine or copy-swap. Between step() calls; drops the
+  // captured graphs (they hold or lack the cone launches).
+  void set_probes(const int64_t* points, int64_t count, int64_t capacity);
+  int64_t probe_count() const { return (int64_t)probe_idx_.size(); }  // this rank's
+  int64_t probe_capacity() const { return probe_cap_; }
+  int64_t probe_recorded() const { return probe_rec_; }
+  // positions of this rank's probes in the list set_probes was given
+  const std::vector<int64_t>& probe_index() const { return probe_idx_; }
+  // H's recorded rows -> host (probe_recorded() x probe_count(), packed); synchronises
+  void probe_history(void* host);
+  void clear_probe_history();  // recorded = 0
+  // raises if n more steps would overflow the history
+  void probe_room(int64_t n) const;
   // Cycles launched by step() since the last reset, by depth: hist[k] for
   // k = 0..kMaxTB (graph replays count their two cycles each).
   void cycle_hist(int64_t out[kMaxTB + 1], bool reset);
@@ -581,6 +608,17 @@ class Solver {
   const void* face_rx() const { return faces_on_ ? face_buf_[0] : nullptr; }
   const void* face_ry() const { return faces_on_ ? face_buf_[1] : nullptr; }
   void drop_graphs();         // captured graphs hold the kernels of the run with / without a source or map
+  // probe points (set_probes): this rank's points as (local row, column) pairs,
+  // the history and the device-resident row base (HIP) or their host twins
+  std::vector<int64_t> probe_idx_;      // positions in the caller's list; empty: no probes
+  std::vector<int64_t> probe_pts_;      // host copy of the local pairs
+  int64_t* d_probe_pts_ = nullptr;
+  void* probe_hist_ = nullptr;          // device (HIP) or host (CPU) memory
+  int64_t* d_probe_base_ = nullptr;
+  int64_t probe_cap_ = 0, probe_rec_ = 0;
+  void free_probes();
+  void set_probe_base();                // the device word <- probe_rec_ (synchronised)
+  void launch_probes(int k, hipStream_t stream);  // the cycle's cone (+ advance), from buf_[cur_]
   int cur_ = 0;
   int64_t steps_ = 0;
   int64_t band_ = 0;     // largest boundary band / halo exchange depth (= K)
@@ -665,6 +703,8 @@ class LoopbackGroup {
   void set_source(const void* host, int64_t ld);  // Solver::set_source on every member (the global array)
   void set_rmap(const void* host, int64_t ld);    // Solver::set_rmap on every member (the global array)
   void set_faces(const void* rx, const void* ry, int64_t ld);  // Solver::set_faces on every member (the global arrays)
+  // Solver::set_probes on every member (the global list: each keeps the points of its rows)
+  void set_probes(const int64_t* points, int64_t count, int64_t capacity);
   int nranks() const { return (int)members_.size(); }
   Solver& member(int i) { return *members_[i]; }
 

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "heat2d/plan_cache.hpp"
+#include "heat2d/probe.hpp"
 #include "heat2d/runtime.hpp"
 #include "heat2d/watchdog.hpp"
 
@@ -326,6 +327,7 @@ Solver::~Solver() {
     if (d_work_) (void)hipFree(d_work_);
     if (d_part_) (void)hipFree(d_part_);
     if (d_queue_) (void)hipFree(d_queue_);
+    free_probes();
     // the streams go before the events recorded on them (captures included)
     if (own_streams_) {
       (void)hipStreamDestroy(s_compute_);
@@ -342,6 +344,7 @@ Solver::~Solver() {
     std::free(src_buf_);
     std::free(rmap_buf_);
     for (auto& b : face_buf_) std::free(b);
+    free_probes();
   }
 }
 
@@ -505,6 +508,7 @@ void Solver::launch_stats_cycle(int k) {
   roctxRangePushA("heat2d.cycle.stats");
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_comm_, 0));
+  launch_probes(k, s_compute_);
   kern::launch_tb_stats(dtype(), buf_[cur_], buf_[cur_ ^ 1], L_, k, cfg_.r, d_part_,
                         d_work_ + kern::stats_work_elems(), s_compute_, cfg_.arith, bc_);
   H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
@@ -543,6 +547,7 @@ void Solver::cycle_finish() {
   pend_ = Pending::None;
   pend_pe_ = -1;
   steps_ += pend_k_;
+  if (probe_cap_ > 0) probe_rec_ += pend_k_;
   hist_[pend_k_] += 1;
   last_k_ = pend_k_;
   ghost_ = pend_x_;
@@ -560,6 +565,7 @@ void Solver::launch_serial(int k) {
   roctxRangePushA("heat2d.cycle.serial");
   PhaseEvents* pe = (timing_ && hip_) ? phase_begin(1) : nullptr;
   if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
+  launch_probes(k, s_compute_);
   cycle_compute(k);
   if (pe) H2D_HIP(hipEventRecord(pe->ev[4], s_compute_));
   if (tr_->exchanges()) {
@@ -1214,6 +1220,7 @@ void Solver::launch_overlap(int k, int64_t B) {
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));  // edge part c-1
     H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));     // main part c-1
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_comm_));
+    launch_probes(k, s_comm_);
     kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
     kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
@@ -1232,6 +1239,7 @@ void Solver::launch_overlap(int k, int64_t B) {
     // comm stream (cycle_finish) = [bands(c) done] exchange(c), beside the interior.
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_comm_, 0));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_compute_));
+    launch_probes(k, s_compute_);
     kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
@@ -1246,6 +1254,7 @@ void Solver::launch_overlap(int k, int64_t B) {
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));  // edge part c-1 (record not yet replaced)
   H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));     // main part c-1
   if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_comm_));
+  launch_probes(k, s_comm_);  // (ahead of the band launch in every order below)
   if (lead) {
     // lead: the band launch first (comm stream), then the interior beside it
     kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
@@ -1300,6 +1309,7 @@ void Solver::run_graph_cycles(int64_t npairs) {
   for (int64_t i = 0; i < npairs; ++i) H2D_HIP(hipGraphLaunch(graph_exec_, s_compute_));
   if (npairs > 0 && tr_->exchanges()) tr_->graph_launched(s_compute_);
   hist_[K] += 2 * npairs;
+  if (probe_cap_ > 0) probe_rec_ += 2 * npairs * K;
   if (npairs > 0) {
     last_k_ = K;
     ghost_ = K;  // both captured cycles exchange K rows
@@ -1332,7 +1342,7 @@ void Solver::ensure_pair_graph() {
     hipGraph_t g = nullptr;
     const hipEvent_t fork = ev_fork_, join = ev_join_;  // (the solver's own: see runtime.hpp)
     const int saved = cur_, saved_ghost = ghost_, saved_last = last_k_;
-    const int64_t saved_steps = steps_, saved_hist = hist_[K], saved_halo = halo_rows_;
+    const int64_t saved_steps = steps_, saved_hist = hist_[K], saved_halo = halo_rows_, saved_rec = probe_rec_;
     ghost_ = (int)band_;  // replays start after step()'s top-up
     const int saved_lx0 = last_x_[0], saved_lx1 = last_x_[1];
     if (tr_->exchanges()) last_x_[0] = last_x_[1] = (int)band_;  // whatever a replay follows
@@ -1368,6 +1378,7 @@ void Solver::ensure_pair_graph() {
     }
     cur_ = saved;
     steps_ = saved_steps;
+    probe_rec_ = saved_rec;
     hist_[K] = saved_hist;
     ghost_ = saved_ghost;
     last_k_ = saved_last;
@@ -1431,6 +1442,7 @@ std::vector<int> Solver::step_cycles(int64_t n) const {
 
 void Solver::step(int64_t n) {
   if (n <= 0) return;
+  probe_room(n);
   if (hip_) H2D_HIP(hipSetDevice(cfg_.device));
   if (cfg_.copy_swap) {
     for (int64_t i = 0; i < n; ++i) cycle_copy_swap();
@@ -1723,7 +1735,7 @@ void Solver::capture_schedule(int64_t n) {
     (void)split_plan_banded(sc[i], std::max(sc[i], exchange_depth(sc, i, sc[0])));
   synchronize();
   const int saved = cur_, saved_ghost = ghost_, saved_last = last_k_;
-  const int64_t saved_steps = steps_, saved_halo = halo_rows_;
+  const int64_t saved_steps = steps_, saved_halo = halo_rows_, saved_rec = probe_rec_;
   ghost_ = (int)band_;  // replays start after step()'s top-up
   const int saved_lx0 = last_x_[0], saved_lx1 = last_x_[1];
   if (tr_->exchanges()) last_x_[0] = last_x_[1] = (int)band_;  // whatever a replay follows
@@ -1750,6 +1762,7 @@ void Solver::capture_schedule(int64_t n) {
   H2D_HIP(hipStreamEndCapture(s_compute_, &g));
   cur_ = saved;
   steps_ = saved_steps;
+  probe_rec_ = saved_rec;
   ghost_ = saved_ghost;
   last_k_ = saved_last;
   halo_rows_ = saved_halo;
@@ -1793,6 +1806,7 @@ void Solver::run_schedule_graph(int64_t n) {
   for (size_t i = 0; i < sc.size(); ++i) {
     hist_[sc[i]] += 1;
     steps_ += sc[i];
+    if (probe_cap_ > 0) probe_rec_ += sc[i];
     if (tr_->exchanges()) halo_rows_ += exchange_depth(sc, i, sc[0]);
   }
   last_k_ = sc.back();
@@ -1956,6 +1970,7 @@ void Solver::synchronize() {
 
 void Solver::step_stats(int64_t n, double out[6]) {
   HEAT2D_REQUIRE(n >= 1, "step_stats needs n >= 1");
+  probe_room(n);
   if (hip_) H2D_HIP(hipSetDevice(cfg_.device));
   // (periodic y: the fused-statistics march would count its ghost columns;
   // insulated axes: the fused-statistics kernel has no insulated edges)
@@ -2235,6 +2250,124 @@ void Solver::set_faces(const void* rx, const void* ry, int64_t ld) {
   faces_on_ = true;
 }
 
+void Solver::free_probes() {
+  if (hip_) {
+    if (d_probe_pts_) (void)hipFree(d_probe_pts_);
+    if (probe_hist_) (void)hipFree(probe_hist_);
+    if (d_probe_base_) (void)hipFree(d_probe_base_);
+  } else {
+    std::free(probe_hist_);
+  }
+  d_probe_pts_ = nullptr;
+  probe_hist_ = nullptr;
+  d_probe_base_ = nullptr;
+  probe_idx_.clear();
+  probe_pts_.clear();
+  probe_cap_ = probe_rec_ = 0;
+}
+
+void Solver::set_probe_base() {
+  if (!hip_ || !d_probe_base_) return;
+  synchronize();
+  H2D_HIP(hipMemcpy(d_probe_base_, &probe_rec_, sizeof(int64_t), hipMemcpyHostToDevice));
+}
+
+void Solver::set_probes(const int64_t* points, int64_t count, int64_t capacity) {
+  HEAT2D_REQUIRE(count >= 0 && count <= kMaxProbes, "set_probes: between 0 and kMaxProbes (" + std::to_string(kMaxProbes) + ") points");
+  if (count > 0) {
+    HEAT2D_REQUIRE(points != nullptr, "set_probes: no points");
+    HEAT2D_REQUIRE(capacity >= 1, "set_probes: the history needs room for at least one step");
+    HEAT2D_REQUIRE(cfg_.arith != 3, "probe points have no arith fast: its intermediate levels are scaled and have no "
+                                    "stated per-step rounding (use exact, fma, jacobi or auto)");
+    HEAT2D_REQUIRE(!jit_ && cfg_.engine == 0, "probe points need the temporal-blocked engine (engine \"jit\" records nothing)");
+    HEAT2D_REQUIRE(!cfg_.copy_swap, "probe points have no copy-swap mode");
+    for (int64_t p = 0; p < count; ++p)
+      HEAT2D_REQUIRE(points[2 * p] >= 1 && points[2 * p] <= L_.nrows_global && points[2 * p + 1] >= 1 &&
+                         points[2 * p + 1] <= L_.ncols,
+                     "set_probes: point " + std::to_string(p) + " = (" + std::to_string(points[2 * p]) + ", " +
+                         std::to_string(points[2 * p + 1]) + ") is not an owned point (1.." +
+                         std::to_string(L_.nrows_global) + ", 1.." + std::to_string(L_.ncols) + ")");
+  }
+  drop_graphs();  // (synchronises)
+  free_probes();
+  if (hip_) H2D_HIP(hipSetDevice(cfg_.device));
+  for (int64_t p = 0; p < count; ++p) {
+    const int64_t i = points[2 * p] - 1 - L_.row0;  // local row
+    if (i < 0 || i >= L_.nrows) continue;
+    probe_idx_.push_back(p);
+    probe_pts_.push_back(i);
+    probe_pts_.push_back(points[2 * p + 1] - 1);
+  }
+  if (count > 0) probe_cap_ = capacity;  // (also on a rank that owns none of the points: the same overflow refusal)
+  if (probe_idx_.empty()) return;
+  const size_t hbytes = (size_t)capacity * probe_idx_.size() * dtype_size(dtype());
+  if (hip_) {
+    H2D_HIP(hipMalloc(reinterpret_cast<void**>(&d_probe_pts_), probe_pts_.size() * sizeof(int64_t)));
+    H2D_HIP(hipMemcpy(d_probe_pts_, probe_pts_.data(), probe_pts_.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    H2D_HIP(hipMalloc(&probe_hist_, hbytes));
+    H2D_HIP(hipMemset(probe_hist_, 0, hbytes));
+    H2D_HIP(hipMalloc(reinterpret_cast<void**>(&d_probe_base_), sizeof(int64_t)));
+    set_probe_base();
+  } else {
+    probe_hist_ = host_alloc(hbytes);
+    std::memset(probe_hist_, 0, hbytes);
+  }
+}
+
+void Solver::clear_probe_history() {
+  probe_rec_ = 0;
+  set_probe_base();
+}
+
+void Solver::probe_room(int64_t n) const {
+  HEAT2D_REQUIRE(probe_cap_ == 0 || probe_rec_ + n <= probe_cap_,
+                 "probe history full: " + std::to_string(probe_rec_) + " of " + std::to_string(probe_cap_) +
+                     " steps recorded, " + std::to_string(n) + " more asked for (set_probes with a larger capacity, or "
+                     "clear_probe_history)");
+}
+
+void Solver::probe_history(void* host) {
+  const size_t bytes = (size_t)probe_rec_ * probe_idx_.size() * dtype_size(dtype());
+  if (bytes == 0) return;
+  if (hip_) {
+    H2D_HIP(hipSetDevice(cfg_.device));
+    synchronize();
+    H2D_HIP(hipMemcpy(host, probe_hist_, bytes, hipMemcpyDeviceToHost));
+  } else {
+    std::memcpy(host, probe_hist_, bytes);
+  }
+}
+
+// The cone of this cycle (depth k from the current buffer) and the advance of
+// the row base, on the stream of the cycle's band launch behind the waits that
+// launch makes: the source buffer is complete there (ghost rows included), and
+// whatever overwrites it next waits for that stream's band launch.
+void Solver::launch_probes(int k, hipStream_t stream) {
+  if (probe_idx_.empty()) return;
+  kern::ProbeArgs a{};
+  a.src = buf_[cur_];
+  a.source = source();
+  a.rmap = rmap();
+  a.rx = face_rx();
+  a.ry = face_ry();
+  a.hist = probe_hist_;
+  a.capacity = probe_cap_;
+  a.P = (int64_t)probe_idx_.size();
+  a.r = cfg_.r;
+  a.k = k;
+  kern::probe_bounds(a, L_, bc_);
+  if (hip_) {
+    a.pts = d_probe_pts_;
+    a.base = d_probe_base_;
+    kern::launch_probe_cone(dtype(), a, cfg_.arith, stream);
+    kern::launch_probe_advance(d_probe_base_, k, stream);
+  } else {
+    a.pts = probe_pts_.data();
+    a.base0 = probe_rec_;
+    cpu::probe_cone(dtype(), a, cfg_.arith);
+  }
+}
+
 void Solver::upload_field(const void* host, int64_t ld) {
   upload_framed(host, ld);
   exchange_post();
@@ -2291,6 +2424,7 @@ void LoopbackGroup::init(const kern::IcParams& ic, const double* xg, const doubl
 // exchanges — the order a multi-process run gets from RCCL's rendezvous.
 void LoopbackGroup::step(int64_t n) {
   if (n <= 0) return;
+  for (auto& m : members_) m->probe_room(n);
   const int K = members_[0]->pref_depth();
   std::vector<int> seq;
   for (int64_t left = n; left > 0;) {
@@ -2335,6 +2469,10 @@ void LoopbackGroup::set_rmap(const void* host, int64_t ld) {
 
 void LoopbackGroup::set_faces(const void* rx, const void* ry, int64_t ld) {
   for (auto& m : members_) m->set_faces(rx, ry, ld);
+}
+
+void LoopbackGroup::set_probes(const int64_t* points, int64_t count, int64_t capacity) {
+  for (auto& m : members_) m->set_probes(points, count, capacity);
 }
 
 void LoopbackGroup::upload_field(const void* host, int64_t ld) {

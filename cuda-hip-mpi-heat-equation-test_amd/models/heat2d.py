@@ -22,6 +22,7 @@ from typing import Optional
 import numpy as np
 
 from ..ops import _native as N
+from ..ops import kernels as K
 from ..parallel import transport as T
 from ..utils.config import Problem
 
@@ -292,6 +293,21 @@ class HeatSolver:
             rmap, arith "exact" / "fma" ("auto" is exact); the depth is clamped
             to info()["faces"]["max_tb"]. :meth:`set_faces` replaces them, or
             returns to the scalar r, between steps.
+        probes: P owned points (i, j) in global frame-inclusive indices,
+            1 <= i, j <= n (shape (P, 2), integers, duplicates allowed, at most
+            4096), whose temperature is recorded after EVERY step — the levels
+            inside a fused pass included, which exist only in registers. One
+            history row per step taken by step() / step_stats(), however the
+            call is cut into cycles; prepare() records nothing.
+            :meth:`probe_history` returns it, bitwise equal to
+            models.reference.probe_history wherever the field equals
+            models.reference.ftcs bitwise. A small kernel beside the march
+            advances the patch around each probe (csrc/kernels/probe_cone.hip);
+            no stencil kernel changes. Each rank keeps the probes of its rows
+            (:attr:`probe_index`). Not with arith "fast", engine "jit" or
+            copy_swap. :meth:`set_probes` replaces or clears them between steps.
+        probe_steps: steps the history has room for (default problem.ntime); a
+            step(n) that would overflow it raises before it launches anything.
     """
 
     def __init__(self, problem: Problem, *, dtype: str = "fp64", backend: str = "auto", tb: int = 0,
@@ -300,7 +316,8 @@ class HeatSolver:
                  device: Optional[int] = None, init: bool = True, rows: Optional[int] = None,
                  comm_cus: int = 0, autotune: int = -1, engine: str = "tb", arith: str = "auto",
                  slab_row0: Optional[int] = None, edge_shift: int = 0, bc_x: str = "dirichlet",
-                 bc_y: str = "dirichlet", source=None, rmap=None, faces=None):
+                 bc_y: str = "dirichlet", source=None, rmap=None, faces=None, probes=None,
+                 probe_steps: Optional[int] = None):
         self.problem = problem
         self.edge_shift = 0 if bc_x == "periodic" else int(edge_shift)  # (periodic x: no edge slabs)
         self.bc_x, self.bc_y = bc_x, bc_y
@@ -367,8 +384,52 @@ class HeatSolver:
             self.set_rmap(rmap)
         if faces is not None:
             self.set_faces(faces)
+        if probes is not None:
+            self.set_probes(probes, probe_steps)
         if init:
             self.init()
+
+    def set_probes(self, points, steps: Optional[int] = None) -> None:
+        """Replace the probe points (see the class docstring) or clear them
+        (None), between step() calls. The history starts empty, with room for
+        ``steps`` steps (default: problem.ntime). Nothing but captured graphs is
+        invalidated."""
+        if points is None:
+            N.call("heat2d_solver_set_probes", self._h, None, 0, 0)
+            return
+        a = K.probe_points(points, int(self.layout.nrows_global), self.ncols)
+        cap = int(self.problem.ntime if steps is None else steps)
+        if len(a) and cap < 1:
+            raise ValueError(f"probe_steps must be at least 1, got {cap}")
+        N.call("heat2d_solver_set_probes", self._h, a.ctypes.data_as(C.c_void_p), len(a), cap)
+
+    def _probes(self) -> dict:
+        v = (C.c_int64 * 4)()
+        N.call("heat2d_solver_probes", self._h, v)
+        return {"count": int(v[0]), "capacity": int(v[1]), "recorded": int(v[2])}
+
+    @property
+    def probe_index(self) -> np.ndarray:
+        """Positions of this rank's probes in the list set_probes was given (the
+        points whose row this rank owns, in the list's order)."""
+        n = self._probes()["count"]
+        out = (C.c_int64 * max(1, n))()
+        N.call("heat2d_solver_probe_index", self._h, out)
+        return np.array(out[:n], dtype=np.int64)
+
+    def probe_history(self) -> np.ndarray:
+        """The recorded history (recorded, P_local) in the run's dtype: row q
+        holds the temperature at this rank's probes after step q + 1 counted
+        from set_probes / clear_probe_history. Synchronises."""
+        pr = self._probes()
+        out = np.empty((pr["recorded"], pr["count"]), dtype=self.np_dtype)
+        if out.size:
+            N.call("heat2d_solver_probe_history", self._h, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def clear_probe_history(self) -> None:
+        """Forget the recorded rows (the probes and the capacity stay)."""
+        N.call("heat2d_solver_clear_probe_history", self._h)
 
     def set_faces(self, faces) -> None:
         """Replace the face coefficients (the pair of global frame-inclusive
@@ -445,6 +506,7 @@ class HeatSolver:
                 "source": _source_info(self._h),
                 "rmap": _rmap_info(self._h),
                 "faces": _faces_info(self._h),
+                "probes": self._probes(),  # {"count": this rank's, "capacity", "recorded"}
                 "rank": self.rank, "size": self.size, "layout": self.layout.as_dict()}
 
     def _bc(self) -> tuple:
@@ -682,7 +744,8 @@ class LoopbackGroup:
     def __init__(self, problem: Problem, nranks: int, *, dtype: str = "fp64", backend: str = "auto",
                  tb: int = 0, tile_rows: int = 0, device: Optional[int] = None, arith: str = "auto",
                  overlap: bool = True, autotune: int = -1, comm_cus: int = 0, edge_shift: int = 0,
-                 bc_x: str = "dirichlet", bc_y: str = "dirichlet", source=None, rmap=None, faces=None):
+                 bc_x: str = "dirichlet", bc_y: str = "dirichlet", source=None, rmap=None, faces=None,
+                 probes=None, probe_steps: Optional[int] = None):
         self.problem = problem
         self.bc_x, self.bc_y = bc_x, bc_y
         self.backend = resolve_backend(backend)
@@ -719,6 +782,9 @@ class LoopbackGroup:
             self.set_rmap(rmap)
         if faces is not None:
             self.set_faces(faces)
+        self._nprobes = 0
+        if probes is not None:
+            self.set_probes(probes, probe_steps)
         x = np.ascontiguousarray(problem.x, dtype=np.float64)
         ic = problem.ic.to_native()
         N.call("heat2d_group_init", self._h, C.byref(ic), x.ctypes.data_as(C.c_void_p),
@@ -756,6 +822,41 @@ class LoopbackGroup:
         m = self.problem.n_owned
         rx, ry = _faces_arrays(faces, m, m, NP_DTYPES[self.dtype])
         N.call("heat2d_group_set_faces", self._h, rx.ctypes.data_as(C.c_void_p), ry.ctypes.data_as(C.c_void_p), m + 2)
+
+    def set_probes(self, points, steps: Optional[int] = None) -> None:
+        """Probe points on every member (HeatSolver.set_probes; the global list:
+        each member keeps the points of its rows). None clears them."""
+        if points is None:
+            N.call("heat2d_group_set_probes", self._h, None, 0, 0)
+            self._nprobes = 0
+            return
+        m = self.problem.n_owned
+        a = K.probe_points(points, m, m)
+        cap = int(self.problem.ntime if steps is None else steps)
+        if len(a) and cap < 1:
+            raise ValueError(f"probe_steps must be at least 1, got {cap}")
+        N.call("heat2d_group_set_probes", self._h, a.ctypes.data_as(C.c_void_p), len(a), cap)
+        self._nprobes = len(a)
+
+    def probe_history(self) -> np.ndarray:
+        """The members' histories merged: (recorded, P), columns in the order of
+        the list set_probes was given."""
+        out = None
+        for i in range(self.nranks):
+            h = self._member(i)
+            v = (C.c_int64 * 4)()
+            N.call("heat2d_solver_probes", h, v)
+            cnt, rec = int(v[0]), int(v[2])
+            if out is None:
+                out = np.empty((rec, self._nprobes), dtype=NP_DTYPES[self.dtype])
+            if cnt == 0 or rec == 0:
+                continue
+            idx = (C.c_int64 * cnt)()
+            N.call("heat2d_solver_probe_index", h, idx)
+            part = np.empty((rec, cnt), dtype=NP_DTYPES[self.dtype])
+            N.call("heat2d_solver_probe_history", h, part.ctypes.data_as(C.c_void_p))
+            out[:, list(idx)] = part
+        return out
 
     def upload(self, arr: np.ndarray) -> None:
         """Whole owned grid -> the members' slabs, then a loopback halo exchange."""

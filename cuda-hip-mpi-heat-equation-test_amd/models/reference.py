@@ -282,6 +282,30 @@ def ftcs(problem: Problem, nsteps: int | None = None, dtype=np.float64, T0: np.n
     return wrap_frame(T, bc_x, bc_y)
 
 
+def probe_history(problem: Problem, nsteps: int, probes, dtype=np.float64, T0: np.ndarray | None = None,
+                  arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
+                  source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None) -> np.ndarray:
+    """The golden of the solver's probe points: the (nsteps, P) array whose row
+    q holds the values :func:`ftcs_step` leaves at ``probes`` after step q + 1.
+    ``probes``: P owned points (i, j) in frame-inclusive indices, 1 <= i, j <= n,
+    duplicates allowed. A thin loop over :func:`ftcs_step`, with its rules (and
+    its refusals); the other arguments are :func:`ftcs`'s."""
+    T = initial_field(problem, dtype) if T0 is None else T0.astype(dtype)
+    p = np.asarray(probes)
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError(f"probes must have shape (P, 2), got {p.shape}")
+    if not np.issubdtype(p.dtype, np.integer):
+        raise ValueError("probes must be integer points (i, j)")
+    n, m = T.shape[0] - 2, T.shape[1] - 2
+    if len(p) and (p.min() < 1 or p[:, 0].max() > n or p[:, 1].max() > m):
+        raise ValueError(f"probes must be owned points (1..{n}, 1..{m})")
+    H = np.empty((nsteps, len(p)), dtype=T.dtype)
+    for q in range(nsteps):
+        T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source, rmap, faces)
+        H[q] = T[p[:, 0], p[:, 1]]
+    return H
+
+
 def fast_error_bound(nsteps: int, dtype, tmax: float) -> float:
     """Stated bound of the scaled-level arithmetic ("fast", the kernels' AR 3)
     against the reference rounding ("exact") after ``nsteps`` steps from a

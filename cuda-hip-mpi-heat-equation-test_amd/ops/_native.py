@@ -212,6 +212,14 @@ _SIGS = {
     "heat2d_solver_faces": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "heat2d_tb_div": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, _P, _I64, C.c_int, _P, _P]),
     "heat2d_cpu_tb_div": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_int, _P, _P]),
+    "heat2d_solver_set_probes": (C.c_int, [_P, _P, _I64, _I64]),
+    "heat2d_group_set_probes": (C.c_int, [_P, _P, _I64, _I64]),
+    "heat2d_solver_probes": (C.c_int, [_P, C.POINTER(_I64)]),
+    "heat2d_solver_probe_index": (C.c_int, [_P, C.POINTER(_I64)]),
+    "heat2d_solver_probe_history": (C.c_int, [_P, _P]),
+    "heat2d_solver_clear_probe_history": (C.c_int, [_P]),
+    "heat2d_probe_cone": (C.c_int, [C.c_int, _P, _LP, C.c_int, C.c_double, C.c_int, C.c_int, _P, _P, _P, _P, _P, _I64,
+                                    _P, _P, C.c_int]),
     "heat2d_plan_max_grid_faces": (C.c_int, [C.c_int, C.c_int, _I64, C.c_int, C.c_int, C.c_int, C.POINTER(_I64)]),
     "heat2d_solver_compare": (C.c_int, [_P, _P, _I64, _I64, _I64, _P]),
     "heat2d_solver_footprint": (C.c_int, [C.POINTER(Config), C.c_int, C.c_int, C.POINTER(_I64)]),

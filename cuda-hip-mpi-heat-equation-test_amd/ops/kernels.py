@@ -192,6 +192,77 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
                C.byref(layout), rb, re, k, r, ar, bc)
 
 
+MAX_PROBES = 4096  # common.hpp kMaxProbes
+
+
+def probe_points(points, nrows_global: int, ncols: int) -> np.ndarray:
+    """``points`` as a (P, 2) int64 array of GLOBAL frame-inclusive indices
+    (i, j), 1 <= i <= nrows_global, 1 <= j <= ncols — the checked form every
+    probe entry point takes. ValueError: a shape other than (P, 2), a
+    non-integer entry, a point off the owned grid, more than MAX_PROBES."""
+    a = np.asarray(points)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"probes must have shape (P, 2), got {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"probes must be integer points (i, j), got dtype {a.dtype}")
+    a = np.ascontiguousarray(a, dtype=np.int64)
+    if len(a) > MAX_PROBES:
+        raise ValueError(f"at most {MAX_PROBES} probes, got {len(a)}")
+    bad = (a[:, 0] < 1) | (a[:, 0] > nrows_global) | (a[:, 1] < 1) | (a[:, 1] > ncols)
+    if bad.any():
+        p = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"probe {p} = ({a[p, 0]}, {a[p, 1]}) is not an owned point "
+                         f"(1..{nrows_global}, 1..{ncols})")
+    return a
+
+
+def probe_cone(src: torch.Tensor, layout: N.Layout, k: int, r: float, points, arith: str = "exact",
+               bc_x: str = "dirichlet", bc_y: str = "dirichlet", source: Optional[torch.Tensor] = None,
+               rmap: Optional[torch.Tensor] = None, faces: Optional[tuple] = None) -> torch.Tensor:
+    """The probe-cone kernel alone (csrc/kernels/probe_cone.hip; CPU tensors:
+    its twin): the values at ``points`` after each of the next k steps of
+    ``src``, a (k, P) tensor of src's dtype and device — row s - 1 holds level
+    s. ``points``: global frame-inclusive (i, j) whose rows this slab owns; the
+    k ghost rows around them must be valid in ``src``. ``layout``, ``r``,
+    ``arith`` ("exact" / "fma" / "jacobi"), ``bc_x`` / ``bc_y`` and the
+    coefficient buffers are :func:`tb_step`'s. Nothing is written but the
+    result."""
+    _check_field(src, layout)
+    pts = probe_points(points, int(layout.nrows_global), int(layout.ncols))
+    loc = pts - np.array([1 + layout.row0, 1], dtype=np.int64)
+    if ((loc[:, 0] < 0) | (loc[:, 0] >= layout.nrows)).any():
+        raise ValueError("probe_cone: a point's row is not an owned row of this slab")
+    if not 1 <= k <= min(N.max_tb(), int(layout.halo)):
+        raise ValueError(f"probe_cone: k must be in [1, {min(N.max_tb(), int(layout.halo))}]")
+    if arith not in ("exact", "fma", "jacobi"):
+        raise ValueError("probe_cone: arith 'exact', 'fma' or 'jacobi'")
+    coefs = [source, rmap] + (list(faces) if faces is not None else [None, None])
+    if (source is not None) + (rmap is not None) + (faces is not None) > 1:
+        raise ValueError("probe_cone: at most one of source, rmap and faces")
+    for f in coefs:
+        if f is not None:
+            _check_field(f, layout)
+            if f.dtype != src.dtype or f.device != src.device:
+                raise ValueError("coefficient buffer dtype/device mismatch")
+    if any(f is not None for f in coefs):
+        if bc_x != "dirichlet" or bc_y != "dirichlet":
+            raise ValueError("a heat source, a diffusivity map and face coefficients need Dirichlet boundaries")
+        if arith == "jacobi":
+            raise ValueError("a heat source, a diffusivity map and face coefficients need arith 'exact' or 'fma'")
+    ar = N.arith_code(arith, r)
+    out = torch.empty((k, len(pts)), dtype=src.dtype, device=src.device)
+    if len(pts) == 0:
+        return out
+    dpts = torch.from_numpy(np.ascontiguousarray(loc)).to(src.device)
+    ptr = [C.c_void_p(f.data_ptr()) if f is not None else None for f in coefs]
+    N.call("heat2d_probe_cone", dtype_code(src), C.c_void_p(src.data_ptr()), C.byref(layout), int(k), float(r), ar,
+           N.bc_bits(bc_x, bc_y), ptr[0], ptr[1], ptr[2], ptr[3], C.c_void_p(dpts.data_ptr()), len(pts),
+           C.c_void_p(out.data_ptr()), _stream(src), int(src.is_cuda))
+    if src.is_cuda:
+        torch.cuda.current_stream(src.device).synchronize()  # keep dpts alive until done
+    return out
+
+
 def source_field(S: np.ndarray, layout: N.Layout, dtype: torch.dtype, device="cpu") -> torch.Tensor:
     """The heat-source buffer :func:`tb_step` takes, from the GLOBAL
     frame-inclusive array ``S`` ((nrows_global + 2) x (ncols + 2)): -0.0

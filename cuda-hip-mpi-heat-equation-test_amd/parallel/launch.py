@@ -76,6 +76,14 @@ def build_parser():
                          "run's dtype; a wrong shape fails); a zero face is a wall. Dirichlet axes, engine tb, arith "
                          "exact / fma (auto is exact), not with --source or --rmap. Checkpoints record its SHA-256; a "
                          "restart needs the same file again")
+    ap.add_argument("--probes", default=None, metavar="FILE",
+                    help="probe points: a .npy integer array (P, 2), or text with two integers per line ('#' comments), "
+                         "of owned points (i, j), 1 <= i, j <= n. Their temperature after EVERY step of the run — the "
+                         "steps inside fused passes included — is written to --probes-out by the root rank at the end, "
+                         "whatever soln says. Not checkpointed: a restarted run records from its restart step. Not "
+                         "with --arith fast, --engine jit or --copy-swap")
+    ap.add_argument("--probes-out", default="probes.npy", metavar="FILE.npy",
+                    help="where the (steps, P) probe history goes (default probes.npy in the working directory)")
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--ntime", type=int, default=None)
     ap.add_argument("--print-every", type=int, default=0)
@@ -272,6 +280,13 @@ def run(argv=None) -> int:
             print(f"warning: max face sum = {smax:.6g} > 1: FTCS is unstable in 2-D", file=sys.stderr)
         if arith == "auto":
             arith = "exact"  # (as the solver and the CLI resolve it with face coefficients)
+    probes = None
+    if a.probes:
+        from ..ops.kernels import probe_points
+        try:
+            probes = probe_points(load_probes(a.probes), prob.n_owned, prob.n_owned)
+        except ValueError as e:
+            raise SystemExit(f"heat2d: --probes {a.probes}: {e}")
     # (with a source auto stays with the solver: fma when r is a power of two, else exact — never jacobi)
     if arith == "auto" and prob.r == 0.25 and prob.ic.sterbenz_safe() and not a.restart and engine == "tb" \
             and source is None:
@@ -336,6 +351,9 @@ def run(argv=None) -> int:
         if root and not a.quiet:
             print(f" restarted from {a.restart} at step {start_step}")
 
+    if probes is not None:  # (the history is not checkpointed: a restarted run records from its restart step)
+        s.set_probes(probes, max(1, nsteps - start_step))
+
     x = prob.x
     if var.outputs == "serial" and a.output == "ascii" and start_step == 0:
         _write_inclusive(s, prob, "int.dat", world)
@@ -387,6 +405,8 @@ def run(argv=None) -> int:
 
     if a.checkpoint:
         checkpoint.save(s, a.checkpoint, step=done)
+    if probes is not None:
+        write_probe_history(s, len(probes), world, a.probes_out)
     if a.output != "none":
         if var.outputs == "serial":
             if a.output == "ascii":
@@ -425,6 +445,51 @@ def run(argv=None) -> int:
         import torch.distributed as dist
         dist.destroy_process_group()
     return 0
+
+
+def load_probes(path):
+    """--probes FILE: a .npy integer array (P, 2), or text with two integers per
+    line and '#' comments. Returns what the file holds (probe_points checks it)."""
+    with open(path, "rb") as f:
+        if f.read(6) == b"\x93NUMPY":
+            return np.load(path, allow_pickle=False)
+    rows = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            t = line.split("#", 1)[0].split()
+            if not t:
+                continue
+            try:
+                if len(t) != 2:
+                    raise ValueError
+                rows.append((int(t[0]), int(t[1])))
+            except ValueError:
+                raise ValueError(f"line {ln}: two integers per line, got {line.strip()!r}") from None
+    return np.array(rows, dtype=np.int64).reshape(-1, 2)
+
+
+def gather_probe_history(s, nprobes, world):
+    """The (recorded, P) history on rank 0, columns in the order of the probe
+    list (None elsewhere): every rank's columns over the host collectives."""
+    part = (s.probe_index, s.probe_history())
+    parts = [part]
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world if s.rank == 0 else None
+        dist.gather_object(part, parts, dst=0)
+        if s.rank != 0:
+            return None
+    H = np.empty((parts[0][1].shape[0], nprobes), dtype=parts[0][1].dtype)
+    for idx, h in parts:
+        H[:, idx] = h
+    return H
+
+
+def write_probe_history(s, nprobes, world, path):
+    """--probes-out: the root rank writes the gathered history (collective)."""
+    H = gather_probe_history(s, nprobes, world)
+    if H is not None:
+        np.save(path, H)
 
 
 def _write_inclusive(s, prob, path, world):
