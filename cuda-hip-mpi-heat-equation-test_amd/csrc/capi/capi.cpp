@@ -217,6 +217,23 @@ int heat2d_cpu_tb_src(int dtype, const void* src, void* dst, const heat2d_layout
   return guarded([&] { cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, arith, 0, source); });
 }
 
+int heat2d_tb_gain(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                   double r, void* stream, int64_t tile_rows, int arith, const void* source, const void* gain,
+                   const int64_t* gain_pos) {
+  return guarded([&] {
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, arith, 0, source,
+                    nullptr, nullptr, nullptr, kern::GainRef{gain, gain_pos});
+  });
+}
+
+int heat2d_cpu_tb_gain(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                       double r, int arith, const void* source, const void* gain, const int64_t* gain_pos) {
+  return guarded([&] {
+    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, arith, 0, source, nullptr, nullptr, nullptr,
+            kern::GainRef{gain, gain_pos});
+  });
+}
+
 int heat2d_tb_var(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                   void* stream, int64_t tile_rows, int arith, const void* rmap) {
   return guarded([&] {
@@ -462,6 +479,19 @@ int heat2d_solver_source(void* s, int32_t* out3) {
   });
 }
 
+int heat2d_solver_set_source_gain(void* s, const void* host, int64_t len, int64_t start) {
+  return guarded([&] { static_cast<Solver*>(s)->set_source_gain(host, len, start); });
+}
+
+int heat2d_solver_source_gain(void* s, int64_t* out3) {
+  return guarded([&] {
+    Solver* so = static_cast<Solver*>(s);
+    out3[0] = so->gain_on() ? 1 : 0;
+    out3[1] = so->gain_length();
+    out3[2] = so->gain_position();
+  });
+}
+
 int heat2d_solver_set_rmap(void* s, const void* host, int64_t ld) {
   return guarded([&] { static_cast<Solver*>(s)->set_rmap(host, ld); });
 }
@@ -488,6 +518,10 @@ int heat2d_solver_faces(void* s, int32_t* out3) {
 
 int heat2d_solver_set_probes(void* s, const int64_t* points, int64_t count, int64_t capacity) {
   return guarded([&] { static_cast<Solver*>(s)->set_probes(points, count, capacity); });
+}
+
+int heat2d_group_set_source_gain(void* g, const void* host, int64_t len, int64_t start) {
+  return guarded([&] { static_cast<LoopbackGroup*>(g)->set_source_gain(host, len, start); });
 }
 
 int heat2d_group_set_probes(void* g, const int64_t* points, int64_t count, int64_t capacity) {
@@ -517,6 +551,27 @@ int heat2d_solver_probe_history(void* s, void* host) {
 
 int heat2d_solver_clear_probe_history(void* s) {
   return guarded([&] { static_cast<Solver*>(s)->clear_probe_history(); });
+}
+
+int heat2d_probe_cone_gain(int dtype, const void* src, const heat2d_layout* L, int k, double r, int arith,
+                           const void* source, const void* gain, const int64_t* pts, int64_t P, void* out, void* stream,
+                           int on_device) {
+  return guarded([&] {
+    HEAT2D_REQUIRE(source && gain, "heat2d_probe_cone_gain: a source and its gains");
+    kern::ProbeArgs a{};
+    a.src = src;
+    a.source = source;
+    a.gain = gain;
+    a.pts = pts;
+    a.hist = out;
+    a.capacity = k;
+    a.P = P;
+    a.r = r;
+    a.k = k;
+    kern::probe_bounds(a, to_layout(L), 0);
+    if (on_device) kern::launch_probe_cone((DType)dtype, a, arith, as_stream(stream));
+    else cpu::probe_cone((DType)dtype, a, arith);
+  });
 }
 
 int heat2d_probe_cone(int dtype, const void* src, const heat2d_layout* L, int k, double r, int arith, int bc,

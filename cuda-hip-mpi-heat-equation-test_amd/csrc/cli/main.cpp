@@ -85,6 +85,9 @@ struct Args {
   // --source FILE.npy: heat source, the frame-inclusive (n+2) x (n+2) per-step increment dt * f
   // (SolverConfig::source; converted to the run's dtype, a wrong shape fails)
   std::string source;
+  // --source-gain FILE: per-step gains of the source (1-D .npy, or text with one number per line),
+  // indexed by the absolute step of the run (Solver::set_source_gain)
+  std::string source_gain;
   // --rmap FILE.npy: diffusivity map, the frame-inclusive (n+2) x (n+2) per-point diffusion number
   // nu(x, y) dt / dx^2 (SolverConfig::rmap; converted to the run's dtype, a wrong shape fails)
   std::string rmap;
@@ -108,7 +111,7 @@ void usage() {
       "              [--checkpoint DIR [--checkpoint-every N]] [--restart DIR]\n"
       "              [--transport auto|rccl|peer] [--share-gpu] [--autotune auto|on|off] [--edge-shift N]\n"
       "              [--bc-x dirichlet|periodic|insulated] [--bc-y dirichlet|periodic|insulated]\n"
-      "              [--source FILE.npy] [--rmap FILE.npy] [--faces FILE.npy]\n"
+      "              [--source FILE.npy] [--source-gain FILE] [--rmap FILE.npy] [--faces FILE.npy]\n"
       "              [--probes FILE [--probes-out FILE.npy]]\n");
 }
 
@@ -155,6 +158,7 @@ Args parse_args(int argc, char** argv) {
     else if (s == "--transport") a.transport = need("--transport");
     else if (s == "--share-gpu") a.share_gpu = true;
     else if (s == "--source") a.source = need("--source");
+    else if (s == "--source-gain") a.source_gain = need("--source-gain");
     else if (s == "--rmap") a.rmap = need("--rmap");
     else if (s == "--faces") a.faces = need("--faces");
     else if (s == "--probes") a.probes = need("--probes");
@@ -216,6 +220,10 @@ struct Shared {
   // --source: the global array in the run's dtype (read by the first rank to need it, under mu) and its digest
   std::vector<char> source;
   std::string source_sha256;
+  // --source-gain: the schedule in the run's dtype, its length and its digest
+  std::vector<char> gain;
+  int64_t gain_len = 0;
+  std::string gain_sha256;
   // --rmap: the same for the diffusivity map
   std::vector<char> rmap;
   std::string rmap_sha256;
@@ -331,6 +339,7 @@ void save_checkpoint(Shared& sh, Solver& s, Transport& tr, int rank, int64_t ste
     m.bc_x = bc_names[s.config().bc_x];
     m.bc_y = bc_names[s.config().bc_y];
     m.source_sha256 = sh.source_sha256;  // (empty: no source, written as null)
+    m.source_gain_sha256 = sh.gain_sha256;  // (empty: no schedule, the key is not written)
     m.rmap_sha256 = sh.rmap_sha256;      // (empty: no map, the key is not written)
     m.faces_sha256 = sh.faces_sha256;    // (empty: no face coefficients, the key is not written)
     ckpt::write_meta(a.checkpoint, name, m);
@@ -411,6 +420,13 @@ void run_rank(Shared& sh, int rank) {
       if (sh.source.empty())
         sh.source = ckpt::read_source(a.source, sh.prob.n_owned + 2, sh.prob.n_owned + 2, cfg.dtype, &sh.source_sha256);
     }
+    if (!a.source_gain.empty()) {
+      HEAT2D_REQUIRE(cfg.source, "--source-gain scales a heat source: give --source too");
+      std::lock_guard<std::mutex> g(sh.mu);
+      if (sh.gain.empty()) sh.gain = ckpt::read_gain(a.source_gain, cfg.dtype, &sh.gain_len, &sh.gain_sha256);
+      HEAT2D_REQUIRE(sh.gain_len >= sh.in.ntime, "--source-gain " + a.source_gain + ": " + std::to_string(sh.gain_len) +
+                                                     " entries, the run takes " + std::to_string(sh.in.ntime) + " steps");
+    }
     if (!a.rmap.empty()) {
       cfg.rmap = 1;
       std::lock_guard<std::mutex> g(sh.mu);
@@ -462,6 +478,14 @@ void run_rank(Shared& sh, int rank) {
                                                   "--source (sha256 " + m0.source_sha256 + ")");
         fail(__FILE__, __LINE__, "the restart's heat source differs from the checkpoint's (sha256 " + sh.source_sha256 +
                                      " != " + m0.source_sha256 + ")");
+      }
+      if (m0.source_gain_sha256 != sh.gain_sha256) {
+        HEAT2D_REQUIRE(!m0.source_gain_sha256.empty(),
+                       "the checkpoint was written without a source gain schedule, this run has one (--source-gain)");
+        HEAT2D_REQUIRE(!sh.gain_sha256.empty(), "the checkpoint was written with a source gain schedule: give the restart "
+                                                "the same --source-gain (sha256 " + m0.source_gain_sha256 + ")");
+        fail(__FILE__, __LINE__, "the restart's source gain schedule differs from the checkpoint's (sha256 " +
+                                     sh.gain_sha256 + " != " + m0.source_gain_sha256 + ")");
       }
       // ... and the diffusivity map the checkpointed run had (it is not saved either), and no other
       if (m0.rmap_sha256 != sh.rmap_sha256) {
@@ -537,6 +561,7 @@ void run_rank(Shared& sh, int rank) {
         if (!a.quiet) std::printf(" restarted from %s at step %lld\n", a.restart.c_str(), (long long)start);
       }
     }
+    if (!a.source_gain.empty()) s.set_source_gain(sh.gain.data(), sh.gain_len, start);  // G is indexed by the absolute step
     if (!a.probes.empty()) {  // (after a restart's upload: the history is not checkpointed, it starts at `start`)
       {
         std::lock_guard<std::mutex> g(sh.mu);

@@ -166,6 +166,9 @@ void ins_cols_impl(T* f, const SlabLayout& L, int64_t r0, int64_t r1) {
 // q (a heat source in the field's layout, Dirichlet axes only): every level adds
 // its row of q to the updated owned points, T' = update + q, as an add of its
 // own (the device march's tb_impl.hpp March SRC); pinned points are copied.
+// gn (with q: the gains of the pass, gn[s - 1] for level s): level s adds
+// gn[s - 1] * q — the product rounded, then the add; arith 1: one fma — the
+// device march's tb_impl.hpp March GAIN.
 // rm (a diffusivity map in the field's layout, Dirichlet axes only): the
 // multiplier of an owned point's update is its element of rm instead of r (the
 // device march's tb_impl.hpp March VAR); pinned points are copied.
@@ -174,7 +177,8 @@ void ins_cols_impl(T* f, const SlabLayout& L, int64_t r0, int64_t r1) {
 // march's tb_impl.hpp March DIV); pinned points are copied.
 template <typename T>
 void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re, int k, T r, int arith, int bc,
-             const T* q = nullptr, const T* rm = nullptr, const T* fx = nullptr, const T* fy = nullptr) {
+             const T* q = nullptr, const T* rm = nullptr, const T* fx = nullptr, const T* fy = nullptr,
+             const T* gn = nullptr) {
   const SlabLayout L = kern::bc_layout(L0, bc & kern::kBcPeriodicX);  // (the columns: free_cols below)
   const bool free_cols = (bc & kern::kBcPeriodicY) != 0;
   const bool ins_x = (bc & kern::kBcInsulatedX) != 0, ins_y = (bc & kern::kBcInsulatedY) != 0;
@@ -231,7 +235,15 @@ void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re,
         row_update(up, mid, dn, out, L.ncols + 2 * g, r);
         if (q) {
           const T* qr = q + L.offset(row, 0);
-          for (int64_t j = 0; j < L.ncols; ++j) out[j] = out[j] + qr[j];
+          if (gn) {
+            const T gs = gn[s - 1];
+            if (arith == 1)
+              for (int64_t j = 0; j < L.ncols; ++j) out[j] = kern::probe_fma(gs, qr[j], out[j]);
+            else
+              for (int64_t j = 0; j < L.ncols; ++j) out[j] = out[j] + gs * qr[j];
+          } else {
+            for (int64_t j = 0; j < L.ncols; ++j) out[j] = out[j] + qr[j];
+          }
         }
       }
     }, L.ncols);
@@ -325,7 +337,8 @@ int num_threads() {
 }
 
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end,
-        int k, double r, int arith, int bc, const void* source, const void* rmap, const void* rx, const void* ry) {
+        int k, double r, int arith, int bc, const void* source, const void* rmap, const void* rx, const void* ry,
+        kern::GainRef gain) {
   HEAT2D_REQUIRE(k >= 1 && k <= L.halo, "k out of range");
   HEAT2D_REQUIRE(arith >= 0 && arith <= 3, "arith must be 0, 1, 2 or 3");
   HEAT2D_REQUIRE(arith != 2 || r == 0.25, "arith 2 (jacobi) needs r == 1/4 exactly");
@@ -342,16 +355,18 @@ void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_b
   HEAT2D_REQUIRE(!rx || ((arith == 0 || arith == 1) && bc == 0 && !source && !rmap),
                  "face coefficients need arith 0 (exact) or 1 (fma), Dirichlet boundaries on both axes, no heat source and "
                  "no diffusivity map");
+  HEAT2D_REQUIRE(!gain.g || (source && gain.pos), "a gain schedule needs a heat source and its position word");
   if (arith == 3) arith = 1;
   if (row_end <= row_begin) return;
+  const int64_t gpos = gain.g ? *gain.pos : 0;
   if (dt == DType::F32)
     tb_impl<float>(static_cast<const float*>(src), static_cast<float*>(dst), L, row_begin, row_end, k, (float)r, arith, bc,
                    static_cast<const float*>(source), static_cast<const float*>(rmap), static_cast<const float*>(rx),
-                   static_cast<const float*>(ry));
+                   static_cast<const float*>(ry), gain.g ? static_cast<const float*>(gain.g) + gpos : nullptr);
   else
     tb_impl<double>(static_cast<const double*>(src), static_cast<double*>(dst), L, row_begin, row_end, k, r, arith, bc,
                     static_cast<const double*>(source), static_cast<const double*>(rmap), static_cast<const double*>(rx),
-                    static_cast<const double*>(ry));
+                    static_cast<const double*>(ry), gain.g ? static_cast<const double*>(gain.g) + gpos : nullptr);
 }
 
 void init(DType dt, void* field, const SlabLayout& L, const kern::IcParams& ic, const double* xc,
@@ -420,7 +435,7 @@ void unpack_rows(DType dt, void* field, const SlabLayout& L, int64_t row, int64_
 // Twin of kernels/probe_cone.hip: the same levels over the same two planes,
 // one probe after the other, through the shared probe_point (heat2d/probe.hpp).
 namespace {
-template <typename T, int MODE, int AR>
+template <typename T, int MODE, int AR, bool GAIN = false>
 void probe_cone_run(const kern::ProbeArgs& a) {
   constexpr int S = kern::kProbeSide;
   std::vector<T> planes((size_t)2 * S * S, T(0));
@@ -439,7 +454,7 @@ void probe_cone_run(const kern::ProbeArgs& a) {
     for (int s = 1; s <= k; ++s) {
       const int w = 2 * (k - s) + 1;
       for (int idx = 0; idx < w * w; ++idx)
-        kern::probe_point<T, MODE, AR>(a, ci, cj, s, idx, plane[(s - 1) & 1], plane[s & 1]);
+        kern::probe_point<T, MODE, AR, GAIN>(a, ci, cj, s, idx, plane[(s - 1) & 1], plane[s & 1]);
       if (base + s - 1 < a.capacity) hist[(base + s - 1) * a.P + p] = plane[s & 1][k * S + k];
     }
   }
@@ -453,7 +468,11 @@ void probe_cone_mode(const kern::ProbeArgs& a, int arith) {
 }
 template <typename T>
 void probe_cone_typed(const kern::ProbeArgs& a, int arith) {
-  if (a.source) probe_cone_mode<T, kern::kProbeSource>(a, arith);
+  if (a.gain) {
+    HEAT2D_REQUIRE(a.source && (arith == 0 || arith == 1), "probe_cone: a gain schedule needs a source and arith exact or fma");
+    if (arith == 0) probe_cone_run<T, kern::kProbeSource, 0, true>(a);
+    else probe_cone_run<T, kern::kProbeSource, 1, true>(a);
+  } else if (a.source) probe_cone_mode<T, kern::kProbeSource>(a, arith);
   else if (a.rmap) probe_cone_mode<T, kern::kProbeMap>(a, arith);
   else if (a.rx) probe_cone_mode<T, kern::kProbeFaces>(a, arith);
   else probe_cone_mode<T, kern::kProbePlain>(a, arith);

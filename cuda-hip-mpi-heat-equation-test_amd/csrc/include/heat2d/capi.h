@@ -187,6 +187,20 @@ int heat2d_tb_src(int dtype, const void* src, void* dst, const heat2d_layout* L,
                   double r, void* stream, int64_t tile_rows, int arith, const void* source);
 int heat2d_cpu_tb_src(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                       double r, int arith, const void* source);
+/* A per-step gain schedule for the source: `host` holds len gains of the field's dtype (finite, >= 0);
+   the step at position q adds host[q] * S (the product rounded, then the add; arith 1: one fma).
+   The position starts at `start` and moves by one per step taken. host = NULL clears it (the source
+   as it is). Needs a source set; a step past the end is refused. Between steps. */
+int heat2d_solver_set_source_gain(void* s, const void* host, int64_t len, int64_t start);
+/* out3 = {a schedule is set, its length, the position} */
+int heat2d_solver_source_gain(void* s, int64_t* out3);
+/* heat2d_tb_src / heat2d_cpu_tb_src with gains: level s adds gain[*gain_pos + s - 1] * source (gain and
+   gain_pos in the memory the fields live in; *gain_pos + k entries readable) */
+int heat2d_tb_gain(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                   double r, void* stream, int64_t tile_rows, int arith, const void* source, const void* gain,
+                   const int64_t* gain_pos);
+int heat2d_cpu_tb_gain(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                       double r, int arith, const void* source, const void* gain, const int64_t* gain_pos);
 /* The diffusivity map of a solver created with config.rmap = 1: `host` is the GLOBAL frame-inclusive
    array (nrows_global + 2) x (ncols + 2) of the per-point diffusion number R = nu(x, y) dt / dx^2 in the
    field's dtype (frame entries ignored; owned entries finite and >= 0); the rank copies its own rows.
@@ -242,6 +256,10 @@ int heat2d_solver_clear_probe_history(void* s);
 int heat2d_probe_cone(int dtype, const void* src, const heat2d_layout* L, int k, double r, int arith, int bc,
                       const void* source, const void* rmap, const void* rx, const void* ry, const int64_t* pts,
                       int64_t P, void* out, void* stream, int on_device);
+/* heat2d_probe_cone with a source and the k gains of its levels (level s: gain[s - 1]); Dirichlet axes */
+int heat2d_probe_cone_gain(int dtype, const void* src, const heat2d_layout* L, int k, double r, int arith,
+                           const void* source, const void* gain, const int64_t* pts, int64_t P, void* out, void* stream,
+                           int on_device);
 /* any rectangle of the current field, local rows [r0, r1) x columns [c0, c1), ghost / frame included */
 int heat2d_solver_download_region(void* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, void* host, int64_t ld);
 // memory-fit planner (runtime.hpp solver_footprint / plan_max_grid): out3 =
@@ -294,6 +312,8 @@ int heat2d_group_download(void* g, void* host, int64_t ld);
 int heat2d_group_upload_field(void* g, const void* host, int64_t ld);
 /* heat2d_solver_set_source on every member (each slices its rows of the global array) */
 int heat2d_group_set_source(void* g, const void* host, int64_t ld);
+/* heat2d_solver_set_source_gain on every member (each takes the whole schedule) */
+int heat2d_group_set_source_gain(void* g, const void* host, int64_t len, int64_t start);
 /* heat2d_solver_set_rmap on every member */
 int heat2d_group_set_rmap(void* g, const void* host, int64_t ld);
 /* heat2d_solver_set_faces on every member */

@@ -27,6 +27,8 @@ struct Meta {
   std::string rmap_sha256;
   // the run's face coefficients (both arrays, RX then RY), recorded the same way; empty: none (the key is absent)
   std::string faces_sha256;
+  // the run's source gain schedule (the converted bytes), recorded the same way; empty: none (the key is absent)
+  std::string source_gain_sha256;
   std::string dir;  // read_meta: the directory holding this step's files
 };
 // A heat source file (--source FILE.npy): a 2-D little-endian f4 / f8 array of exactly rows x cols
@@ -36,6 +38,10 @@ std::vector<char> read_source(const std::string& path, int64_t rows, int64_t col
 // A face-coefficient file (--faces FILE.npy): a 3-D little-endian f4 / f8 array of exactly 2 x rows x cols
 // (RX, then RY), converted to `dtype`; *sha256 receives the digest of the converted bytes (Meta::faces_sha256).
 std::vector<char> read_faces(const std::string& path, int64_t rows, int64_t cols, int dtype, std::string* sha256);
+// A gain schedule file (--source-gain FILE): a 1-D little-endian f4 / f8 .npy, or text with one number
+// per line and # comments; non-empty, every entry finite and >= 0, converted to `dtype`. *len receives
+// the entry count, *sha256 the digest of the converted bytes (Meta::source_gain_sha256).
+std::vector<char> read_gain(const std::string& path, int dtype, int64_t* len, std::string* sha256);
 // SHA-256 of a byte range, lower-case hex
 std::string sha256_hex(const void* data, size_t bytes);
 

@@ -66,6 +66,12 @@ TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end
 //     Not with arith 3, nor the fused statistics; an axis is periodic or
 //     insulated, not both.
 constexpr int kBcPeriodicX = 1, kBcPeriodicY = 2, kBcInsulatedX = 4, kBcInsulatedY = 8;
+// A source's gain schedule as the launchers take it (launch_tb below): the gain
+// array and the position word, both in the launch's memory space.
+struct GainRef {
+  const void* g = nullptr;
+  const int64_t* pos = nullptr;
+};
 // ghost columns per side kept as wrap images: the deepest pass (kMaxTB) reads that many
 constexpr int64_t kWrapCols = kMaxTB;
 static_assert(kWrapCols <= kColPad && kWrapCols >= 4, "ghost columns must fit the column padding");
@@ -128,15 +134,22 @@ void launch_ins_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool h
 // -1 of rx, frame row -1 of ry). With faces every rect of the launch runs
 // tb_kernel_div (tb_impl.hpp): Dirichlet on both axes, arith 0 / 1, depths
 // 1..kMaxTBDiv, no wave-pair plans, not together with a source or a map.
+// gain (optional, after ry; needs a source): a per-step gain schedule, level s
+// of the pass adds g[*pos + s - 1] * S — the product rounded, then the add;
+// arith 1: fma(g, S, update), one rounding. g: device array of the field's
+// dtype, readable up to *pos + k entries (the solver pads it by kMaxTBSrc);
+// pos: a device word, read when the kernel runs, so a captured launch takes the
+// position of its replay. Every rect runs tb_kernel_gain, tb_kernel_src's
+// launch shape. {}: the source as it is.
 void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
                int64_t row_end, int k, double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0,
                int arith = 0, int bc = 0, const void* source = nullptr, const void* rmap = nullptr,
-               const void* rx = nullptr, const void* ry = nullptr);
+               const void* rx = nullptr, const void* ry = nullptr, GainRef gain = {});
 // Same for TWO disjoint row ranges [rb0, re0) and [rb1, re1) in one launch.
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
                 int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0,
                 int arith = 0, int bc = 0, const void* source = nullptr, const void* rmap = nullptr,
-                const void* rx = nullptr, const void* ry = nullptr);
+                const void* rx = nullptr, const void* ry = nullptr, GainRef gain = {});
 
 // Split schedule of one cycle (k steps over the whole slab) into two launches
 // on two streams:
@@ -214,12 +227,13 @@ bool edges_on_main(const SlabLayout& L, const SplitPlan& p);
 bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i);
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
                       hipStream_t stream, int arith = 0, int bc = 0, const void* source = nullptr,
-                      const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr);
+                      const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr,
+                      GainRef gain = {});
 // queue: 2 device counters (zeroed once) for plans with flags & kPlanDynamic (dynamic items)
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
                   double r, hipStream_t stream, int arith = 0, uint32_t* queue = nullptr, int bc = 0,
                   const void* source = nullptr, const void* rmap = nullptr, const void* rx = nullptr,
-                  const void* ry = nullptr);
+                  const void* ry = nullptr, GainRef gain = {});
 
 // Initial / boundary condition kinds (covers every IC of the reference
 // variants, see models/presets.py for the mapping).

@@ -48,6 +48,10 @@ struct ProbeArgs {
   int64_t wall_r0, wall_r1, wall_c0, wall_c1;
   double r;
   int32_t k;
+  // a source's gain schedule (nullptr: none): level s adds gain[*gain_pos + gain_pos0 + s - 1] * S
+  const void* gain;
+  const int64_t* gain_pos;  // the solver's position word (nullptr: 0)
+  int64_t gain_pos0;
 };
 
 // The frame and wall lines of a slab under boundary bits `bc`.
@@ -73,10 +77,11 @@ __host__ __device__ inline double probe_fma(double a, double b, double c) { retu
 // rounds on its own unless it is written as an fma). c: centre; s, e, n, w:
 // (i+1, j), (i, j+1), (i-1, j), (i, j-1); AR 0 exact, 1 fma, 2 jacobi.
 //   plain:  coef[0] = r
-//   source: coef[0] = r, coef[1] = S[i,j]
+//   source: coef[0] = r, coef[1] = S[i,j]; GAIN: coef[2] = the level's gain g,
+//           upd + g * S (the product rounded, then the add; AR 1: fma(g, S, upd))
 //   map:    coef[0] = R[i,j]
 //   faces:  coef = RY[i,j], RX[i,j], RY[i-1,j], RX[i,j-1]
-template <typename T, int MODE, int AR>
+template <typename T, int MODE, int AR, bool GAIN = false>
 __host__ __device__ inline T probe_update(T c, T s, T e, T n, T w, const T* coef) {
   if (MODE == kProbeFaces) {
     const T ds = s - c, de = e - c, dn = n - c, dw = w - c;
@@ -89,13 +94,16 @@ __host__ __device__ inline T probe_update(T c, T s, T e, T n, T w, const T* coef
   if (AR == 2) upd = r * sum;
   else if (AR == 1) upd = probe_fma(r, probe_fma(T(-4), c, sum), c);
   else upd = c + r * (sum - T(4) * c);
-  if (MODE == kProbeSource) upd = upd + coef[1];
+  if (MODE == kProbeSource) {
+    if (GAIN) upd = AR == 1 ? probe_fma(coef[2], coef[1], upd) : upd + coef[2] * coef[1];
+    else upd = upd + coef[1];
+  }
   return upd;
 }
 
 // Level s of one probe's cone, point `idx` of the (2 (k - s) + 1)^2 updated at
 // that level: from plane `in` into plane `out` (kProbeSide x kProbeSide).
-template <typename T, int MODE, int AR>
+template <typename T, int MODE, int AR, bool GAIN = false>
 __host__ __device__ inline void probe_point(const ProbeArgs& a, int64_t ci, int64_t cj, int s, int idx, const T* in,
                                             T* out) {
   const int w = 2 * (a.k - s) + 1;
@@ -126,8 +134,9 @@ __host__ __device__ inline void probe_point(const ProbeArgs& a, int64_t ci, int6
   } else {
     coef[0] = (T)a.r;
     if (MODE == kProbeSource) coef[1] = static_cast<const T*>(a.source)[o];
+    if (GAIN) coef[2] = static_cast<const T*>(a.gain)[(a.gain_pos ? *a.gain_pos : 0) + a.gain_pos0 + s - 1];
   }
-  out[at] = probe_update<T, MODE, AR>(c, so, ea, no, we, coef);
+  out[at] = probe_update<T, MODE, AR, GAIN>(c, so, ea, no, we, coef);
 }
 
 // Whether patch point (row, col) is loaded: on the grid and inside the allocation.
@@ -142,6 +151,11 @@ __host__ __device__ inline bool probe_loads(const ProbeArgs& a, int64_t row, int
 void launch_probe_cone(DType dt, const ProbeArgs& a, int arith, hipStream_t stream);
 // *base += k, one thread, behind a cone launch on the same stream.
 void launch_probe_advance(int64_t* base, int k, hipStream_t stream);
+// A gain schedule's position for the next cycle: *to = *from + k, one thread.
+// The solver keeps two words, one per buffer parity: a cycle reads its own and
+// writes the other's, on a stream ordered behind the previous cycle's launches
+// (the other word's readers), so no launch ever sees a word move under it.
+void launch_gain_step(const int64_t* from, int64_t* to, int k, hipStream_t stream);
 
 }  // namespace kern
 

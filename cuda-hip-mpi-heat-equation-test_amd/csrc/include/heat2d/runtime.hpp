@@ -268,7 +268,7 @@ std::shared_ptr<Transport> make_ipc_loop_transport(int device);
 namespace cpu {
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
         int64_t row_end, int k, double r, int arith = 0, int bc = 0, const void* source = nullptr,
-        const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr);
+        const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr, kern::GainRef gain = {});
 void wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1);
 void wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k);
 // insulated frame images (kern::launch_ins_cols / launch_ins_rows)
@@ -451,6 +451,18 @@ class Solver {
   // without. Between step() calls; invalidates nothing but the captured graphs.
   void set_source(const void* host, int64_t ld);
   bool has_source() const { return src_on_; }
+  // A per-step gain schedule for the source (len entries of the field's dtype,
+  // finite and >= 0; nullptr: none, the source as it is): step q of the run —
+  // counted from `start` here, one entry per step taken by step() / step_stats(),
+  // however the call is cut into cycles — adds host[q] * S, the product rounded,
+  // then the add (arith fma: fma(host[q], S, update)). Needs a source set;
+  // set_source(nullptr) clears it. prepare(), autotune trials and schedule
+  // rehearsals consume nothing; a step(n) past the end raises before it launches
+  // anything. Synchronises and drops captured graphs.
+  void set_source_gain(const void* host, int64_t len, int64_t start);
+  bool gain_on() const { return gain_buf_ != nullptr && src_on_; }
+  int64_t gain_length() const { return gain_len_; }
+  int64_t gain_position() const { return gain_pos_; }
   // The diffusivity map (SolverConfig::rmap = 1): `host` is the GLOBAL
   // frame-inclusive array of the per-point diffusion number, (nrows_global + 2)
   // x (ncols + 2) in the field's dtype, leading dimension ld; this rank copies
@@ -498,8 +510,9 @@ class Solver {
   // H's recorded rows -> host (probe_recorded() x probe_count(), packed); synchronises
   void probe_history(void* host);
   void clear_probe_history();  // recorded = 0
-  // raises if n more steps would overflow the history
-  void probe_room(int64_t n) const;
+  // raises if n more steps would overflow the probe history or run past the
+  // end of the source's gain schedule (before step() launches anything)
+  void step_room(int64_t n) const;
   // Cycles launched by step() since the last reset, by depth: hist[k] for
   // k = 0..kMaxTB (graph replays count their two cycles each).
   void cycle_hist(int64_t out[kMaxTB + 1], bool reset);
@@ -600,6 +613,18 @@ class Solver {
   void* src_buf_ = nullptr;  // the heat source (cfg_.source), in L_'s layout
   bool src_on_ = false;      // set_source has filled it
   const void* source() const { return src_on_ ? src_buf_ : nullptr; }
+  // the gain schedule (set_source_gain): the array padded by kMaxTBSrc entries
+  // and two position words, one per buffer parity, in device (HIP) or host (CPU)
+  // memory. The cycle from buf_[cur_] reads word cur_ and writes word cur_ ^ 1
+  // (launch_cycle_aux); gain_pos_ is the host's count, as probe_rec_.
+  void* gain_buf_ = nullptr;
+  int64_t* gain_posw_ = nullptr;
+  int64_t gain_len_ = 0, gain_pos_ = 0;
+  kern::GainRef gain() const { return gain_on() ? kern::GainRef{gain_buf_, gain_posw_ + cur_} : kern::GainRef{}; }
+  void free_gain();
+  // both position words <- gain_pos_ (synchronised): wherever cur_ is set outside a cycle,
+  // since only the word of the current parity follows the host's count through the cycles
+  void set_gain_words();
   void* rmap_buf_ = nullptr;  // the diffusivity map (cfg_.rmap), in L_'s layout
   bool rmap_on_ = false;      // set_rmap has filled it
   const void* rmap() const { return rmap_on_ ? rmap_buf_ : nullptr; }
@@ -618,7 +643,9 @@ class Solver {
   int64_t probe_cap_ = 0, probe_rec_ = 0;
   void free_probes();
   void set_probe_base();                // the device word <- probe_rec_ (synchronised)
-  void launch_probes(int k, hipStream_t stream);  // the cycle's cone (+ advance), from buf_[cur_]
+  // what a cycle launches beside its stencil kernels, ahead of its band launch: the gain
+  // schedule's position for the next cycle, the probe cone (+ its advance) from buf_[cur_]
+  void launch_cycle_aux(int k, hipStream_t stream);
   int cur_ = 0;
   int64_t steps_ = 0;
   int64_t band_ = 0;     // largest boundary band / halo exchange depth (= K)
@@ -703,6 +730,7 @@ class LoopbackGroup {
   void set_source(const void* host, int64_t ld);  // Solver::set_source on every member (the global array)
   void set_rmap(const void* host, int64_t ld);    // Solver::set_rmap on every member (the global array)
   void set_faces(const void* rx, const void* ry, int64_t ld);  // Solver::set_faces on every member (the global arrays)
+  void set_source_gain(const void* host, int64_t len, int64_t start);  // on every member (the whole schedule)
   // Solver::set_probes on every member (the global list: each keeps the points of its rows)
   void set_probes(const int64_t* points, int64_t count, int64_t capacity);
   int nranks() const { return (int)members_.size(); }

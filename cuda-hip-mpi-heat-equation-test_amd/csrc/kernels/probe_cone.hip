@@ -43,6 +43,37 @@ __global__ __launch_bounds__(256) void probe_cone(ProbeArgs a) {
   }
 }
 
+// The source cone with a gain schedule (ProbeArgs::gain): the same planes and
+// levels, level s scaled by its gain (probe_update GAIN).
+template <typename T, int AR>
+__global__ __launch_bounds__(256) void probe_cone_gain(ProbeArgs a) {
+  __shared__ T plane[2][kProbeSide * kProbeSide];
+  const int64_t p = blockIdx.x;
+  const int64_t ci = a.pts[2 * p], cj = a.pts[2 * p + 1];
+  const int k = a.k, side = 2 * k + 1;
+  const T* src = static_cast<const T*>(a.src);
+  for (int idx = threadIdx.x; idx < side * side; idx += 256) {
+    const int u = idx / side, v = idx % side;
+    const int64_t row = ci - k + u, col = cj - k + v;
+    if (probe_loads(a, row, col)) plane[0][u * kProbeSide + v] = src[a.L.offset(row, col)];
+  }
+  __syncthreads();
+  const int64_t base = (a.base ? *a.base : 0) + a.base0;
+  T* hist = static_cast<T*>(a.hist);
+  for (int s = 1; s <= k; ++s) {
+    const int w = 2 * (k - s) + 1;
+    const T* in = plane[(s - 1) & 1];
+    T* out = plane[s & 1];
+    for (int idx = threadIdx.x; idx < w * w; idx += 256) probe_point<T, kProbeSource, AR, true>(a, ci, cj, s, idx, in, out);
+    __syncthreads();
+    if (threadIdx.x == 0 && base + s - 1 < a.capacity) hist[(base + s - 1) * a.P + p] = out[k * kProbeSide + k];
+  }
+}
+
+__global__ __launch_bounds__(64) void gain_step(const int64_t* from, int64_t* to, int k) {
+  if (threadIdx.x == 0) *to = *from + k;
+}
+
 __global__ __launch_bounds__(64) void probe_advance(int64_t* base, int k) {
   if (threadIdx.x == 0) *base = *base + k;
 }
@@ -58,7 +89,12 @@ void launch_mode(const ProbeArgs& a, int arith, hipStream_t stream) {
 
 template <typename T>
 void launch_typed(const ProbeArgs& a, int arith, hipStream_t stream) {
-  if (a.source) launch_mode<T, kProbeSource>(a, arith, stream);
+  if (a.gain) {
+    const dim3 grid((unsigned)a.P), block(256);
+    if (!a.source || arith > 1) fail(__FILE__, __LINE__, "probe_cone: a gain schedule needs a source and arith exact or fma");
+    if (arith == 0) hipLaunchKernelGGL((probe_cone_gain<T, 0>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((probe_cone_gain<T, 1>), grid, block, 0, stream, a);
+  } else if (a.source) launch_mode<T, kProbeSource>(a, arith, stream);
   else if (a.rmap) launch_mode<T, kProbeMap>(a, arith, stream);
   else if (a.rx) launch_mode<T, kProbeFaces>(a, arith, stream);
   else launch_mode<T, kProbePlain>(a, arith, stream);
@@ -76,6 +112,12 @@ void launch_probe_cone(DType dt, const ProbeArgs& a, int arith, hipStream_t stre
   else launch_typed<float>(a, arith, stream);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) fail(__FILE__, __LINE__, std::string("probe_cone launch: ") + hipGetErrorString(e));
+}
+
+void launch_gain_step(const int64_t* from, int64_t* to, int k, hipStream_t stream) {
+  hipLaunchKernelGGL(gain_step, dim3(1), dim3(64), 0, stream, from, to, k);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) fail(__FILE__, __LINE__, std::string("gain_step launch: ") + hipGetErrorString(e));
 }
 
 void launch_probe_advance(int64_t* base, int k, hipStream_t stream) {

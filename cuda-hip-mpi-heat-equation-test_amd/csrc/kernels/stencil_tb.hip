@@ -291,6 +291,13 @@ int occupancy_ins(DType dt, int k, int arith) {
   });
 }
 
+// Heat source with a gain schedule (tb_kernel_gain): resident waves per CU (one-wave workgroups)
+int occupancy_gain(DType dt, int k, int arith) {
+  HEAT2D_REQUIRE(arith == 0 || arith == 1, "a gain schedule needs arith 0 (exact) or 1 (fma)");
+  if (arith == 1) return dt == DType::F32 ? occupancy_waves_gain<float, 1>(k) : occupancy_waves_gain<double, 1>(k);
+  return dt == DType::F32 ? occupancy_waves_gain<float, 0>(k) : occupancy_waves_gain<double, 0>(k);
+}
+
 // Heat source (tb_kernel_src): resident waves per CU (one-wave workgroups)
 int occupancy_src(DType dt, int k, int arith) {
   HEAT2D_REQUIRE(arith == 0 || arith == 1, "a heat source needs arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 have no source kernels");
@@ -362,7 +369,8 @@ void fill_frames(DType dt, void* dst, const SlabLayout& L0, const TbRect* rects,
 int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
                        const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
                        double* partials, uint32_t* queue, int bc, bool pipe, const void* source = nullptr,
-                       const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr) {
+                       const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr,
+                       GainRef gain = {}) {
   // rx / ry != nullptr (the per-face diffusion numbers in the field's layout; Dirichlet axes only):
   // every launch, interior ones too, runs tb_kernel_div (ring 4, the general kernel's four edge kinds)
   // on at most as many waves as that kernel keeps resident; `r` is not used.
@@ -391,9 +399,11 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
     HEAT2D_REQUIRE(bc == 0, "a heat source needs Dirichlet boundaries on both axes");
     HEAT2D_REQUIRE(!partials && !pipe, "a heat source has no fused-statistics and no wave-pair kernel");
     HEAT2D_REQUIRE(k <= kMaxTBSrc, "temporal depth exceeds the heat-source kernels' deepest pass (kMaxTBSrc)");
-    nwaves = std::min<int64_t>(nwaves, (int64_t)cu_count() * occupancy_src(dt, k, arith));
+    // (with a gain schedule the launch runs tb_kernel_gain: that instance's own occupancy)
+    nwaves = std::min<int64_t>(nwaves, (int64_t)cu_count() * (gain.g ? occupancy_gain(dt, k, arith) : occupancy_src(dt, k, arith)));
     main = false;
   }
+  HEAT2D_REQUIRE(!gain.g || (source && gain.pos), "a gain schedule needs a heat source and its position word");
   HEAT2D_REQUIRE(nrect >= 1 && nrect <= (main ? kMainRects : kMaxRects), "bad rect count");
   HEAT2D_REQUIRE(!pipe || (main && !partials && pipe_available(dt, k, arith)), "no wave-pair kernel for this launch");
   const int ins = main ? 0 : ins_edges(bc);  // (interior launches: launch_rects keeps insulated edges out of them)
@@ -477,6 +487,18 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
       if (arith == 1) dispatch_var<double, 1>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, m64, stream);
       else dispatch_var<double, 0>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, m64, stream);
     }
+  } else if (source && gain.g) {  // the source scaled per step: tb_kernel_gain, the same launch shape
+    if (dt == DType::F32) {
+      const float *s32 = static_cast<const float*>(src) + o, *q32 = static_cast<const float*>(source) + o;
+      const float* g32 = static_cast<const float*>(gain.g);
+      if (arith == 1) dispatch_gain<float, 1>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, (float)r, q32, g32, gain.pos, stream);
+      else dispatch_gain<float, 0>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, (float)r, q32, g32, gain.pos, stream);
+    } else {
+      const double *s64 = static_cast<const double*>(src) + o, *q64 = static_cast<const double*>(source) + o;
+      const double* g64 = static_cast<const double*>(gain.g);
+      if (arith == 1) dispatch_gain<double, 1>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, r, q64, g64, gain.pos, stream);
+      else dispatch_gain<double, 0>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, r, q64, g64, gain.pos, stream);
+    }
   } else if (source) {
     if (dt == DType::F32) {
       const float *s32 = static_cast<const float*>(src) + o, *q32 = static_cast<const float*>(source) + o;
@@ -532,13 +554,13 @@ int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0,
                      const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
                      double* partials = nullptr, uint32_t* queue = nullptr, int bc = 0, bool pipe = false,
                      const void* source = nullptr, const void* rmap = nullptr, const void* rx = nullptr,
-                     const void* ry = nullptr) {
+                     const void* ry = nullptr, GainRef gain = {}) {
   HEAT2D_REQUIRE((bc & ~kBcAll) == 0, "bc must be a set of kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY");
   HEAT2D_REQUIRE(!((bc & kBcPeriodicX) && (bc & kBcInsulatedX)) && !((bc & kBcPeriodicY) && (bc & kBcInsulatedY)),
                  "an axis is periodic or insulated, not both");
   if (!(main && (bc & kBcInsulatedY))) {
     const int64_t nw = launch_rects_1(dt, src, dst, L0, k, ring, main, rects, nrect, nwaves, r, stream, arith, partials,
-                                      queue, bc, pipe, source, rmap, rx, ry);
+                                      queue, bc, pipe, source, rmap, rx, ry, gain);
     fill_frames(dt, dst, L0, rects, nrect, bc, stream);
     return nw;
   }
@@ -629,13 +651,13 @@ TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end
 
 void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end, int k,
                double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc, const void* source,
-               const void* rmap, const void* rx, const void* ry) {
-  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith, bc, source, rmap, rx, ry);
+               const void* rmap, const void* rx, const void* ry, GainRef gain) {
+  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith, bc, source, rmap, rx, ry, gain);
 }
 
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
                 int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc,
-                const void* source, const void* rmap, const void* rx, const void* ry) {
+                const void* source, const void* rmap, const void* rx, const void* ry, GainRef gain) {
   check_layout(dt, L, k);
   const int64_t n0 = std::max<int64_t>(0, re0 - rb0), n1 = std::max<int64_t>(0, re1 - rb1);
   if (n0 + n1 == 0) return;
@@ -650,7 +672,7 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
     if (n0 > 0) rects[nr++] = TbRect{rb0, re0, 0, p.nstrips, -std::min<int64_t>(s0, n0 * p.nstrips)};
     if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, -std::min<int64_t>(std::max<int64_t>(1, ns - s0), n1 * p.nstrips)};
     launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, p.nwaves, r, stream, arith, nullptr, nullptr, bc,
-                 false, source, rmap, rx, ry);
+                 false, source, rmap, rx, ry, gain);
     return;
   }
   const int64_t nb = std::max<int64_t>(p.ntiles, (n0 > 0) + (n1 > 0));
@@ -659,7 +681,7 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
   if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, std::min<int64_t>(nb - nb0, n1)};
   const int64_t slots = (int64_t)(cus > 0 ? cus : cu_count()) * p.blocks_per_cu * 4;
   launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, slots, r, stream, arith, nullptr, nullptr, bc, false,
-               source, rmap, rx, ry);
+               source, rmap, rx, ry, gain);
 }
 
 // r = 1/4 kernels (arith 2): an interior item costs 3 adds + 2 DPP moves per
@@ -934,19 +956,19 @@ bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i) {
 
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
                       hipStream_t stream, int arith, int bc, const void* source, const void* rmap, const void* rx,
-                      const void* ry) {
+                      const void* ry, GainRef gain) {
   HEAT2D_REQUIRE(i >= 0 && i < p.nedge, "edge rect index");
   const TbRect& R = p.edge[i];
   const bool on_main = edges_on_main(bc_layout(L, bc), p.k, &R, 1);
   const int64_t items = R.nb > 0 ? R.nb * (R.s1 - R.s0) : -R.nb;
   const int64_t slots = (int64_t)cu_count() * occupancy(dt, p.ring, on_main, p.k, arith) * 4;
   launch_rects(dt, src, dst, L, p.k, p.ring, on_main, &R, 1, std::min<int64_t>(items, slots), r, stream, arith,
-               nullptr, nullptr, bc, false, source, rmap, rx, ry);
+               nullptr, nullptr, bc, false, source, rmap, rx, ry, gain);
 }
 
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
                   double r, hipStream_t stream, int arith, uint32_t* queue, int bc, const void* source,
-                  const void* rmap, const void* rx, const void* ry) {
+                  const void* rmap, const void* rx, const void* ry, GainRef gain) {
   HEAT2D_REQUIRE(!(rx || ry) || !(p.flags & kPlanPipe), "face coefficients have no wave-pair kernel (no pipe plans)");
   HEAT2D_REQUIRE(!source || !(p.flags & kPlanPipe), "a heat source has no wave-pair kernel (no pipe plans)");
   HEAT2D_REQUIRE(!rmap || !(p.flags & kPlanPipe), "a diffusivity map has no wave-pair kernel (no pipe plans)");
@@ -959,15 +981,15 @@ void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, con
   if (p.valid == 2) {  // single general launch over the whole slab (no edge part)
     if (main_part)
       launch_rects(dt, src, dst, L, p.k, p.ring, false, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc, false,
-                   source, rmap, rx, ry);
+                   source, rmap, rx, ry, gain);
     return;
   }
   if (main_part)
     launch_rects(dt, src, dst, L, p.k, p.ring, true, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc,
-                 (p.flags & kPlanPipe) != 0, source, rmap, rx, ry);
+                 (p.flags & kPlanPipe) != 0, source, rmap, rx, ry, gain);
   else
     launch_rects(dt, src, dst, L, p.k, p.ring, edges_on_main(bc_layout(L, bc), p.k, p.edge, p.nedge), p.edge, p.nedge,
-                 p.edge_waves, r, stream, arith, nullptr, nullptr, bc, false, source, rmap, rx, ry);
+                 p.edge_waves, r, stream, arith, nullptr, nullptr, bc, false, source, rmap, rx, ry, gain);
 }
 
 }  // namespace kern

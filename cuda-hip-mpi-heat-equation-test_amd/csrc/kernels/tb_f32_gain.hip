@@ -1,0 +1,13 @@
+// Instantiation unit: the heat-source stencil with a per-step gain schedule
+// (float, ring 4, reference arithmetic AR = 0 and contracted fma AR = 1; see
+// tb_impl.hpp tb_kernel_gain / March GAIN).
+#include "tb_impl.hpp"
+
+namespace heat2d {
+namespace kern {
+namespace tbimpl {
+H2D_GAIN_UNIT(float, 0)
+H2D_GAIN_UNIT(float, 1)
+}  // namespace tbimpl
+}  // namespace kern
+}  // namespace heat2d

@@ -450,9 +450,19 @@ struct DivState<K, RING, true> {
     return *reinterpret_cast<const Q4*>(div_ring<K, WHICH>() + o + dlane);
   }
 };
+// GAIN (tb_kernel_gain, a source with a per-step gain: level s of a pass adds
+// g_s * S, T' = update + g_s * S — the product rounded, then the add; AR 1:
+// fma(g_s, S, update), one rounding): on top of SRC, the K gains of the pass,
+// wave-uniform, read before the march. (Empty unless GAIN, as the states above.)
+template <typename T, int K, bool GAIN>
+struct GainState {};
+template <typename T, int K>
+struct GainState<T, K, true> {
+  T gs[K];  // gs[s - 1]: the gain of level s
+};
 template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false,
-          bool SRC = false, bool VAR = false, bool DIV = false>
-struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, DIV> {
+          bool SRC = false, bool VAR = false, bool DIV = false, bool GAIN = false>
+struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, DIV>, GainState<T, K, GAIN> {
   using S = TbShape<T, NV, K>;
   static constexpr int V = S::V;
   static constexpr int VM = S::VM;
@@ -462,6 +472,7 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, 
   static_assert(RING % 2 == 0 && RING >= 4, "ring must be even (parity-indexed level rings) and >= 4");
   static_assert(!SRC || (NV == 1 && CL == K && (AR == 0 || AR == 1) && !ST),
                 "source term: 16 B per lane, one chain, unscaled arithmetic, no fused statistics");
+  static_assert(!GAIN || SRC, "a gain schedule scales a source");
   static_assert(!VAR || (NV == 1 && CL == K && (AR == 0 || AR == 1) && !ST && !SRC && !INS && EK == 0),
                 "diffusivity map: 16 B per lane, one chain, unscaled arithmetic, no statistics, source or insulated "
                 "edges; the map pins (EK 0)");
@@ -725,7 +736,10 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, 
       if constexpr (SRC) {  // + S(row m + off(s)): its own rounded add (-ffp-contract=off)
         const VT q = __builtin_bit_cast(VT, this->q_level(s));
 #pragma unroll
-        for (int e = 0; e < V; ++e) out[e] = out[e] + q[e];
+        for (int e = 0; e < V; ++e) {
+          if constexpr (GAIN) out[e] = AR == 1 ? fma_t(this->gs[s - 1], q[e], out[e]) : out[e] + this->gs[s - 1] * q[e];
+          else out[e] = out[e] + q[e];
+        }
       }
       if (s < K) {
 #pragma unroll
@@ -845,8 +859,8 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, 
 // level adds it with two packed adds (see SrcState).
 // VAR: a map row sits there in the same order and is the Row `re` of the level.
 template <int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false, bool SRC = false,
-          bool VAR = false>
-struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC || VAR> {
+          bool VAR = false, bool GAIN = false>
+struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC || VAR>, GainState<float, K, GAIN> {
   using F2 = float __attribute__((ext_vector_type(2)));
   using VT = float __attribute__((ext_vector_type(4)));
   using U4 = unsigned int __attribute__((ext_vector_type(4)));
@@ -854,6 +868,7 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC || VAR> {
   static_assert(RING % 2 == 0 && RING >= 4, "ring must be even and >= 4");
   static_assert(!SRC || (CL == K && (AR == 0 || AR == 1) && !ST),
                 "source term: one chain, unscaled arithmetic, no fused statistics");
+  static_assert(!GAIN || SRC, "a gain schedule scales a source");
   static_assert(!VAR || (CL == K && (AR == 0 || AR == 1) && !ST && !SRC && !INS && EK == 0),
                 "diffusivity map: one chain, unscaled arithmetic, no statistics, source or insulated edges; the map pins");
   struct Row {
@@ -1072,7 +1087,16 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC || VAR> {
         }
         if constexpr (SRC) {  // + S(row m + off(s)): its own rounded add (-ffp-contract=off)
           const VT q = __builtin_bit_cast(VT, this->q_level(s));
-          X[ps][i] = Row{X[ps][i].a + F2{q.x, q.y}, X[ps][i].b + F2{q.z, q.w}};
+          if constexpr (GAIN) {  // g_s * S rounded, then the add (AR 1: one fma)
+            const F2 g2{this->gs[s - 1], this->gs[s - 1]};
+            if constexpr (AR == 1)
+              X[ps][i] = Row{__builtin_elementwise_fma(g2, F2{q.x, q.y}, X[ps][i].a),
+                             __builtin_elementwise_fma(g2, F2{q.z, q.w}, X[ps][i].b)};
+            else
+              X[ps][i] = Row{X[ps][i].a + g2 * F2{q.x, q.y}, X[ps][i].b + g2 * F2{q.z, q.w}};
+          } else {
+            X[ps][i] = Row{X[ps][i].a + F2{q.x, q.y}, X[ps][i].b + F2{q.z, q.w}};
+          }
         }
         part = nxtpart;
       } else {
@@ -1088,7 +1112,13 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC || VAR> {
         }
         if constexpr (SRC) {  // (w in memory order, the ring row as (c0, c2, c1, c3))
           const VT q = __builtin_bit_cast(VT, this->q_level(K));
-          w = VT{w.x + q.x, w.y + q.z, w.z + q.y, w.w + q.w};
+          if constexpr (GAIN) {
+            const float g = this->gs[K - 1];
+            if constexpr (AR == 1) w = VT{fma_t(g, q.x, w.x), fma_t(g, q.z, w.y), fma_t(g, q.y, w.z), fma_t(g, q.w, w.w)};
+            else w = VT{w.x + g * q.x, w.y + g * q.z, w.z + g * q.y, w.w + g * q.w};
+          } else {
+            w = VT{w.x + q.x, w.y + q.z, w.z + q.y, w.w + q.w};
+          }
         }
         store_row(live, w);
         if constexpr (ST) {
@@ -1173,10 +1203,10 @@ constexpr bool kPackedF32 = false;
 constexpr int kInsRowLo = 1, kInsRowHi = 2, kInsColLo = 4, kInsColHi = 8;
 
 template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, bool PS = false, int CLX = 0,
-          bool INS = false, bool SRC = false, bool VAR = false, bool DIV = false>
+          bool INS = false, bool SRC = false, bool VAR = false, bool DIV = false, bool GAIN = false>
 __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r, int64_t strip, int64_t t0,
                                       int64_t t1, int lane, StatAcc* acc = nullptr, int ins = 0,
-                                      const T* qsrc = nullptr, const T* qsrc2 = nullptr) {
+                                      const T* qsrc = nullptr, const T* qsrc2 = nullptr, const T* gain = nullptr) {
   using S = TbShape<T, NV, K>;
   constexpr int V = S::V;
   constexpr int ES = (int)sizeof(T);
@@ -1190,8 +1220,8 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
   constexpr int CL = CLX > 0 ? (CLX < K ? CLX : K) : (ST ? K : chain_len<T, K>());
   // (DIV: the element-wise march in both dtypes)
   constexpr bool kPacked = kPackedF32<T, NV> && !DIV;
-  using W = typename std::conditional<kPacked, MarchF32<K, EK, RING, AR, ST, CL, INS, SRC, VAR>,
-                                      March<T, NV, K, EK, RING, AR, ST, CL, INS, SRC, VAR, DIV>>::type;
+  using W = typename std::conditional<kPacked, MarchF32<K, EK, RING, AR, ST, CL, INS, SRC, VAR, GAIN>,
+                                      March<T, NV, K, EK, RING, AR, ST, CL, INS, SRC, VAR, DIV, GAIN>>::type;
   W w;
   // row base = column col_lo (= -cpad) of row 0; offsets are relative to it
   w.srow = reinterpret_cast<const char*>(src + a.col_lo);
@@ -1245,6 +1275,10 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
     w.qrow = reinterpret_cast<const char*>(qsrc + a.col_lo);
     w.qdelta = w.qrow - w.srow;
     w.q_reset(lane);
+  }
+  if constexpr (GAIN) {  // the pass's K gains (gain: the entry of level 1), wave-uniform
+#pragma unroll
+    for (int s = 0; s < K; ++s) w.gs[s] = gain[s];
   }
   if constexpr (DIV) {  // RX (qsrc) and RY (qsrc2) have the field's layout
     w.dxdelta = reinterpret_cast<const char*>(qsrc + a.col_lo) - w.srow;
@@ -1538,6 +1572,45 @@ __global__ __launch_bounds__(64) void tb_kernel_src(const T* __restrict__ src, T
   queue_exit(a);
 }
 
+// The heat-source kernel with a gain schedule: level s of the pass adds
+// g[*pos + s - 1] * S (March GAIN). `g` and `pos` live in device memory — the
+// position is a word the solver moves between cycles, not an argument, so a
+// captured launch replays with the position of its replay. Every launch of a
+// cycle reads the same word; the K gains are wave-uniform loads ahead of the
+// march (the buffer is padded by kMaxTBSrc entries past its end). Items, kinds
+// and the LDS ring are tb_kernel_src's.
+template <typename T, int NV, int K, int RING, int AR>
+__global__ __launch_bounds__(64) void tb_kernel_gain(const T* __restrict__ src, T* __restrict__ dst, TbArgs a, T r,
+                                                     const T* __restrict__ q, const T* __restrict__ g,
+                                                     const int64_t* __restrict__ pos) {
+  using S = TbShape<T, NV, K>;
+  const int lane = threadIdx.x;
+  const int64_t wid = (int64_t)blockIdx.x;
+  if (wid >= a.nwaves) return;
+  const T* gp = g + *pos;
+  int64_t it = wid;
+  int32_t lin = tb_span<kMaxRects>(a, it).lin;
+  while (it < a.nitems) {
+    int64_t strip, t0, t1;
+    if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {
+      it = next_item(a, it);
+      if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;
+      continue;
+    }
+    lin += (int32_t)(t1 - t0);
+    const int64_t c0 = strip * S::U - S::KA;
+    const int ek = (((t0 - K < a.fixed_lo) || (t1 + K > a.fixed_hi)) ? 1 : 0) |
+                   (((c0 < 0) || (c0 + S::W > a.ncols)) ? 2 : 0);
+    switch (ek) {
+      case 0: march<T, NV, K, 0, RING, AR, false, false, K, false, true, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q, nullptr, gp); break;
+      case 1: march<T, NV, K, 1, RING, AR, false, false, K, false, true, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q, nullptr, gp); break;
+      case 2: march<T, NV, K, 2, RING, AR, false, false, K, false, true, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q, nullptr, gp); break;
+      default: march<T, NV, K, 3, RING, AR, false, false, K, false, true, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q, nullptr, gp); break;
+    }
+  }
+  queue_exit(a);
+}
+
 // The general kernel with a diffusivity map (`rmap`: the per-point diffusion
 // number in the field's layout, +0.0 at every pinned point, an argument of this
 // kernel only — TbArgs and every other kernel stay as they are; the scalar r is
@@ -1649,6 +1722,12 @@ template <typename T, int AR>
 void dispatch_src(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, T r, const T* q, hipStream_t s);
 template <typename T, int AR>
 int occupancy_waves_src(int k);
+// heat-source kernels with a gain schedule: the same family (tb_<dtype>_gain.hip, both forms per unit)
+template <typename T, int AR>
+void dispatch_gain(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, T r, const T* q, const T* g,
+                   const int64_t* pos, hipStream_t s);
+template <typename T, int AR>
+int occupancy_waves_gain(int k);
 // diffusivity-map kernels: ring 4, depths 1..kMaxTBVar (tb_<dtype>_var[_fma].hip)
 template <typename T, int AR>
 void dispatch_var(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, const T* rmap, hipStream_t s);
@@ -1827,6 +1906,53 @@ int waves_per_cu_src() {
   int occupancy_waves_src<T, AR>(int k) {                                                                     \
     switch (k) {                                                                                              \
       H2D_TB_CASES(H2D_SRC_OCC_CASE, T, 4, false, AR)                                                         \
+      default:                                                                                                \
+        break;                                                                                                \
+    }                                                                                                         \
+    return 4;                                                                                                 \
+  }
+
+// resident waves (one-wave workgroups) per CU of one tb_kernel_gain instance
+template <typename T, int K, int AR>
+int waves_per_cu_gain() {
+  static std::mutex mu;
+  static std::map<int, int> cache;  // device -> waves/CU
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> g(mu);
+  auto it = cache.find(dev);
+  if (it != cache.end()) return it->second;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tb_kernel_gain<T, 1, K, 4, AR>), 64,
+                                                   0) != hipSuccess ||
+      nb <= 0)
+    nb = 4;
+  cache[dev] = nb;
+  return nb;
+}
+#define H2D_GAIN_OCC_CASE(T, RING, MAIN, AR, KK) \
+  case KK:                                       \
+    return waves_per_cu_gain<T, KK, AR>();
+#define H2D_GAIN_CASE(T, RING, MAIN, AR, KK)                                                                  \
+  case KK:                                                                                                    \
+    hipLaunchKernelGGL((tb_kernel_gain<T, 1, KK, 4, AR>), dim3(nwaves), dim3(64), 0, s, src, dst, a, r, q, g, \
+                       pos);                                                                                  \
+    return;
+#define H2D_GAIN_UNIT(T, AR)                                                                                  \
+  template <>                                                                                                 \
+  void dispatch_gain<T, AR>(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, T r, const T* q,   \
+                            const T* g, const int64_t* pos, hipStream_t s) {                                  \
+    switch (k) {                                                                                              \
+      H2D_TB_CASES(H2D_GAIN_CASE, T, 4, false, AR)                                                            \
+      default:                                                                                                \
+        break;                                                                                                \
+    }                                                                                                         \
+    HEAT2D_REQUIRE(false, "temporal depth not instantiated for the gain-schedule kernel");                    \
+  }                                                                                                           \
+  template <>                                                                                                 \
+  int occupancy_waves_gain<T, AR>(int k) {                                                                    \
+    switch (k) {                                                                                              \
+      H2D_TB_CASES(H2D_GAIN_OCC_CASE, T, 4, false, AR)                                                        \
       default:                                                                                                \
         break;                                                                                                \
     }                                                                                                         \

@@ -13,6 +13,7 @@
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <dirent.h>
@@ -226,7 +227,7 @@ void write_rank(const std::string& dir, const std::string& name, int rank, Solve
 }
 
 void write_meta(const std::string& dir, const std::string& name, const Meta& m) {
-  char buf[1024];
+  char buf[1280];
   std::snprintf(buf, sizeof(buf),
                 "{\n \"format\": \"%s\",\n \"step\": %lld,\n \"nranks\": %d,\n \"dtype\": \"%s\",\n"
                 " \"n_owned\": %lld,\n \"n_input\": %lld,\n \"convention\": \"%s\",\n \"sigma\": %.17g,\n"
@@ -240,7 +241,9 @@ void write_meta(const std::string& dir, const std::string& name, const Meta& m) 
                 // (the key only with a diffusivity map: saves without one keep their key set)
                 ((m.rmap_sha256.empty() ? "" : " \"rmap_sha256\": \"" + m.rmap_sha256 + "\",\n") +
                  // (and the key of the face coefficients only with them)
-                 (m.faces_sha256.empty() ? "" : " \"faces_sha256\": \"" + m.faces_sha256 + "\",\n")).c_str());
+                 (m.faces_sha256.empty() ? "" : " \"faces_sha256\": \"" + m.faces_sha256 + "\",\n") +
+                 // (and the key of the source's gain schedule only with one)
+                 (m.source_gain_sha256.empty() ? "" : " \"source_gain_sha256\": \"" + m.source_gain_sha256 + "\",\n")).c_str());
   write_atomic(join(join(dir, name), "meta.json"), buf);  // + fsync of the step directory (rank files' entries)
   write_atomic(join(dir, "latest"), name + "\n");  // the commit point
   // prune: keep the two newest complete saves, ordered by (step, generation)
@@ -304,6 +307,12 @@ Meta read_meta(const std::string& dir) {
     m.rmap_sha256 = json_value(js, "rmap_sha256");
     while (!m.rmap_sha256.empty() && (m.rmap_sha256.back() == ' ' || m.rmap_sha256.back() == '\r')) m.rmap_sha256.pop_back();
     if (m.rmap_sha256 == "null") m.rmap_sha256.clear();
+  }
+  if (js.find("\"source_gain_sha256\"") != std::string::npos) {
+    m.source_gain_sha256 = json_value(js, "source_gain_sha256");
+    while (!m.source_gain_sha256.empty() && (m.source_gain_sha256.back() == ' ' || m.source_gain_sha256.back() == '\r'))
+      m.source_gain_sha256.pop_back();
+    if (m.source_gain_sha256 == "null") m.source_gain_sha256.clear();
   }
   if (js.find("\"faces_sha256\"") != std::string::npos) {
     m.faces_sha256 = json_value(js, "faces_sha256");
@@ -404,6 +413,70 @@ std::vector<char> read_source(const std::string& path, int64_t rows, int64_t col
 
 std::vector<char> read_faces(const std::string& path, int64_t rows, int64_t cols, int dtype, std::string* sha256) {
   return read_array(path, 2, rows, cols, dtype, sha256);
+}
+
+std::vector<char> read_gain(const std::string& path, int dtype, int64_t* len, std::string* sha256) {
+  std::vector<double> g;
+  {
+    File file(path, "rb");
+    unsigned char magic[6] = {0};
+    const bool npy = std::fread(magic, 1, 6, file.f) == 6 && std::memcmp(magic, "\x93NUMPY", 6) == 0;
+    std::rewind(file.f);
+    if (npy) {
+      unsigned char head[12];
+      HEAT2D_REQUIRE(std::fread(head, 1, 10, file.f) == 10, path + ": truncated header");
+      size_t hlen = (size_t)head[8] | ((size_t)head[9] << 8);
+      if (head[6] != 1) {
+        HEAT2D_REQUIRE(std::fread(head + 10, 1, 2, file.f) == 2, path + ": truncated header");
+        hlen |= ((size_t)head[10] << 16) | ((size_t)head[11] << 24);
+      }
+      HEAT2D_REQUIRE(hlen > 0 && hlen < (1u << 20), path + ": bad header length");
+      std::string h(hlen, '\0');
+      HEAT2D_REQUIRE(std::fread(&h[0], 1, hlen, file.f) == hlen, path + ": truncated header");
+      const bool f8 = h.find("'<f8'") != std::string::npos;
+      HEAT2D_REQUIRE(f8 || h.find("'<f4'") != std::string::npos, path + ": dtype is not little-endian f4/f8");
+      const size_t sp = h.find("'shape':");
+      long long n = 0;
+      char close = 0;
+      HEAT2D_REQUIRE(sp != std::string::npos && std::sscanf(h.c_str() + sp, "'shape': (%lld,%c", &n, &close) == 2 &&
+                         close == ')' && n >= 1,
+                     path + ": a gain schedule is a non-empty 1-D array");
+      g.resize((size_t)n);
+      if (f8) {
+        HEAT2D_REQUIRE(std::fread(g.data(), 8, (size_t)n, file.f) == (size_t)n, path + ": truncated data");
+      } else {
+        std::vector<float> raw((size_t)n);
+        HEAT2D_REQUIRE(std::fread(raw.data(), 4, (size_t)n, file.f) == (size_t)n, path + ": truncated data");
+        for (size_t i = 0; i < raw.size(); ++i) g[i] = (double)raw[i];
+      }
+    } else {
+      char line[512];
+      while (std::fgets(line, sizeof(line), file.f)) {
+        if (char* c = std::strchr(line, '#')) *c = '\0';
+        char* p = line;
+        while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') ++p;
+        if (!*p) continue;
+        char* end = nullptr;
+        const double v = std::strtod(p, &end);
+        HEAT2D_REQUIRE(end != p, path + ": not a number: " + std::string(p));
+        while (*end == ' ' || *end == '\t' || *end == '\r' || *end == '\n') ++end;
+        HEAT2D_REQUIRE(!*end, path + ": one number per line");
+        g.push_back(v);
+      }
+      HEAT2D_REQUIRE(!g.empty(), path + ": an empty gain schedule");
+    }
+  }
+  std::vector<char> out(g.size() * (dtype == 0 ? 4 : 8));
+  for (size_t i = 0; i < g.size(); ++i) {
+    const double v = dtype == 0 ? (double)(float)g[i] : g[i];
+    HEAT2D_REQUIRE(std::isfinite(v) && v >= 0.0,
+                   path + ": entry " + std::to_string(i) + " is not finite and >= 0 (put the sign into the source)");
+    if (dtype == 0) reinterpret_cast<float*>(out.data())[i] = (float)g[i];
+    else reinterpret_cast<double*>(out.data())[i] = g[i];
+  }
+  if (len) *len = (int64_t)g.size();
+  if (sha256) *sha256 = sha256_hex(out.data(), out.size());
+  return out;
 }
 
 void read_rows(const Meta& m, int64_t row0, int64_t nrows, int64_t ncols, int dtype, void* out) {

@@ -328,6 +328,7 @@ Solver::~Solver() {
     if (d_part_) (void)hipFree(d_part_);
     if (d_queue_) (void)hipFree(d_queue_);
     free_probes();
+    free_gain();
     // the streams go before the events recorded on them (captures included)
     if (own_streams_) {
       (void)hipStreamDestroy(s_compute_);
@@ -345,6 +346,7 @@ Solver::~Solver() {
     std::free(rmap_buf_);
     for (auto& b : face_buf_) std::free(b);
     free_probes();
+    free_gain();
   }
 }
 
@@ -366,6 +368,7 @@ void Solver::init(const kern::IcParams& ic, const double* xg, const double* yg) 
   for (int b = 0; b < 2; ++b) wrap_cols_all(buf_[b]);
   // ghost rows are filled from the global IC directly: no exchange needed
   cur_ = 0;
+  set_gain_words();  // (the schedule keeps its position; the word of parity 0 may be a cycle behind)
   steps_ = 0;
   ghost_ = cfg_.bc_x == kBcPeriodic ? 0 : (int)band_;
   last_x_[0] = last_x_[1] = 0;
@@ -404,9 +407,9 @@ bool Solver::pipe_ok(int k) const {
 void Solver::launch_tb(const void* src, void* dst, int64_t rb, int64_t re, int k) {
   if (re <= rb) return;
   if (hip_)
-    kern::launch_tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, s_compute_, cfg_.tile_rows, compute_cus_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry());
+    kern::launch_tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, s_compute_, cfg_.tile_rows, compute_cus_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain());
   else
-    cpu::tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry());
+    cpu::tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain());
 }
 
 void Solver::exchange_on(void* field, int64_t k, hipStream_t s) {
@@ -508,7 +511,7 @@ void Solver::launch_stats_cycle(int k) {
   roctxRangePushA("heat2d.cycle.stats");
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_comm_, 0));
-  launch_probes(k, s_compute_);
+  launch_cycle_aux(k, s_compute_);
   kern::launch_tb_stats(dtype(), buf_[cur_], buf_[cur_ ^ 1], L_, k, cfg_.r, d_part_,
                         d_work_ + kern::stats_work_elems(), s_compute_, cfg_.arith, bc_);
   H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
@@ -534,7 +537,7 @@ void Solver::cycle_finish() {
     if (pe) H2D_HIP(hipEventRecord(pe->ev[5], s_comm_));
     if (pend_frame_ >= 0) {  // the edge rank's frame-side band (launch_overlap), after the exchange
       kern::launch_edge_rect(dtype(), buf_[cur_], dst, L_, split_plan_banded(pend_k_, pend_frame_b_), pend_frame_, cfg_.r,
-                             s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry());
+                             s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain());
       // the next cycle's compute-stream work waits for it (and so for the
       // exchange ahead of it); ev_bnd_, posted to the transport, is left alone
       H2D_HIP(hipEventRecord(ev_frame_, s_comm_));
@@ -548,6 +551,7 @@ void Solver::cycle_finish() {
   pend_pe_ = -1;
   steps_ += pend_k_;
   if (probe_cap_ > 0) probe_rec_ += pend_k_;
+  if (gain_on()) gain_pos_ += pend_k_;
   hist_[pend_k_] += 1;
   last_k_ = pend_k_;
   ghost_ = pend_x_;
@@ -565,7 +569,7 @@ void Solver::launch_serial(int k) {
   roctxRangePushA("heat2d.cycle.serial");
   PhaseEvents* pe = (timing_ && hip_) ? phase_begin(1) : nullptr;
   if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-  launch_probes(k, s_compute_);
+  launch_cycle_aux(k, s_compute_);
   cycle_compute(k);
   if (pe) H2D_HIP(hipEventRecord(pe->ev[4], s_compute_));
   if (tr_->exchanges()) {
@@ -799,8 +803,8 @@ void Solver::trial_cycle(const kern::SplitPlan& c) {
   last_k_ = 0;  // the other buffer no longer holds T_{n-1}: stats(residual) reports NaN
   if (c.valid == 3) {  // edge-first: both parts in order on the compute stream
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
-    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
-    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
+    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
     return;
@@ -808,15 +812,15 @@ void Solver::trial_cycle(const kern::SplitPlan& c) {
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
   H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));
   if (c.flags & kern::kPlanLead) {  // lead: the band launch issued first
-    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
-    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
+    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
     return;
   }
-  kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
+  kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
   H2D_HIP(hipEventRecord(ev_int_, s_compute_));
-  kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
+  kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain());
   H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
 }
 
@@ -1220,10 +1224,10 @@ void Solver::launch_overlap(int k, int64_t B) {
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));  // edge part c-1
     H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));     // main part c-1
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_comm_));
-    launch_probes(k, s_comm_);
-    kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry());
+    launch_cycle_aux(k, s_comm_);
+    kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_comm_));
@@ -1239,13 +1243,13 @@ void Solver::launch_overlap(int k, int64_t B) {
     // comm stream (cycle_finish) = [bands(c) done] exchange(c), beside the interior.
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_comm_, 0));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_compute_));
-    launch_probes(k, s_compute_);
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
+    launch_cycle_aux(k, s_compute_);
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
     if (tr_->exchanges()) tr_->post(dst, L_, ev_bnd_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     pend_ = Pending::EdgeFirst;
@@ -1254,26 +1258,26 @@ void Solver::launch_overlap(int k, int64_t B) {
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));  // edge part c-1 (record not yet replaced)
   H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));     // main part c-1
   if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_comm_));
-  launch_probes(k, s_comm_);  // (ahead of the band launch in every order below)
+  launch_cycle_aux(k, s_comm_);  // (ahead of the band launch in every order below)
   if (lead) {
     // lead: the band launch first (comm stream), then the interior beside it
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
   } else if (sp.valid) {
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain());
   } else {  // slab too thin / narrow to split: all of it beside the exchange
     if (pe) {
       H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
       H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     }
-    kern::launch_tb(dtype(), src, dst, L_, 0, L_.nrows, k, cfg_.r, s_comm_, 0, 0, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry());
+    kern::launch_tb(dtype(), src, dst, L_, 0, L_.nrows, k, cfg_.r, s_comm_, 0, 0, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain());
   }
   if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_comm_));
   H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
@@ -1310,6 +1314,7 @@ void Solver::run_graph_cycles(int64_t npairs) {
   if (npairs > 0 && tr_->exchanges()) tr_->graph_launched(s_compute_);
   hist_[K] += 2 * npairs;
   if (probe_cap_ > 0) probe_rec_ += 2 * npairs * K;
+  if (gain_on()) gain_pos_ += 2 * npairs * K;
   if (npairs > 0) {
     last_k_ = K;
     ghost_ = K;  // both captured cycles exchange K rows
@@ -1342,7 +1347,7 @@ void Solver::ensure_pair_graph() {
     hipGraph_t g = nullptr;
     const hipEvent_t fork = ev_fork_, join = ev_join_;  // (the solver's own: see runtime.hpp)
     const int saved = cur_, saved_ghost = ghost_, saved_last = last_k_;
-    const int64_t saved_steps = steps_, saved_hist = hist_[K], saved_halo = halo_rows_, saved_rec = probe_rec_;
+    const int64_t saved_steps = steps_, saved_hist = hist_[K], saved_halo = halo_rows_, saved_rec = probe_rec_, saved_gain = gain_pos_;
     ghost_ = (int)band_;  // replays start after step()'s top-up
     const int saved_lx0 = last_x_[0], saved_lx1 = last_x_[1];
     if (tr_->exchanges()) last_x_[0] = last_x_[1] = (int)band_;  // whatever a replay follows
@@ -1379,6 +1384,7 @@ void Solver::ensure_pair_graph() {
     cur_ = saved;
     steps_ = saved_steps;
     probe_rec_ = saved_rec;
+    gain_pos_ = saved_gain;
     hist_[K] = saved_hist;
     ghost_ = saved_ghost;
     last_k_ = saved_last;
@@ -1442,7 +1448,7 @@ std::vector<int> Solver::step_cycles(int64_t n) const {
 
 void Solver::step(int64_t n) {
   if (n <= 0) return;
-  probe_room(n);
+  step_room(n);
   if (hip_) H2D_HIP(hipSetDevice(cfg_.device));
   if (cfg_.copy_swap) {
     for (int64_t i = 0; i < n; ++i) cycle_copy_swap();
@@ -1735,7 +1741,7 @@ void Solver::capture_schedule(int64_t n) {
     (void)split_plan_banded(sc[i], std::max(sc[i], exchange_depth(sc, i, sc[0])));
   synchronize();
   const int saved = cur_, saved_ghost = ghost_, saved_last = last_k_;
-  const int64_t saved_steps = steps_, saved_halo = halo_rows_, saved_rec = probe_rec_;
+  const int64_t saved_steps = steps_, saved_halo = halo_rows_, saved_rec = probe_rec_, saved_gain = gain_pos_;
   ghost_ = (int)band_;  // replays start after step()'s top-up
   const int saved_lx0 = last_x_[0], saved_lx1 = last_x_[1];
   if (tr_->exchanges()) last_x_[0] = last_x_[1] = (int)band_;  // whatever a replay follows
@@ -1763,6 +1769,7 @@ void Solver::capture_schedule(int64_t n) {
   cur_ = saved;
   steps_ = saved_steps;
   probe_rec_ = saved_rec;
+  gain_pos_ = saved_gain;
   ghost_ = saved_ghost;
   last_k_ = saved_last;
   halo_rows_ = saved_halo;
@@ -1807,6 +1814,7 @@ void Solver::run_schedule_graph(int64_t n) {
     hist_[sc[i]] += 1;
     steps_ += sc[i];
     if (probe_cap_ > 0) probe_rec_ += sc[i];
+    if (gain_on()) gain_pos_ += sc[i];
     if (tr_->exchanges()) halo_rows_ += exchange_depth(sc, i, sc[0]);
   }
   last_k_ = sc.back();
@@ -1970,7 +1978,7 @@ void Solver::synchronize() {
 
 void Solver::step_stats(int64_t n, double out[6]) {
   HEAT2D_REQUIRE(n >= 1, "step_stats needs n >= 1");
-  probe_room(n);
+  step_room(n);
   if (hip_) H2D_HIP(hipSetDevice(cfg_.device));
   // (periodic y: the fused-statistics march would count its ghost columns;
   // insulated axes: the fused-statistics kernel has no insulated edges)
@@ -2146,6 +2154,7 @@ void Solver::set_source(const void* host, int64_t ld) {
   drop_graphs();
   if (!host) {
     src_on_ = false;
+    free_gain();  // (a schedule scales a source: none without one)
     return;
   }
   HEAT2D_REQUIRE(ld >= L_.ncols + 2, "set_source: leading dimension below ncols + 2");
@@ -2165,6 +2174,63 @@ void Solver::set_source(const void* host, int64_t ld) {
   if (hip_) H2D_HIP(hipMemcpy(src_buf_, stage.data(), stage.size(), hipMemcpyHostToDevice));
   else std::memcpy(src_buf_, stage.data(), stage.size());
   src_on_ = true;
+}
+
+void Solver::free_gain() {
+  if (hip_) {
+    if (gain_buf_) (void)hipFree(gain_buf_);
+    if (gain_posw_) (void)hipFree(gain_posw_);
+  } else {
+    std::free(gain_buf_);
+    std::free(gain_posw_);
+  }
+  gain_buf_ = nullptr;
+  gain_posw_ = nullptr;
+  gain_len_ = gain_pos_ = 0;
+}
+
+// The schedule's device copy carries kMaxTBSrc entries of padding (+0.0) past
+// its end: a trial cycle, which reads the current position at any depth and
+// whose result is dropped, stays in bounds. Both position words take `start`;
+// the one of the current buffer parity is the one the next cycle reads.
+void Solver::set_source_gain(const void* host, int64_t len, int64_t start) {
+  HEAT2D_REQUIRE(host == nullptr || src_on_,
+                 "a gain schedule scales a heat source: this solver has none (pass source= / set_source first)");
+  if (hip_) H2D_HIP(hipSetDevice(cfg_.device));
+  synchronize();
+  drop_graphs();
+  free_gain();
+  if (!host) return;
+  HEAT2D_REQUIRE(len >= 1, "set_source_gain: an empty schedule");
+  HEAT2D_REQUIRE(start >= 0 && start <= len, "set_source_gain: start outside [0, length]");
+  const size_t es = dtype_size(dtype());
+  const size_t bytes = (size_t)(len + kMaxTBSrc) * es;
+  std::vector<char> stage(bytes, 0);
+  std::memcpy(stage.data(), host, (size_t)len * es);
+  if (hip_) {
+    H2D_HIP(hipMalloc(&gain_buf_, bytes));
+    H2D_HIP(hipMemcpy(gain_buf_, stage.data(), bytes, hipMemcpyHostToDevice));
+    H2D_HIP(hipMalloc(reinterpret_cast<void**>(&gain_posw_), 2 * sizeof(int64_t)));
+  } else {
+    gain_buf_ = host_alloc(bytes);
+    std::memcpy(gain_buf_, stage.data(), bytes);
+    gain_posw_ = static_cast<int64_t*>(host_alloc(2 * sizeof(int64_t)));
+  }
+  gain_len_ = len;
+  gain_pos_ = start;
+  set_gain_words();
+}
+
+void Solver::set_gain_words() {
+  if (!gain_posw_) return;
+  const int64_t words[2] = {gain_pos_, gain_pos_};
+  if (hip_) {
+    H2D_HIP(hipSetDevice(cfg_.device));
+    synchronize();
+    H2D_HIP(hipMemcpy(gain_posw_, words, sizeof(words), hipMemcpyHostToDevice));
+  } else {
+    std::memcpy(gain_posw_, words, sizeof(words));
+  }
 }
 
 void Solver::set_rmap(const void* host, int64_t ld) {
@@ -2319,11 +2385,15 @@ void Solver::clear_probe_history() {
   set_probe_base();
 }
 
-void Solver::probe_room(int64_t n) const {
+void Solver::step_room(int64_t n) const {
   HEAT2D_REQUIRE(probe_cap_ == 0 || probe_rec_ + n <= probe_cap_,
                  "probe history full: " + std::to_string(probe_rec_) + " of " + std::to_string(probe_cap_) +
                      " steps recorded, " + std::to_string(n) + " more asked for (set_probes with a larger capacity, or "
                      "clear_probe_history)");
+  HEAT2D_REQUIRE(!gain_on() || gain_pos_ + n <= gain_len_,
+                 "source gain schedule exhausted: at position " + std::to_string(gain_pos_) + " of " +
+                     std::to_string(gain_len_) + ", " + std::to_string(n) + " more steps asked for (set_source_gain "
+                     "with a longer schedule)");
 }
 
 void Solver::probe_history(void* host) {
@@ -2342,9 +2412,22 @@ void Solver::probe_history(void* host) {
 // the row base, on the stream of the cycle's band launch behind the waits that
 // launch makes: the source buffer is complete there (ghost rows included), and
 // whatever overwrites it next waits for that stream's band launch.
-void Solver::launch_probes(int k, hipStream_t stream) {
+// With a gain schedule, first the position of the NEXT cycle: the word of the
+// other buffer parity <- this cycle's + k. This stream is ordered behind every
+// launch of the previous cycle (the readers of the word written), and every
+// launch of the next cycle is ordered behind this stream's band launch; this
+// cycle's launches all read this parity's word, which nothing writes until
+// the next cycle. Trial cycles never come here: they move nothing.
+void Solver::launch_cycle_aux(int k, hipStream_t stream) {
+  const kern::GainRef g = gain();
+  if (g.g) {
+    if (hip_) kern::launch_gain_step(gain_posw_ + cur_, gain_posw_ + (cur_ ^ 1), k, stream);
+    else gain_posw_[cur_ ^ 1] = gain_posw_[cur_] + k;
+  }
   if (probe_idx_.empty()) return;
   kern::ProbeArgs a{};
+  a.gain = g.g;
+  a.gain_pos = g.pos;
   a.src = buf_[cur_];
   a.source = source();
   a.rmap = rmap();
@@ -2424,7 +2507,7 @@ void LoopbackGroup::init(const kern::IcParams& ic, const double* xg, const doubl
 // exchanges — the order a multi-process run gets from RCCL's rendezvous.
 void LoopbackGroup::step(int64_t n) {
   if (n <= 0) return;
-  for (auto& m : members_) m->probe_room(n);
+  for (auto& m : members_) m->step_room(n);
   const int K = members_[0]->pref_depth();
   std::vector<int> seq;
   for (int64_t left = n; left > 0;) {
@@ -2469,6 +2552,10 @@ void LoopbackGroup::set_rmap(const void* host, int64_t ld) {
 
 void LoopbackGroup::set_faces(const void* rx, const void* ry, int64_t ld) {
   for (auto& m : members_) m->set_faces(rx, ry, ld);
+}
+
+void LoopbackGroup::set_source_gain(const void* host, int64_t len, int64_t start) {
+  for (auto& m : members_) m->set_source_gain(host, len, start);
 }
 
 void LoopbackGroup::set_probes(const int64_t* points, int64_t count, int64_t capacity) {

@@ -81,6 +81,28 @@ def _source_array(source, nrows_global: int, ncols: int, np_dtype) -> np.ndarray
     return a
 
 
+def _gain_array(source_gain, np_dtype) -> np.ndarray:
+    """The gain schedule in the field's dtype: 1-D, non-empty, every entry
+    finite and >= 0 (ValueError otherwise). The solver's copy of the source
+    holds -0.0 at pinned points and g * -0.0 keeps -0.0 only for g >= 0: the
+    sign of the heating belongs into the source."""
+    a = np.asarray(source_gain)
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError(f"source_gain must be a non-empty 1-D array, got shape {a.shape}")
+    a = np.ascontiguousarray(a, dtype=np_dtype)
+    if not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError("source_gain entries must be finite and >= 0 (put the sign into the source)")
+    return a
+
+
+def _gain_info(h) -> dict:
+    """info()["source_gain"]: whether a schedule is set, its length and the
+    position of the next step's entry."""
+    v = (C.c_int64 * 3)()
+    N.call("heat2d_solver_source_gain", h, v)
+    return {"set": bool(v[0]), "length": int(v[1]), "position": int(v[2])}
+
+
 def _source_info(h) -> dict:
     """info()["source"]: whether the solver was built for a heat source, whether
     one is set, and the depth clamp that then applies (0: none)."""
@@ -264,6 +286,16 @@ class HeatSolver:
             when r is a power of two, else exact — never jacobi); the depth is
             clamped to the source kernels' deepest pass (info()["source"]).
             :meth:`set_source` replaces or clears it between steps.
+        source_gain: with source=, a 1-D array G of per-step gains, finite and
+            >= 0, converted to the run's dtype: the separable time-dependent
+            source G[q] * S. The step at position q adds G[q] * S — the product
+            rounded, then the add; "fma": fma(G[q], S, update), one rounding —
+            at every fused level of any pass (models.reference.ftcs(source_gain=)
+            bitwise). The position starts at 0 and moves by one per step taken by
+            step() / step_stats(), however the call is cut into cycles; prepare()
+            and the autotuner consume nothing; a step(n) past the end of G raises
+            before it launches anything. G == 1 gives the bits of source= alone.
+            :meth:`set_source_gain` replaces or clears it between steps.
         rmap: a diffusivity map, u_t = nu(x, y) lap(u) (the NON-divergence
             form: variable heat capacity over constant conductivity; not
             div(k grad u)): the GLOBAL frame-inclusive array (rows + 2) x
@@ -317,7 +349,7 @@ class HeatSolver:
                  comm_cus: int = 0, autotune: int = -1, engine: str = "tb", arith: str = "auto",
                  slab_row0: Optional[int] = None, edge_shift: int = 0, bc_x: str = "dirichlet",
                  bc_y: str = "dirichlet", source=None, rmap=None, faces=None, probes=None,
-                 probe_steps: Optional[int] = None):
+                 probe_steps: Optional[int] = None, source_gain=None):
         self.problem = problem
         self.edge_shift = 0 if bc_x == "periodic" else int(edge_shift)  # (periodic x: no edge slabs)
         self.bc_x, self.bc_y = bc_x, bc_y
@@ -364,6 +396,7 @@ class HeatSolver:
         self.arith = arith
         cfg.source = int(source is not None)
         self.source_sha256 = None
+        self.source_gain_sha256 = None
         cfg.rmap = int(rmap is not None)
         self.rmap_sha256 = None
         if rmap is not None and arith == "auto":
@@ -380,6 +413,8 @@ class HeatSolver:
         N.call("heat2d_solver_layout", self._h, C.byref(self.layout))
         if source is not None:
             self.set_source(source)
+        if source_gain is not None:
+            self.set_source_gain(source_gain)
         if rmap is not None:
             self.set_rmap(rmap)
         if faces is not None:
@@ -467,6 +502,7 @@ class HeatSolver:
         if source is None:
             N.call("heat2d_solver_set_source", self._h, None, 0)
             self.source_sha256 = None
+            self.source_gain_sha256 = None  # (a schedule scales a source: cleared with it)
             return
         a = _source_array(source, int(self.layout.nrows_global), self.ncols, self.np_dtype)
         N.call("heat2d_solver_set_source", self._h, a.ctypes.data_as(C.c_void_p), a.shape[1])
@@ -474,6 +510,23 @@ class HeatSolver:
         self.source_sha256 = hashlib.sha256(a.tobytes()).hexdigest()
 
     # ------------------------------------------------------------------ info
+    def set_source_gain(self, source_gain, start: int = 0) -> None:
+        """Replace the source's gain schedule (see the class docstring) or clear
+        it (None: the source as it is again, bit for bit), between step()
+        calls. The next step takes ``source_gain[start]``. Needs a source
+        (RuntimeError without one); entries finite and >= 0, 1-D, non-empty
+        (ValueError). Synchronises; captured graphs are dropped."""
+        if source_gain is None:
+            N.call("heat2d_solver_set_source_gain", self._h, None, 0, 0)
+            self.source_gain_sha256 = None
+            return
+        a = _gain_array(source_gain, self.np_dtype)
+        if not 0 <= int(start) <= a.size:
+            raise ValueError(f"start must be in [0, {a.size}], got {start}")
+        N.call("heat2d_solver_set_source_gain", self._h, a.ctypes.data_as(C.c_void_p), a.size, int(start))
+        # what a checkpoint records of the schedule: the digest of the converted bytes
+        self.source_gain_sha256 = hashlib.sha256(a.tobytes()).hexdigest()
+
     @property
     def rank(self) -> int:
         return self.transport.rank
@@ -504,6 +557,7 @@ class HeatSolver:
                 "arith": _arith(self._h),  # the resolved code: 0 exact, 1 fma, 2 jacobi, 3 fast
                 "bc_x": self._bc()[0], "bc_y": self._bc()[1],  # "dirichlet" | "periodic" | "insulated", as the native solver runs
                 "source": _source_info(self._h),
+                "source_gain": _gain_info(self._h),  # {"set", "length", "position"}
                 "rmap": _rmap_info(self._h),
                 "faces": _faces_info(self._h),
                 "probes": self._probes(),  # {"count": this rank's, "capacity", "recorded"}
@@ -745,7 +799,7 @@ class LoopbackGroup:
                  tb: int = 0, tile_rows: int = 0, device: Optional[int] = None, arith: str = "auto",
                  overlap: bool = True, autotune: int = -1, comm_cus: int = 0, edge_shift: int = 0,
                  bc_x: str = "dirichlet", bc_y: str = "dirichlet", source=None, rmap=None, faces=None,
-                 probes=None, probe_steps: Optional[int] = None):
+                 probes=None, probe_steps: Optional[int] = None, source_gain=None):
         self.problem = problem
         self.bc_x, self.bc_y = bc_x, bc_y
         self.backend = resolve_backend(backend)
@@ -778,6 +832,8 @@ class LoopbackGroup:
         self._h = h
         if source is not None:
             self.set_source(source)
+        if source_gain is not None:
+            self.set_source_gain(source_gain)
         if rmap is not None:
             self.set_rmap(rmap)
         if faces is not None:
@@ -802,6 +858,21 @@ class LoopbackGroup:
         m = self.problem.n_owned
         a = _source_array(source, m, m, NP_DTYPES[self.dtype])
         N.call("heat2d_group_set_source", self._h, a.ctypes.data_as(C.c_void_p), m + 2)
+
+    def set_source_gain(self, source_gain, start: int = 0) -> None:
+        """The source's gain schedule on every member (HeatSolver.set_source_gain):
+        each takes the whole schedule, nothing is exchanged. None clears it."""
+        if source_gain is None:
+            N.call("heat2d_group_set_source_gain", self._h, None, 0, 0)
+            return
+        a = _gain_array(source_gain, NP_DTYPES[self.dtype])
+        if not 0 <= int(start) <= a.size:
+            raise ValueError(f"start must be in [0, {a.size}], got {start}")
+        N.call("heat2d_group_set_source_gain", self._h, a.ctypes.data_as(C.c_void_p), a.size, int(start))
+
+    def gain_info(self, i: int = 0) -> dict:
+        """info()["source_gain"] of member i."""
+        return _gain_info(self._member(i))
 
     def set_rmap(self, rmap) -> None:
         """Replace (the global frame-inclusive array) or drop (None) the

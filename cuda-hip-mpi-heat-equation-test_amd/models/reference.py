@@ -117,13 +117,18 @@ def fma(a, b, c):
     return th + _sum_round_odd(tl, ul)
 
 
-def _ftcs_step_source(T: np.ndarray, r, arith: str, source: np.ndarray) -> np.ndarray:
+def _ftcs_step_source(T: np.ndarray, r, arith: str, source: np.ndarray, gain=None) -> np.ndarray:
     """One step with a heat source: the update of :func:`ftcs_step`, rounded as
     it is there, then one separately rounded add of the source,
         exact: T' = (C + r*((((S_+E)+N)+W) - 4C)) + S[i,j]
         fma:   T' = fma(r, fma(-4, C, sum), C)    + S[i,j]
     at the owned points; the frame stays pinned and the frame entries of
-    ``source`` are ignored."""
+    ``source`` are ignored.
+    gain (a scalar g, finite and >= 0, converted to the field's dtype): the step
+    of a time-dependent source g(t) * S,
+        exact: T' = upd + (g * S[i,j])      (the product rounded, then the add)
+        fma:   T' = fma(g, S[i,j], upd)     (one rounding)
+    g == 1 gives the bits of the source alone in both forms. None: no gain."""
     if arith not in ("exact", "fma"):
         raise ValueError("a heat source needs arith 'exact' or 'fma'")
     if source.shape != T.shape:
@@ -138,7 +143,16 @@ def _ftcs_step_source(T: np.ndarray, r, arith: str, source: np.ndarray) -> np.nd
         upd = fma(np.broadcast_to(r, c.shape), fma(np.broadcast_to(-four, c.shape), c, total), c)
     else:
         upd = c + r * (total - four * c)
-    out[1:-1, 1:-1] = upd + S[1:-1, 1:-1]
+    if gain is None:
+        out[1:-1, 1:-1] = upd + S[1:-1, 1:-1]
+        return out
+    g = T.dtype.type(gain)
+    if not (np.isfinite(g) and g >= 0):
+        raise ValueError("a source gain must be finite and >= 0 (put the sign into the source)")
+    if arith == "fma":
+        out[1:-1, 1:-1] = fma(np.broadcast_to(g, c.shape), S[1:-1, 1:-1], upd)
+    else:
+        out[1:-1, 1:-1] = upd + g * S[1:-1, 1:-1]
     return out
 
 
@@ -199,7 +213,7 @@ def _ftcs_step_faces(T: np.ndarray, arith: str, faces) -> np.ndarray:
 
 
 def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
-              source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None) -> np.ndarray:
+              source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None, gain=None) -> np.ndarray:
     """One FTCS step of a frame-inclusive field. On a Dirichlet axis the frame
     is kept fixed; on a periodic or insulated one it is refreshed from the
     owned points before the step (:func:`wrap_frame`) — the update and its
@@ -218,7 +232,11 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
     differ, while with "exact" they are bitwise equal.
     faces ((RX, RY), per-face diffusion numbers; Dirichlet axes, arith "exact" or
     "fma", no source, no rmap): the conservative form (:func:`_ftcs_step_faces`);
-    ``r`` is then not used. None: today's function."""
+    ``r`` is then not used. None: today's function.
+    gain (with source=): this step's gain of a time-dependent source
+    (:func:`_ftcs_step_source`). None: the source as it is."""
+    if gain is not None and source is None:
+        raise ValueError("gain= scales a heat source: pass source=")
     if faces is not None:
         if rmap is not None or source is not None:
             raise ValueError("face coefficients together with rmap= or source= are not offered")
@@ -236,7 +254,7 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
     if source is not None:
         if bc_x != "dirichlet" or bc_y != "dirichlet":
             raise ValueError("a heat source needs Dirichlet boundaries on both axes")
-        return _ftcs_step_source(T, r, arith, source)
+        return _ftcs_step_source(T, r, arith, source, gain)
     T = wrap_frame(T, bc_x, bc_y)
     r = T.dtype.type(r)
     four = T.dtype.type(4)
@@ -257,14 +275,23 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
 
 def ftcs(problem: Problem, nsteps: int | None = None, dtype=np.float64, T0: np.ndarray | None = None,
          arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
-         source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None) -> np.ndarray:
+         source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None,
+         source_gain=None, gain_start: int = 0) -> np.ndarray:
     """Run FTCS; returns the frame-inclusive field (frame entries on periodic
     / insulated axes: wrap / edge images of the returned owned points).
     source: a heat source added at every step (:func:`ftcs_step`).
     rmap: a diffusivity map in place of problem.r (:func:`ftcs_step`).
-    faces: (RX, RY) per-face diffusion numbers, the conservative form (:func:`ftcs_step`)."""
+    faces: (RX, RY) per-face diffusion numbers, the conservative form (:func:`ftcs_step`).
+    source_gain (with source=): a 1-D array G of per-step gains, the separable
+    time-dependent source G[q] * S; step q of this run takes G[gain_start + q]
+    (:func:`ftcs_step` gain=)."""
     T = initial_field(problem, dtype) if T0 is None else T0.astype(dtype)
     n = problem.ntime if nsteps is None else nsteps
+    if source_gain is not None:
+        G = _gain_array(source_gain, T.dtype, source, gain_start, n)
+        for q in range(n):
+            T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source, rmap, faces, gain=G[gain_start + q])
+        return T
     if faces is not None:
         for _ in range(n):
             T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source, rmap, faces)
@@ -282,9 +309,25 @@ def ftcs(problem: Problem, nsteps: int | None = None, dtype=np.float64, T0: np.n
     return wrap_frame(T, bc_x, bc_y)
 
 
+def _gain_array(source_gain, dtype, source, start: int, nsteps: int) -> np.ndarray:
+    """The schedule in the run's dtype, checked: 1-D, non-empty, finite, >= 0,
+    with a source, and long enough for nsteps steps from ``start``."""
+    if source is None:
+        raise ValueError("source_gain= scales a heat source: pass source=")
+    G = np.asarray(source_gain, dtype=dtype)
+    if G.ndim != 1 or G.size == 0:
+        raise ValueError("source_gain must be a non-empty 1-D array")
+    if not (np.isfinite(G).all() and (G >= 0).all()):
+        raise ValueError("source_gain entries must be finite and >= 0 (put the sign into the source)")
+    if start < 0 or start + nsteps > G.size:
+        raise ValueError(f"source_gain has {G.size} entries: steps {start}..{start + nsteps - 1} run past its end")
+    return G
+
+
 def probe_history(problem: Problem, nsteps: int, probes, dtype=np.float64, T0: np.ndarray | None = None,
                   arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
-                  source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None) -> np.ndarray:
+                  source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None,
+                  source_gain=None, gain_start: int = 0) -> np.ndarray:
     """The golden of the solver's probe points: the (nsteps, P) array whose row
     q holds the values :func:`ftcs_step` leaves at ``probes`` after step q + 1.
     ``probes``: P owned points (i, j) in frame-inclusive indices, 1 <= i, j <= n,
@@ -300,8 +343,10 @@ def probe_history(problem: Problem, nsteps: int, probes, dtype=np.float64, T0: n
     if len(p) and (p.min() < 1 or p[:, 0].max() > n or p[:, 1].max() > m):
         raise ValueError(f"probes must be owned points (1..{n}, 1..{m})")
     H = np.empty((nsteps, len(p)), dtype=T.dtype)
+    G = None if source_gain is None else _gain_array(source_gain, T.dtype, source, gain_start, nsteps)
     for q in range(nsteps):
-        T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source, rmap, faces)
+        T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source, rmap, faces,
+                      gain=None if G is None else G[gain_start + q])
         H[q] = T[p[:, 0], p[:, 1]]
     return H
 

@@ -202,6 +202,13 @@ _SIGS = {
     "heat2d_solver_source": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "heat2d_tb_src": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, _P, _I64, C.c_int, _P]),
     "heat2d_cpu_tb_src": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, C.c_int, _P]),
+    "heat2d_solver_set_source_gain": (C.c_int, [_P, _P, _I64, _I64]),
+    "heat2d_group_set_source_gain": (C.c_int, [_P, _P, _I64, _I64]),
+    "heat2d_solver_source_gain": (C.c_int, [_P, C.POINTER(_I64)]),
+    "heat2d_tb_gain": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, _P, _I64, C.c_int, _P, _P, _P]),
+    "heat2d_cpu_tb_gain": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, C.c_int, _P, _P, _P]),
+    "heat2d_probe_cone_gain": (C.c_int, [C.c_int, _P, _LP, C.c_int, C.c_double, C.c_int, _P, _P, _P, _I64, _P, _P,
+                                         C.c_int]),
     "heat2d_solver_set_rmap": (C.c_int, [_P, _P, _I64]),
     "heat2d_group_set_rmap": (C.c_int, [_P, _P, _I64]),
     "heat2d_solver_rmap": (C.c_int, [_P, C.POINTER(C.c_int32)]),

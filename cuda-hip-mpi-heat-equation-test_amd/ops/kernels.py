@@ -87,7 +87,8 @@ def init_field(field: torch.Tensor, layout: N.Layout, ic, xcoord: np.ndarray,
 def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: float,
             rows: Optional[tuple[int, int]] = None, tile_rows: int = 0, arith: str = "exact",
             bc_x: str = "dirichlet", bc_y: str = "dirichlet", source: Optional[torch.Tensor] = None,
-            rmap: Optional[torch.Tensor] = None, faces: Optional[tuple] = None) -> None:
+            rmap: Optional[torch.Tensor] = None, faces: Optional[tuple] = None,
+            gain: Optional[torch.Tensor] = None, gain_pos: int = 0) -> None:
     """dst[rows] = k FTCS steps of src (temporal-blocked kernel). The k ghost rows
     around ``rows`` must be valid in ``src``; Dirichlet rows/cols are kept.
     ``arith``: "exact" (reference rounding), "fma" (contracted update) or
@@ -117,7 +118,21 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
     form div(k grad u) in the field's layout, dtype and device
     (:func:`faces_field`); ``r`` is then not used. Dirichlet axes, arith
     "exact" / "fma" ("auto" is exact), no ``source`` and no ``rmap``; on the
-    device k is at most ``kMaxTBDiv`` (``HeatSolver.info()["faces"]["max_tb"]``)."""
+    device k is at most ``kMaxTBDiv`` (``HeatSolver.info()["faces"]["max_tb"]``).
+    ``gain`` (with ``source``): a 1-D tensor of per-step gains in the field's
+    dtype and device, finite and >= 0; level s of the pass adds
+    ``gain[gain_pos + s - 1] * source`` — the product rounded, then the add;
+    arith "fma": one fma (csrc/kernels/tb_impl.hpp ``tb_kernel_gain``). It must
+    hold at least ``gain_pos + k`` entries."""
+    if gain is not None:
+        if source is None:
+            raise RuntimeError("gain= scales a heat source: pass source=")
+        if gain.dim() != 1 or gain.dtype != src.dtype or gain.device != src.device or not gain.is_contiguous():
+            raise ValueError("gain must be a contiguous 1-D tensor of the field's dtype and device")
+        if gain_pos < 0 or gain_pos + k > gain.numel():
+            raise ValueError(f"gain has {gain.numel()} entries: levels {gain_pos}..{gain_pos + k - 1} run past its end")
+        if not bool((torch.isfinite(gain) & (gain >= 0)).all()):
+            raise ValueError("gain entries must be finite and >= 0 (put the sign into the source)")
     _check_field(src, layout)
     _check_field(dst, layout)
     if faces is not None:
@@ -176,6 +191,18 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
             N.call("heat2d_cpu_tb_var", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
                    C.byref(layout), rb, re, k, ar, C.c_void_p(rmap.data_ptr()))
         return
+    if source is not None and gain is not None:
+        pos = torch.tensor([int(gain_pos)], dtype=torch.int64, device=src.device)
+        if src.is_cuda:
+            N.call("heat2d_tb_gain", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                   C.byref(layout), rb, re, k, r, _stream(src), tile_rows, ar, C.c_void_p(source.data_ptr()),
+                   C.c_void_p(gain.data_ptr()), C.c_void_p(pos.data_ptr()))
+            torch.cuda.current_stream(src.device).synchronize()  # keep pos alive until done
+        else:
+            N.call("heat2d_cpu_tb_gain", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                   C.byref(layout), rb, re, k, r, ar, C.c_void_p(source.data_ptr()), C.c_void_p(gain.data_ptr()),
+                   C.c_void_p(pos.data_ptr()))
+        return
     if source is not None:
         if src.is_cuda:
             N.call("heat2d_tb_src", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
@@ -218,15 +245,26 @@ def probe_points(points, nrows_global: int, ncols: int) -> np.ndarray:
 
 def probe_cone(src: torch.Tensor, layout: N.Layout, k: int, r: float, points, arith: str = "exact",
                bc_x: str = "dirichlet", bc_y: str = "dirichlet", source: Optional[torch.Tensor] = None,
-               rmap: Optional[torch.Tensor] = None, faces: Optional[tuple] = None) -> torch.Tensor:
+               rmap: Optional[torch.Tensor] = None, faces: Optional[tuple] = None,
+               gain: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The probe-cone kernel alone (csrc/kernels/probe_cone.hip; CPU tensors:
     its twin): the values at ``points`` after each of the next k steps of
     ``src``, a (k, P) tensor of src's dtype and device — row s - 1 holds level
     s. ``points``: global frame-inclusive (i, j) whose rows this slab owns; the
     k ghost rows around them must be valid in ``src``. ``layout``, ``r``,
     ``arith`` ("exact" / "fma" / "jacobi"), ``bc_x`` / ``bc_y`` and the
-    coefficient buffers are :func:`tb_step`'s. Nothing is written but the
-    result."""
+    coefficient buffers are :func:`tb_step`'s. ``gain`` (with ``source``): the
+    k gains of the levels, level s scaled by ``gain[s - 1]`` (``probe_cone_gain``).
+    Nothing is written but the result."""
+    if gain is not None:
+        if source is None:
+            raise RuntimeError("gain= scales a heat source: pass source=")
+        if gain.dim() != 1 or gain.dtype != src.dtype or gain.device != src.device or not gain.is_contiguous():
+            raise ValueError("gain must be a contiguous 1-D tensor of the field's dtype and device")
+        if gain.numel() < k:
+            raise ValueError(f"gain has {gain.numel()} entries for {k} levels")
+        if not bool((torch.isfinite(gain) & (gain >= 0)).all()):
+            raise ValueError("gain entries must be finite and >= 0 (put the sign into the source)")
     _check_field(src, layout)
     pts = probe_points(points, int(layout.nrows_global), int(layout.ncols))
     loc = pts - np.array([1 + layout.row0, 1], dtype=np.int64)
@@ -255,6 +293,13 @@ def probe_cone(src: torch.Tensor, layout: N.Layout, k: int, r: float, points, ar
         return out
     dpts = torch.from_numpy(np.ascontiguousarray(loc)).to(src.device)
     ptr = [C.c_void_p(f.data_ptr()) if f is not None else None for f in coefs]
+    if gain is not None:
+        N.call("heat2d_probe_cone_gain", dtype_code(src), C.c_void_p(src.data_ptr()), C.byref(layout), int(k), float(r),
+               ar, ptr[0], C.c_void_p(gain.data_ptr()), C.c_void_p(dpts.data_ptr()), len(pts),
+               C.c_void_p(out.data_ptr()), _stream(src), int(src.is_cuda))
+        if src.is_cuda:
+            torch.cuda.current_stream(src.device).synchronize()  # keep dpts alive until done
+        return out
     N.call("heat2d_probe_cone", dtype_code(src), C.c_void_p(src.data_ptr()), C.byref(layout), int(k), float(r), ar,
            N.bc_bits(bc_x, bc_y), ptr[0], ptr[1], ptr[2], ptr[3], C.c_void_p(dpts.data_ptr()), len(pts),
            C.c_void_p(out.data_ptr()), _stream(src), int(src.is_cuda))

@@ -64,6 +64,11 @@ def build_parser():
                          "increment dt * f (converted to the run's dtype; a wrong shape fails), added at every step "
                          "as an operation of its own. Dirichlet axes, engine tb, arith exact / fma (auto picks one of "
                          "them). Checkpoints record its SHA-256; a restart needs the same file again")
+    ap.add_argument("--source-gain", default=None, metavar="FILE",
+                    help="with --source, a time-dependent source g(t) * f: per-step gains, a 1-D .npy or text with one "
+                         "number per line (# comments), finite and >= 0, indexed by the absolute step of the run; step "
+                         "q adds G[q] * source. A file shorter than ntime fails before the first step. Checkpoints "
+                         "record its SHA-256; a restart continues at G[step] and needs the same file again")
     ap.add_argument("--rmap", default=None, metavar="FILE.npy",
                     help="diffusivity map u_t = nu(x, y) lap(u) (non-divergence form): the frame-inclusive (n+2) x (n+2) "
                          "array of the per-point diffusion number nu(x, y) dt / dx^2 (converted to the run's dtype; a "
@@ -254,6 +259,13 @@ def run(argv=None) -> int:
         m = prob.n_owned + 2
         if source.shape != (m, m):
             raise SystemExit(f"heat2d: --source {a.source}: shape {source.shape}, the frame-inclusive grid is {(m, m)}")
+    source_gain = None
+    if a.source_gain:
+        if source is None:
+            raise SystemExit("heat2d: --source-gain scales a heat source: give --source too")
+        source_gain = load_source_gain(a.source_gain)
+        if len(source_gain) < nsteps:
+            raise SystemExit(f"heat2d: --source-gain {a.source_gain}: {len(source_gain)} entries, the run takes {nsteps} steps")
     rmap = None
     if a.rmap:
         import numpy as np
@@ -332,7 +344,7 @@ def run(argv=None) -> int:
         return HeatSolver(prob, dtype=a.dtype, backend=backend, tb=a.tb, overlap=not a.no_overlap,
                           copy_swap=a.copy_swap, managed=a.managed or var.managed, graph=a.graph, transport=tr,
                           device=local if backend == "hip" else None, engine=engine, arith=arith,
-                          edge_shift=edge_shift, source=source, rmap=rmap, faces=faces, **bc)
+                          edge_shift=edge_shift, source=source, rmap=rmap, faces=faces, source_gain=source_gain, **bc)
 
     tr, s, kind, fallback = _make_solver(kinds, make_transport, make_solver, world)
     if fallback and root and not a.quiet:
@@ -350,6 +362,9 @@ def run(argv=None) -> int:
         start_step = int(meta["step"])
         if root and not a.quiet:
             print(f" restarted from {a.restart} at step {start_step}")
+
+    if source_gain is not None and start_step:  # the schedule is indexed by the absolute step
+        s.set_source_gain(source_gain, start=start_step)
 
     if probes is not None:  # (the history is not checkpointed: a restarted run records from its restart step)
         s.set_probes(probes, max(1, nsteps - start_step))
@@ -445,6 +460,24 @@ def run(argv=None) -> int:
         import torch.distributed as dist
         dist.destroy_process_group()
     return 0
+
+
+def load_source_gain(path: str):
+    """--source-gain FILE: a 1-D .npy, or text with one number per line and #
+    comments; the 1-D float64 array (the solver converts and checks it)."""
+    import numpy as np
+    try:
+        with open(path, "rb") as f:
+            npy = f.read(6) == b"\x93NUMPY"
+        g = np.load(path, allow_pickle=False) if npy else np.loadtxt(path, comments="#", ndmin=1)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"heat2d: --source-gain {path}: {e}")
+    g = np.asarray(g, dtype=np.float64)
+    if g.ndim != 1 or g.size == 0:
+        raise SystemExit(f"heat2d: --source-gain {path}: a non-empty 1-D array of gains, got shape {g.shape}")
+    if not np.isfinite(g).all() or (g < 0).any():
+        raise SystemExit(f"heat2d: --source-gain {path}: entries must be finite and >= 0 (put the sign into the source)")
+    return g
 
 
 def load_probes(path):

@@ -127,6 +127,10 @@ def save(solver, directory: str, step: Optional[int] = None, extra: Optional[dic
         # ... and the face coefficients of the conservative form (HeatSolver.faces_sha256)
         if getattr(solver, "faces_sha256", None) is not None:
             meta["faces_sha256"] = solver.faces_sha256
+        # ... and the source's gain schedule (HeatSolver.source_gain_sha256: the converted bytes); a
+        # restart continues at G[step] and must be given the same schedule
+        if getattr(solver, "source_gain_sha256", None) is not None:
+            meta["source_gain_sha256"] = solver.source_gain_sha256
         meta.update(extra or {})
         _write_atomic(os.path.join(sd, "meta.json"), json.dumps(meta, indent=1))
         _write_atomic(os.path.join(directory, "latest"), os.path.basename(sd) + "\n")  # the commit point
@@ -189,6 +193,14 @@ def load(solver, directory: str) -> dict:
             raise ValueError("the checkpoint was written with face coefficients: give the restart the same faces "
                              f"(sha256 {saved})")
         raise ValueError(f"the restart's face coefficients differ from the checkpoint's (sha256 {have} != {saved})")
+    have, saved = getattr(solver, "source_gain_sha256", None), meta.get("source_gain_sha256")  # (absent: none)
+    if saved != have:
+        if saved is None:
+            raise ValueError("the checkpoint was written without a source gain schedule, this run has one")
+        if have is None:
+            raise ValueError("the checkpoint was written with a source gain schedule: give the restart the same "
+                             f"source_gain (sha256 {saved})")
+        raise ValueError(f"the restart's source gain schedule differs from the checkpoint's (sha256 {have} != {saved})")
     want = "fp64" if solver.np_dtype == np.float64 else "fp32"
     if meta["dtype"] != want:
         raise ValueError(f"checkpoint dtype {meta['dtype']} != solver dtype {want}")

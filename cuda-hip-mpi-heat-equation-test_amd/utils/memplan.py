@@ -51,15 +51,27 @@ def probe_bytes(probes: int, probe_steps: int, dtype: str = "fp32") -> int:
     return int(probes) * int(probe_steps) * (8 if DTYPES[dtype] else 4) + 16 * int(probes) + 8
 
 
+MAX_TB_SRC = 16  # common.hpp kMaxTBSrc: the padding past a gain schedule's end
+
+
+def gain_bytes(source_gain: int, dtype: str = "fp32") -> int:
+    """Device bytes of a source gain schedule of that many entries
+    (HeatSolver source_gain=): the padded array and the two position words."""
+    if source_gain <= 0:
+        return 0
+    return (int(source_gain) + MAX_TB_SRC) * (8 if DTYPES[dtype] else 4) + 16
+
+
 def footprint(n: int, nranks: int = 1, dtype: str = "fp32", rank: int = 0, backend: str = "hip",
               source: bool = False, rmap: bool = False, faces: bool = False, probes: int = 0,
-              probe_steps: int = 0) -> dict:
+              probe_steps: int = 0, source_gain: int = 0) -> dict:
     """Device bytes of one rank's solver for an n x n grid on nranks ranks:
     {"field_bytes", "work_bytes", "total_bytes"} (the constructor's allocations).
     source: a solver with a heat source (a third buffer in the field's layout);
     rmap: one with a diffusivity map (one more); faces: one with per-face
     diffusion numbers (two more); probes, probe_steps: one with that many probe
-    points and room for that many steps (probe_bytes, counted as work bytes)."""
+    points and room for that many steps (probe_bytes, counted as work bytes);
+    source_gain: one with a gain schedule of that many entries (gain_bytes, work bytes)."""
     cfg = N.Config()
     cfg.n_rows = cfg.n_cols = int(n)
     cfg.dtype = DTYPES[dtype]
@@ -69,13 +81,13 @@ def footprint(n: int, nranks: int = 1, dtype: str = "fp32", rank: int = 0, backe
     cfg.faces = int(bool(faces))
     out = (C.c_int64 * 3)()
     N.call("heat2d_solver_footprint", C.byref(cfg), int(rank), int(nranks), out)
-    pb = probe_bytes(probes, probe_steps, dtype)
+    pb = probe_bytes(probes, probe_steps, dtype) + gain_bytes(source_gain, dtype)
     return {"field_bytes": out[0], "work_bytes": out[1] + pb, "total_bytes": out[2] + pb}
 
 
 def plan_max_grid(dtype: str = "fp32", nranks: int = 1, free_bytes: Optional[int] = None, device: int = 0,
                   reserve: Optional[int] = None, source: bool = False, rmap: bool = False,
-                  faces: bool = False, probes: int = 0, probe_steps: int = 0) -> dict:
+                  faces: bool = False, probes: int = 0, probe_steps: int = 0, source_gain: int = 0) -> dict:
     """The largest n x n grid of ``dtype`` whose largest slab on ``nranks``
     ranks fits ``free_bytes`` (default: this device's hipMemGetInfo free
     memory) minus ``reserve`` (default: reserve_bytes(free)). Returns {"n",
@@ -84,10 +96,10 @@ def plan_max_grid(dtype: str = "fp32", nranks: int = 1, free_bytes: Optional[int
     free = mem_info(device)[0] if free_bytes is None else int(free_bytes)
     res = reserve_bytes(free) if reserve is None else int(reserve)
     n = C.c_int64()
-    pb = probe_bytes(probes, probe_steps, dtype)  # (does not grow with n: off the budget)
+    pb = probe_bytes(probes, probe_steps, dtype) + gain_bytes(source_gain, dtype)  # (does not grow with n: off the budget)
     N.call("heat2d_plan_max_grid_faces", DTYPES[dtype], int(nranks), int(free - res - pb), int(bool(source)),
            int(bool(rmap)), int(bool(faces)), C.byref(n))
     fp = footprint(n.value, nranks, dtype, source=source, rmap=rmap, faces=faces, probes=probes,
-                   probe_steps=probe_steps)["total_bytes"]
+                   probe_steps=probe_steps, source_gain=source_gain)["total_bytes"]
     return {"n": int(n.value), "nranks": int(nranks), "dtype": dtype, "free_bytes": free, "reserve_bytes": res,
             "footprint_bytes": fp, "fraction_of_free": fp / free if free > 0 else 0.0}
