@@ -205,6 +205,25 @@ int heat2d_tb_bc(int dtype, const void* src, void* dst, const heat2d_layout* L, 
   });
 }
 
+int heat2d_tb_rob(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                  double r, void* stream, int64_t tile_rows, int arith, int bc, const double* robin) {
+  return guarded([&] {
+    HEAT2D_REQUIRE(robin != nullptr, "heat2d_tb_rob needs the walls' pairs");
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, arith, bc, nullptr,
+                    nullptr, nullptr, nullptr, {}, robin);
+  });
+}
+
+int heat2d_cpu_tb_rob(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                      double r, int arith, int bc, const double* robin) {
+  return guarded([&] {
+    HEAT2D_REQUIRE(robin != nullptr, "heat2d_cpu_tb_rob needs the walls' pairs");
+    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, arith, bc, nullptr, nullptr, nullptr, nullptr, {}, robin);
+  });
+}
+
+int heat2d_max_tb_rob(void) { return kMaxTBRob; }
+
 int heat2d_tb_src(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                   double r, void* stream, int64_t tile_rows, int arith, const void* source) {
   return guarded([&] {
@@ -599,6 +618,24 @@ int heat2d_probe_cone(int dtype, const void* src, const heat2d_layout* L, int k,
   });
 }
 
+int heat2d_probe_cone_rob(int dtype, const void* src, const heat2d_layout* L, int k, double r, int arith, int bc,
+                          const double* robin, const int64_t* pts, int64_t P, void* out, void* stream, int on_device) {
+  return guarded([&] {
+    HEAT2D_REQUIRE(robin != nullptr, "heat2d_probe_cone_rob needs the walls' pairs");
+    kern::ProbeArgs a{};
+    a.src = src;
+    a.pts = pts;
+    a.hist = out;
+    a.capacity = k;
+    a.P = P;
+    a.r = r;
+    a.k = k;
+    kern::probe_bounds(a, to_layout(L), bc, robin);
+    if (on_device) kern::launch_probe_cone((DType)dtype, a, arith, as_stream(stream));
+    else cpu::probe_cone((DType)dtype, a, arith);
+  });
+}
+
 int heat2d_solver_download_region(void* s, int64_t r0, int64_t r1, int64_t c0, int64_t c1, void* host, int64_t ld) {
   return guarded([&] { static_cast<Solver*>(s)->download_region(r0, r1, c0, c1, host, ld); });
 }
@@ -677,6 +714,15 @@ int heat2d_solver_info(void* s, int32_t* tb, int64_t* band, int64_t* steps, void
 
 int heat2d_solver_arith(void* s, int32_t* out) {
   return guarded([&] { *out = static_cast<Solver*>(s)->config().arith; });
+}
+
+int heat2d_solver_robin(void* s, double* out8, int32_t* max_tb) {
+  return guarded([&] {
+    const SolverConfig& c = static_cast<Solver*>(s)->config();
+    const bool rob = c.bc_x == kBcRobinKind || c.bc_y == kBcRobinKind;
+    for (int i = 0; i < 8; ++i) out8[i] = rob ? c.robin[i] : ((i & 1) ? -0.0 : 1.0);
+    *max_tb = rob ? kMaxTBRob : 0;
+  });
 }
 
 int heat2d_solver_bc(void* s, int32_t* bc_x, int32_t* bc_y) {

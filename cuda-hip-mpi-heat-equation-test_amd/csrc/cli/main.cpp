@@ -79,9 +79,14 @@ struct Args {
   bool share_gpu = false;          // --share-gpu: every rank on device 0 (peer transport; tests / rehearsals)
   int autotune = -1;               // --autotune auto|on|off (SolverConfig::autotune)
   int edge_shift = 0;              // --edge-shift N: rows each edge slab gives the middle ones (>= 3 ranks)
-  // --bc-x / --bc-y dirichlet|periodic|insulated (SolverConfig::bc_x / bc_y; x = rows, decomposed over ranks).
+  // --bc-x / --bc-y dirichlet|periodic|insulated|robin (SolverConfig::bc_x / bc_y; x = rows, decomposed over ranks).
   // Empty: not given — dirichlet, or a restart's checkpointed setting
   std::string bc_x, bc_y;
+  // --robin-x-lo / --robin-x-hi / --robin-y-lo / --robin-y-hi A,B: the pair (a, b) of a Robin wall, ghost =
+  // a * C + b (SolverConfig::robin, sides in that order); needed exactly for the sides of the robin axes,
+  // or taken from a restart's checkpoint
+  bool robin_set[4] = {false, false, false, false};
+  double robin[8] = {1.0, -0.0, 1.0, -0.0, 1.0, -0.0, 1.0, -0.0};
   // --source FILE.npy: heat source, the frame-inclusive (n+2) x (n+2) per-step increment dt * f
   // (SolverConfig::source; converted to the run's dtype, a wrong shape fails)
   std::string source;
@@ -101,6 +106,9 @@ struct Args {
   std::string probes_out = "probes.npy";
 };
 
+// the sides of the Robin pairs, in SolverConfig::robin's order, as the flags name them
+const char* const kRobinSides[4] = {"x-lo", "x-hi", "y-lo", "y-hi"};
+
 void usage() {
   std::printf(
       "usage: heat2d [input.dat] [--variant mpi|mpicuda|serial|cuda] [--gpus N | --cpu] [--dtype fp64|fp32]\n"
@@ -110,7 +118,8 @@ void usage() {
       "              [--time-transfers]\n"
       "              [--checkpoint DIR [--checkpoint-every N]] [--restart DIR]\n"
       "              [--transport auto|rccl|peer] [--share-gpu] [--autotune auto|on|off] [--edge-shift N]\n"
-      "              [--bc-x dirichlet|periodic|insulated] [--bc-y dirichlet|periodic|insulated]\n"
+      "              [--bc-x dirichlet|periodic|insulated|robin] [--bc-y dirichlet|periodic|insulated|robin]\n"
+      "              [--robin-x-lo A,B] [--robin-x-hi A,B] [--robin-y-lo A,B] [--robin-y-hi A,B]\n"
       "              [--source FILE.npy] [--source-gain FILE] [--rmap FILE.npy] [--faces FILE.npy]\n"
       "              [--probes FILE [--probes-out FILE.npy]]\n");
 }
@@ -165,11 +174,34 @@ Args parse_args(int argc, char** argv) {
     else if (s == "--probes-out") a.probes_out = need("--probes-out");
     else if (s == "--bc-x" || s == "--bc-y") {
       const std::string v = need(s.c_str());
-      if (v != "dirichlet" && v != "periodic" && v != "insulated") {
-        std::fprintf(stderr, "%s must be dirichlet, periodic or insulated\n", s.c_str());
+      if (v != "dirichlet" && v != "periodic" && v != "insulated" && v != "robin") {
+        std::fprintf(stderr, "%s must be dirichlet, periodic, insulated or robin\n", s.c_str());
         std::exit(2);
       }
       (s == "--bc-x" ? a.bc_x : a.bc_y) = v;
+    }
+    else if (s.compare(0, 8, "--robin-") == 0) {  // --robin-x-lo A,B (or --robin-x-lo=A,B)
+      const size_t eq = s.find('=');
+      const std::string flag = s.substr(0, eq);
+      int side = -1;
+      for (int k = 0; k < 4; ++k)
+        if (flag == std::string("--robin-") + kRobinSides[k]) side = k;
+      if (side < 0) {
+        std::fprintf(stderr, "unknown flag %s (--robin-x-lo, --robin-x-hi, --robin-y-lo, --robin-y-hi)\n", flag.c_str());
+        std::exit(2);
+      }
+      const std::string v = eq == std::string::npos ? need(flag.c_str()) : s.substr(eq + 1);
+      char* e1 = nullptr;
+      char* e2 = nullptr;
+      const double av = std::strtod(v.c_str(), &e1);
+      const double bv = (e1 && *e1 == ',') ? std::strtod(e1 + 1, &e2) : 0.0;
+      if (!e1 || e1 == v.c_str() || *e1 != ',' || !e2 || e2 == e1 + 1 || *e2 != '\0') {
+        std::fprintf(stderr, "%s expects A,B (two numbers), got %s\n", flag.c_str(), v.c_str());
+        std::exit(2);
+      }
+      a.robin_set[side] = true;
+      a.robin[2 * side] = av;
+      a.robin[2 * side + 1] = bv;
     }
     else if (s == "--edge-shift") {
       a.edge_shift = std::atoi(need("--edge-shift").c_str());
@@ -335,9 +367,16 @@ void save_checkpoint(Shared& sh, Solver& s, Transport& tr, int rank, int64_t ste
     m.dom_len = sh.in.dom_len;
     m.r = sh.prob.r;
     m.edge_shift = s.config().edge_shift;  // (0 with periodic x: no edge slabs)
-    const char* const bc_names[3] = {"dirichlet", "periodic", "insulated"};
+    const char* const bc_names[4] = {"dirichlet", "periodic", "insulated", "robin"};
     m.bc_x = bc_names[s.config().bc_x];
     m.bc_y = bc_names[s.config().bc_y];
+    // the Robin walls' pairs as the solver converted them (exactly: hex floats), for the Robin axes' sides only
+    for (int k = 0; k < 4; ++k)
+      if ((k < 2 ? s.config().bc_x : s.config().bc_y) == kBcRobinKind) {
+        m.robin_sides |= 1 << k;
+        m.robin[2 * k] = s.config().robin[2 * k];
+        m.robin[2 * k + 1] = s.config().robin[2 * k + 1];
+      }
     m.source_sha256 = sh.source_sha256;  // (empty: no source, written as null)
     m.source_gain_sha256 = sh.gain_sha256;  // (empty: no schedule, the key is not written)
     m.rmap_sha256 = sh.rmap_sha256;      // (empty: no map, the key is not written)
@@ -463,6 +502,12 @@ void run_rank(Shared& sh, int rank) {
     // boundary conditions: the flags, or a restart's checkpointed settings (a
     // flag that says otherwise fails: the resumed run would not be the saved one)
     std::string bc_x = a.bc_x.empty() ? "dirichlet" : a.bc_x, bc_y = a.bc_y.empty() ? "dirichlet" : a.bc_y;
+    bool robin_set[4];
+    for (int k = 0; k < 4; ++k) {
+      robin_set[k] = a.robin_set[k];
+      cfg.robin[2 * k] = a.robin[2 * k];
+      cfg.robin[2 * k + 1] = a.robin[2 * k + 1];
+    }
     if (!a.restart.empty()) {
       const ckpt::Meta m0 = ckpt::read_meta(a.restart);
       HEAT2D_REQUIRE(a.bc_x.empty() || a.bc_x == m0.bc_x,
@@ -471,6 +516,16 @@ void run_rank(Shared& sh, int rank) {
                      "--bc-y " + a.bc_y + " conflicts with the checkpoint's bc_y = " + m0.bc_y);
       bc_x = m0.bc_x;
       bc_y = m0.bc_y;
+      // the Robin pairs come from the checkpoint; a flag must name a side it has, with the same converted values
+      for (int k = 0; k < 4; ++k) {
+        const double fa = cfg.dtype == 0 ? (double)(float)a.robin[2 * k] : a.robin[2 * k];
+        const double fb = cfg.dtype == 0 ? (double)(float)a.robin[2 * k + 1] : a.robin[2 * k + 1];
+        HEAT2D_REQUIRE(!a.robin_set[k] || ((m0.robin_sides >> k & 1) && fa == m0.robin[2 * k] && fb == m0.robin[2 * k + 1]),
+                       std::string("--robin-") + kRobinSides[k] + " conflicts with the checkpoint's Robin pairs");
+        robin_set[k] = (m0.robin_sides >> k & 1) != 0;
+        cfg.robin[2 * k] = m0.robin[2 * k];
+        cfg.robin[2 * k + 1] = m0.robin[2 * k + 1];
+      }
       // a restart must be given the source the checkpointed run had (it is not saved), and no other
       if (m0.source_sha256 != sh.source_sha256) {
         HEAT2D_REQUIRE(!m0.source_sha256.empty(), "the checkpoint was written without a heat source, this run has one (--source)");
@@ -507,9 +562,25 @@ void run_rank(Shared& sh, int rank) {
                                      " != " + mf.faces_sha256 + ")");
       }
     }
-    auto bc_code = [](const std::string& v) { return v == "periodic" ? kBcPeriodic : v == "insulated" ? kBcInsulated : kBcDirichlet; };
+    auto bc_code = [](const std::string& v) {
+      return v == "periodic" ? kBcPeriodic : v == "insulated" ? kBcInsulated : v == "robin" ? kBcRobinKind : kBcDirichlet;
+    };
     cfg.bc_x = bc_code(bc_x);
     cfg.bc_y = bc_code(bc_y);
+    // Robin walls: a pair exactly for every side of a robin axis (a missing or surplus side fails here,
+    // before the first step); |a| > 1 draws the stability warning
+    const bool robin_any = cfg.bc_x == kBcRobinKind || cfg.bc_y == kBcRobinKind;
+    for (int k = 0; k < 4; ++k) {
+      const bool want = (k < 2 ? cfg.bc_x : cfg.bc_y) == kBcRobinKind;
+      HEAT2D_REQUIRE(!want || robin_set[k], std::string("--robin-") + kRobinSides[k] + " A,B is missing: every side of a "
+                                                "robin axis needs its pair");
+      HEAT2D_REQUIRE(want || !robin_set[k], std::string("--robin-") + kRobinSides[k] + " names no side of a robin axis");
+      HEAT2D_REQUIRE(!want || (std::isfinite(cfg.robin[2 * k]) && std::isfinite(cfg.robin[2 * k + 1])),
+                     std::string("--robin-") + kRobinSides[k] + ": a and b must be finite");
+      if (want && std::fabs(cfg.robin[2 * k]) > 1.0 && root && !a.quiet)
+        std::fprintf(stderr, "warning: Robin |a| > 1 at %s (a = %.6g): the wall amplifies, FTCS may be unstable\n",
+                     kRobinSides[k], cfg.robin[2 * k]);
+    }
     if (a.engine != "tb" && a.engine != "jit") fail(__FILE__, __LINE__, "--engine must be tb or jit");
     cfg.engine = a.engine == "jit" ? 1 : 0;  // jit: hipRTC kernel rendered for this slab (python/cuda/cuda.py)
     if (a.arith != "exact" && a.arith != "fma" && a.arith != "jacobi" && a.arith != "fast" && a.arith != "auto")
@@ -521,7 +592,8 @@ void run_rank(Shared& sh, int rank) {
       // the whole run — the IC in [m, 2m] (the reference's: 1 and 2) keeps
       // every sum - 4c exact; a restart's data is not known to be
       // (with a source auto stays with the solver: fma or exact, never jacobi)
-      if (sh.prob.r == 0.25 && ic_sterbenz_safe(sh.prob.ic) && a.restart.empty() && cfg.engine == 0 && !cfg.source && !cfg.rmap && !cfg.faces) {
+      if (sh.prob.r == 0.25 && ic_sterbenz_safe(sh.prob.ic) && a.restart.empty() && cfg.engine == 0 && !cfg.source && !cfg.rmap && !cfg.faces &&
+          !robin_any) {  // (with Robin walls auto stays with the solver too: fma or exact, never jacobi)
         cfg.arith = 2;
         arith_used = "jacobi (auto)";
       } else {

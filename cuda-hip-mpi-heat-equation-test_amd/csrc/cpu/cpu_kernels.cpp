@@ -154,6 +154,25 @@ void ins_cols_impl(T* f, const SlabLayout& L, int64_t r0, int64_t r1) {
   }
 }
 
+// The ghost value beyond a Robin wall (the device march's tb_impl.hpp rob_ghost): a * c + b, the
+// product rounded, then the add (this file is built with -ffp-contract=off); arith 1: one fma.
+template <typename T>
+inline T rob_ghost(T a, T c, T b, int arith) {
+  return arith == 1 ? kern::probe_fma(a, c, b) : a * c + b;
+}
+template <typename T>
+void rob_cols_impl(T* f, const SlabLayout& L, int64_t r0, int64_t r1, const double* p, int arith) {
+  for (int64_t i = r0; i < r1; ++i) {
+    T* row = f + L.offset(i, 0);
+    row[-1] = rob_ghost((T)p[0], row[0], (T)p[1], arith);
+    row[L.ncols] = rob_ghost((T)p[2], row[L.ncols - 1], (T)p[3], arith);
+  }
+}
+template <typename T>
+void rob_row_impl(T* dst, const T* src, int64_t n, T a, T b, int arith) {
+  for (int64_t j = 0; j < n; ++j) dst[j] = rob_ghost(a, src[j], b, arith);
+}
+
 // bc (kernels.hpp kBcPeriodicX / kBcPeriodicY), as the device march: periodic
 // x pins no row, periodic y pins no column — level s is computed over the
 // ghost columns [-(k - s), ncols + (k - s)) too, from level-0 wrap images k
@@ -163,6 +182,11 @@ void ins_cols_impl(T* f, const SlabLayout& L, int64_t r0, int64_t r1) {
 // device march's substitution, tb_impl.hpp March INS) — here by giving the
 // frame entry beside it that value before each level reads it; the frame
 // images of the rows written are refreshed.
+// kBcRobinX / kBcRobinY (rob: the walls' pairs, kernels.hpp): the same with
+// the ghost value a * C + b in place of the point's own value (the device
+// march's tb_impl.hpp March ROB), formed from each level's own C; an insulated
+// axis beside a Robin one is the pair (1, -0.0). The frame of the rows written
+// gets the ghost values, the wall rows first, then the columns over them.
 // q (a heat source in the field's layout, Dirichlet axes only): every level adds
 // its row of q to the updated owned points, T' = update + q, as an add of its
 // own (the device march's tb_impl.hpp March SRC); pinned points are copied.
@@ -178,11 +202,23 @@ void ins_cols_impl(T* f, const SlabLayout& L, int64_t r0, int64_t r1) {
 template <typename T>
 void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re, int k, T r, int arith, int bc,
              const T* q = nullptr, const T* rm = nullptr, const T* fx = nullptr, const T* fy = nullptr,
-             const T* gn = nullptr) {
+             const T* gn = nullptr, const double* rob = nullptr) {
   const SlabLayout L = kern::bc_layout(L0, bc & kern::kBcPeriodicX);  // (the columns: free_cols below)
   const bool free_cols = (bc & kern::kBcPeriodicY) != 0;
-  const bool ins_x = (bc & kern::kBcInsulatedX) != 0, ins_y = (bc & kern::kBcInsulatedY) != 0;
-  HEAT2D_REQUIRE(!(ins_x && (bc & kern::kBcPeriodicX)) && !(ins_y && free_cols), "an axis is periodic or insulated, not both");
+  const bool robin = (bc & kern::kBcRobin) != 0;
+  // (with a Robin axis the insulated walls run as Robin ones with (1, -0.0): wall_x / wall_y below)
+  const bool ins_x = !robin && (bc & kern::kBcInsulatedX), ins_y = !robin && (bc & kern::kBcInsulatedY);
+  const bool wall_x = robin && (bc & kern::kBcWallX), wall_y = robin && (bc & kern::kBcWallY);
+  HEAT2D_REQUIRE(!((bc & kern::kBcWallX) && (bc & kern::kBcPeriodicX)) && !((bc & kern::kBcWallY) && free_cols),
+                 "an axis is periodic or insulated, not both");
+  HEAT2D_REQUIRE(!((bc & kern::kBcRobinX) && (bc & kern::kBcInsulatedX)) && !((bc & kern::kBcRobinY) && (bc & kern::kBcInsulatedY)),
+                 "an axis is Robin or insulated, not both");
+  double px[4] = {1.0, -0.0, 1.0, -0.0}, py[4] = {1.0, -0.0, 1.0, -0.0};
+  if (robin) {
+    HEAT2D_REQUIRE(rob && (arith == 0 || arith == 1), "Robin walls need their pairs and arith 0 (exact) or 1 (fma)");
+    kern::wall_pairs(bc, true, rob, px);
+    kern::wall_pairs(bc, false, rob, py);
+  }
   if (free_cols) HEAT2D_REQUIRE(L.ncols >= kern::kWrapCols, "periodic y needs at least kWrapCols (24) owned columns");
   const int64_t R = re - rb + 2 * k;  // level-0 rows [rb-k, re+k)
   const int64_t P = L.pitch;
@@ -207,6 +243,19 @@ void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re,
       for (const int64_t w : {fixed_lo - 1, fixed_hi}) {
         const int64_t li = w - (rb - k), from = w < fixed_lo ? li + 1 : li - 1;
         if (li >= s - 1 && li < R - s + 1 && from >= 0 && from < R) std::memcpy(a + li * P, a + from * P, sizeof(T) * (size_t)P);
+      }
+    // Robin walls: the ghost values of level s - 1, from its own values (no owned point reads a corner entry)
+    if (wall_y)
+      for (int64_t li = s - 1; li < R - s + 1; ++li) {
+        a[li * P + c - 1] = rob_ghost((T)py[0], a[li * P + c], (T)py[1], arith);
+        a[li * P + c + L.ncols] = rob_ghost((T)py[2], a[li * P + c + L.ncols - 1], (T)py[3], arith);
+      }
+    if (wall_x)  // (whole padded rows: periodic y's ghost columns too)
+      for (const int64_t w : {fixed_lo - 1, fixed_hi}) {
+        const bool lo = w < fixed_lo;
+        const int64_t li = w - (rb - k), from = lo ? li + 1 : li - 1;
+        if (li >= s - 1 && li < R - s + 1 && from >= 0 && from < R)
+          rob_row_impl(a + li * P, a + from * P, P, (T)px[lo ? 0 : 2], (T)px[lo ? 1 : 3], arith);
       }
     parallel_rows(s, R - s, [&](int64_t lb, int64_t le) {
       for (int64_t li = lb; li < le; ++li) {
@@ -253,6 +302,13 @@ void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re,
     std::memcpy(dst + L.offset(i, 0), a + (i - rb + k) * P + c, sizeof(T) * (size_t)L.ncols);
   if (free_cols) wrap_cols_impl(dst, L, rb, re);
   if (ins_y) ins_cols_impl(dst, L, rb, re);
+  if (robin) {  // the golden's order: the wall rows (whole padded rows), then the columns over them
+    const bool tlo = wall_x && L.row0 == 0 && rb <= 0 && re > 0;
+    const bool thi = wall_x && L.row0 + L.nrows == L.nrows_global && rb < L.nrows && re >= L.nrows;
+    if (tlo) rob_row_impl(dst + L.offset(-1, -L.cpad), dst + L.offset(0, -L.cpad), P, (T)px[0], (T)px[1], arith);
+    if (thi) rob_row_impl(dst + L.offset(L.nrows, -L.cpad), dst + L.offset(L.nrows - 1, -L.cpad), P, (T)px[2], (T)px[3], arith);
+    if (wall_y) rob_cols_impl(dst, L, rb - (tlo ? 1 : 0), re + (thi ? 1 : 0), py, arith);
+  }
   if (ins_x) {
     const size_t rowb = sizeof(T) * (size_t)P;
     if (L.row0 == 0 && rb <= 0 && re > 0) std::memcpy(dst + L.offset(-1, -L.cpad), dst + L.offset(0, -L.cpad), rowb);
@@ -338,7 +394,7 @@ int num_threads() {
 
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end,
         int k, double r, int arith, int bc, const void* source, const void* rmap, const void* rx, const void* ry,
-        kern::GainRef gain) {
+        kern::GainRef gain, const double* robin) {
   HEAT2D_REQUIRE(k >= 1 && k <= L.halo, "k out of range");
   HEAT2D_REQUIRE(arith >= 0 && arith <= 3, "arith must be 0, 1, 2 or 3");
   HEAT2D_REQUIRE(arith != 2 || r == 0.25, "arith 2 (jacobi) needs r == 1/4 exactly");
@@ -347,6 +403,8 @@ void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_b
   // contracted form (arith 1), within the same stated bound of exact
   HEAT2D_REQUIRE(arith != 3 || !(bc & (kern::kBcInsulatedX | kern::kBcInsulatedY)),
                  "insulated boundaries have no arith 3 (fast) kernels");
+  HEAT2D_REQUIRE(!(bc & kern::kBcRobin) || (robin && (arith == 0 || arith == 1)),
+                 "Robin walls need their pairs and arith 0 (exact) or 1 (fma)");
   HEAT2D_REQUIRE(!source || ((arith == 0 || arith == 1) && bc == 0),
                  "a heat source needs arith 0 (exact) or 1 (fma) and Dirichlet boundaries on both axes");
   HEAT2D_REQUIRE(!rmap || ((arith == 0 || arith == 1) && bc == 0 && !source),
@@ -362,11 +420,11 @@ void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_b
   if (dt == DType::F32)
     tb_impl<float>(static_cast<const float*>(src), static_cast<float*>(dst), L, row_begin, row_end, k, (float)r, arith, bc,
                    static_cast<const float*>(source), static_cast<const float*>(rmap), static_cast<const float*>(rx),
-                   static_cast<const float*>(ry), gain.g ? static_cast<const float*>(gain.g) + gpos : nullptr);
+                   static_cast<const float*>(ry), gain.g ? static_cast<const float*>(gain.g) + gpos : nullptr, robin);
   else
     tb_impl<double>(static_cast<const double*>(src), static_cast<double*>(dst), L, row_begin, row_end, k, r, arith, bc,
                     static_cast<const double*>(source), static_cast<const double*>(rmap), static_cast<const double*>(rx),
-                    static_cast<const double*>(ry), gain.g ? static_cast<const double*>(gain.g) + gpos : nullptr);
+                    static_cast<const double*>(ry), gain.g ? static_cast<const double*>(gain.g) + gpos : nullptr, robin);
 }
 
 void init(DType dt, void* field, const SlabLayout& L, const kern::IcParams& ic, const double* xc,
@@ -397,6 +455,30 @@ void ins_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1
   HEAT2D_REQUIRE(r0 >= -L.halo && r1 <= L.nrows + L.halo, "ins_cols: rows outside the allocation");
   if (dt == DType::F32) ins_cols_impl<float>(static_cast<float*>(field), L, r0, r1);
   else ins_cols_impl<double>(static_cast<double*>(field), L, r0, r1);
+}
+
+void rob_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1, const double* pairs, int arith) {
+  if (r1 <= r0) return;
+  HEAT2D_REQUIRE(pairs && (arith == 0 || arith == 1), "rob_cols: the walls' pairs and arith 0 (exact) or 1 (fma)");
+  HEAT2D_REQUIRE(r0 >= -L.halo && r1 <= L.nrows + L.halo, "rob_cols: rows outside the allocation");
+  if (dt == DType::F32) rob_cols_impl<float>(static_cast<float*>(field), L, r0, r1, pairs, arith);
+  else rob_cols_impl<double>(static_cast<double*>(field), L, r0, r1, pairs, arith);
+}
+
+void rob_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool hi, const double* pairs, int arith) {
+  HEAT2D_REQUIRE(pairs && (arith == 0 || arith == 1), "rob_rows: the walls' pairs and arith 0 (exact) or 1 (fma)");
+  HEAT2D_REQUIRE(L.halo >= 1 && L.nrows >= 1, "rob_rows: no room for the frame rows");
+  auto one = [&](int64_t to, int64_t from, double a, double b) {
+    if (dt == DType::F32) {
+      float* f = static_cast<float*>(field);
+      rob_row_impl<float>(f + L.offset(to, -L.cpad), f + L.offset(from, -L.cpad), L.pitch, (float)a, (float)b, arith);
+    } else {
+      double* f = static_cast<double*>(field);
+      rob_row_impl<double>(f + L.offset(to, -L.cpad), f + L.offset(from, -L.cpad), L.pitch, a, b, arith);
+    }
+  };
+  if (lo && L.row0 == 0) one(-1, 0, pairs[0], pairs[1]);
+  if (hi && L.row0 + L.nrows == L.nrows_global) one(L.nrows, L.nrows - 1, pairs[2], pairs[3]);
 }
 
 void ins_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool hi) {
@@ -435,7 +517,7 @@ void unpack_rows(DType dt, void* field, const SlabLayout& L, int64_t row, int64_
 // Twin of kernels/probe_cone.hip: the same levels over the same two planes,
 // one probe after the other, through the shared probe_point (heat2d/probe.hpp).
 namespace {
-template <typename T, int MODE, int AR, bool GAIN = false>
+template <typename T, int MODE, int AR, bool GAIN = false, bool ROB = false>
 void probe_cone_run(const kern::ProbeArgs& a) {
   constexpr int S = kern::kProbeSide;
   std::vector<T> planes((size_t)2 * S * S, T(0));
@@ -454,7 +536,7 @@ void probe_cone_run(const kern::ProbeArgs& a) {
     for (int s = 1; s <= k; ++s) {
       const int w = 2 * (k - s) + 1;
       for (int idx = 0; idx < w * w; ++idx)
-        kern::probe_point<T, MODE, AR, GAIN>(a, ci, cj, s, idx, plane[(s - 1) & 1], plane[s & 1]);
+        kern::probe_point<T, MODE, AR, GAIN, ROB>(a, ci, cj, s, idx, plane[(s - 1) & 1], plane[s & 1]);
       if (base + s - 1 < a.capacity) hist[(base + s - 1) * a.P + p] = plane[s & 1][k * S + k];
     }
   }
@@ -468,7 +550,12 @@ void probe_cone_mode(const kern::ProbeArgs& a, int arith) {
 }
 template <typename T>
 void probe_cone_typed(const kern::ProbeArgs& a, int arith) {
-  if (a.gain) {
+  if (a.robin) {
+    HEAT2D_REQUIRE(!a.source && !a.rmap && !a.rx && !a.gain && (arith == 0 || arith == 1),
+                   "probe_cone: Robin walls take the plain mode and arith exact or fma");
+    if (arith == 0) probe_cone_run<T, kern::kProbePlain, 0, false, true>(a);
+    else probe_cone_run<T, kern::kProbePlain, 1, false, true>(a);
+  } else if (a.gain) {
     HEAT2D_REQUIRE(a.source && (arith == 0 || arith == 1), "probe_cone: a gain schedule needs a source and arith exact or fma");
     if (arith == 0) probe_cone_run<T, kern::kProbeSource, 0, true>(a);
     else probe_cone_run<T, kern::kProbeSource, 1, true>(a);

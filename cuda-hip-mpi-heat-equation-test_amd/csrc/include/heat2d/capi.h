@@ -35,11 +35,15 @@ typedef struct heat2d_config {
   int32_t engine, arith; /* arith: 0 reference rounding, 1 contracted fma, 2 jacobi (r = 1/4) */
   int32_t edge_shift; /* rows each edge slab gives the middle ones (common.hpp decompose) */
   int64_t slab_row0, slab_rows_global; /* 1-rank rehearsal of a middle slab (0: the slab is the grid) */
-  int32_t bc_x, bc_y; /* boundary condition of the row / column axis: 0 dirichlet, 1 periodic, 2 insulated */
+  int32_t bc_x, bc_y; /* boundary condition of the row / column axis: 0 dirichlet, 1 periodic, 2 insulated, 3 robin */
   int32_t source; /* 1: the solver carries a heat source (heat2d_solver_set_source) */
   int32_t rmap;   /* 1: the solver carries a diffusivity map (heat2d_solver_set_rmap) */
   int32_t faces;  /* 1: the solver carries per-face diffusion numbers (heat2d_solver_set_faces) */
   int32_t pad1;
+  /* the (a, b) pairs of the Robin walls, ghost = a * C + b: {x_lo a, b, x_hi a, b, y_lo a, b, y_hi a, b}
+     (x_lo: the wall before the first owned row, y_lo: before the first owned column); read for the axes
+     whose bc is 3, converted to the run's dtype by the solver (heat2d_solver_robin returns them) */
+  double robin[8];
 } heat2d_config;
 
 typedef struct heat2d_tb_plan {
@@ -183,6 +187,16 @@ int heat2d_solver_set_source(void* s, const void* host, int64_t ld);
 int heat2d_solver_source(void* s, int32_t* out3);
 /* heat2d_tb / heat2d_cpu_tb with a heat source buffer in the field's layout (-0.0 in its frame and
    pad entries): Dirichlet axes, arith 0 / 1, k <= kMaxTBSrc on the device */
+/* heat2d_tb_bc / heat2d_cpu_tb_bc with Robin walls: bc may hold 16 (Robin x) | 32 (Robin y) beside the
+ * other kinds; robin: the 8 values of heat2d_config::robin, already in the field's dtype. At a point next to
+ * a Robin wall the operand from beyond the wall is a * C + b of the point's own value C at every fused level
+ * (arith 1: fma(a, C, b)); an insulated axis beside a Robin one runs as (1, -0.0). arith 0 / 1, depths
+ * 1..heat2d_max_tb_rob(). The frame of the rows written gets the ghost values. */
+int heat2d_tb_rob(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                  double r, void* stream, int64_t tile_rows, int arith, int bc, const double* robin);
+int heat2d_cpu_tb_rob(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                      double r, int arith, int bc, const double* robin);
+int heat2d_max_tb_rob(void);
 int heat2d_tb_src(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                   double r, void* stream, int64_t tile_rows, int arith, const void* source);
 int heat2d_cpu_tb_src(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
@@ -253,6 +267,9 @@ int heat2d_solver_clear_probe_history(void* s);
    points — device memory when on_device —, the centre after level s in out[(s - 1) * P + p] (k x P
    elements of dtype). arith 0 / 1 / 2 (2: no coefficient buffer), bc as heat2d_tb_bc, at most one of
    source / rmap / (rx, ry) in the field's layout; k <= L.halo ghost rows valid around every point. */
+/* heat2d_probe_cone in the plain mode with Robin walls (bc and robin as heat2d_tb_rob; arith 0 / 1) */
+int heat2d_probe_cone_rob(int dtype, const void* src, const heat2d_layout* L, int k, double r, int arith, int bc,
+                          const double* robin, const int64_t* pts, int64_t P, void* out, void* stream, int on_device);
 int heat2d_probe_cone(int dtype, const void* src, const heat2d_layout* L, int k, double r, int arith, int bc,
                       const void* source, const void* rmap, const void* rx, const void* ry, const int64_t* pts,
                       int64_t P, void* out, void* stream, int on_device);
@@ -301,6 +318,9 @@ int heat2d_solver_info(void* s, int32_t* tb, int64_t* band, int64_t* steps, void
 int heat2d_solver_arith(void* s, int32_t* out);
 /* boundary conditions the solver runs: 0 dirichlet, 1 periodic, 2 insulated, per axis */
 int heat2d_solver_bc(void* s, int32_t* bc_x, int32_t* bc_y);
+/* the Robin pairs the solver runs (heat2d_config::robin converted to its dtype; (1, -0.0) where the axis is
+   not Robin) and the depth clamp of the Robin kernels: out8 pairs, *max_tb (0 without a Robin axis) */
+int heat2d_solver_robin(void* s, double* out8, int32_t* max_tb);
 
 /* Loopback group: P slabs on one device (or host). */
 int heat2d_group_create(const heat2d_config* cfg, int nranks, void** out);

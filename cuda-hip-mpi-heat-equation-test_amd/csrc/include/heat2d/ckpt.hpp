@@ -19,7 +19,12 @@ struct Meta {
   std::string convention = "ghost";  // ghost | inclusive
   double sigma = 0, nu = 0, dom_len = 0, r = 0;
   int64_t edge_shift = 0;  // the writer's decomposition (common.hpp decompose); absent in older saves: 0
-  std::string bc_x = "dirichlet", bc_y = "dirichlet";  // dirichlet | periodic | insulated; absent in older saves: dirichlet
+  std::string bc_x = "dirichlet", bc_y = "dirichlet";  // dirichlet | periodic | insulated | robin; absent in older saves: dirichlet
+  // the Robin walls' pairs in the run's dtype, recorded exactly (meta.json "robin": {side: [a, b]} as hex
+  // floats, as utils/checkpoint.py writes them; the key only with a Robin axis). robin_sides: bit k = side
+  // k (x_lo, x_hi, y_lo, y_hi) is recorded; robin[2k], robin[2k + 1] its (a, b)
+  int robin_sides = 0;
+  double robin[8] = {1.0, -0.0, 1.0, -0.0, 1.0, -0.0, 1.0, -0.0};
   // the run's heat source: SHA-256 (hex) of the global frame-inclusive array's bytes in the run's
   // dtype, as utils/checkpoint.py records it; empty: none (null, or absent in older saves)
   std::string source_sha256;

@@ -63,6 +63,9 @@ constexpr int kMaxTBVar = 16;
 // Deepest pass of the conservative form (tb_kernel_div: depths 1..kMaxTBDiv, both
 // dtypes, exact and fma, none with scratch; a solver with face coefficients clamps to it).
 constexpr int kMaxTBDiv = 16;
+// Deepest pass with Robin walls (tb_kernel_rob: depths 1..kMaxTBRob, both dtypes,
+// exact and fma, none with scratch — every depth the insulated kernels have).
+constexpr int kMaxTBRob = 24;
 // Most probe points of one solver (Solver::set_probes: one probe_cone workgroup
 // per point and cycle).
 constexpr int kMaxProbes = 4096;

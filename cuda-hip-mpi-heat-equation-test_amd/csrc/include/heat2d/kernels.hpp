@@ -65,7 +65,32 @@ TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end
 //     the rows they wrote (launch_ins_cols / launch_ins_rows, same stream).
 //     Not with arith 3, nor the fused statistics; an axis is periodic or
 //     insulated, not both.
-constexpr int kBcPeriodicX = 1, kBcPeriodicY = 2, kBcInsulatedX = 4, kBcInsulatedY = 8;
+//   kBcRobinX / kBcRobinY: a Robin (convective) wall in the insulated
+//     geometry: the value beyond the wall is the affine ghost G = a * C + b of
+//     the adjacent owned point C (the product rounded, then the add; arith 1:
+//     fma(a, C, b)), with a pair (a, b) per wall (`robin`, the launchers' last
+//     argument). G depends on the level's own C, so it is formed inside the
+//     march at every level: tb_kernel_rob (tb_impl.hpp March ROB) takes the
+//     place of tb_kernel_ins in every launch, and an insulated wall on the
+//     other axis runs on it as (1, -0.0), which returns every C unchanged.
+//     The launchers write the ghost values into the frame of the rows they
+//     wrote (launch_rob_rows, then launch_rob_cols over the frame rows too:
+//     the golden's x first, then y). Arith 0 / 1, depths 1..kMaxTBRob.
+constexpr int kBcPeriodicX = 1, kBcPeriodicY = 2, kBcInsulatedX = 4, kBcInsulatedY = 8, kBcRobinX = 16, kBcRobinY = 32;
+// an axis with walls half a cell outside its first and last owned point
+constexpr int kBcWallX = kBcInsulatedX | kBcRobinX, kBcWallY = kBcInsulatedY | kBcRobinY;
+constexpr int kBcRobin = kBcRobinX | kBcRobinY;
+// The Robin pairs as the launchers take them: 8 values already converted to the
+// field's dtype, {x_lo a, b, x_hi a, b, y_lo a, b, y_hi a, b} (x_lo: the wall
+// before the first owned row, y_lo: before the first owned column); the entries
+// of an axis that is not Robin are not read.
+constexpr int kRobinXLo = 0, kRobinXHi = 2, kRobinYLo = 4, kRobinYHi = 6;
+// (a_lo, b_lo, a_hi, b_hi) of the walls of one axis in a launch with a Robin
+// axis: the axis' own pairs, or (1, -0.0) twice where it is insulated
+inline void wall_pairs(int bc, bool x_axis, const double* robin, double out[4]) {
+  const bool rob = (bc & (x_axis ? kBcRobinX : kBcRobinY)) != 0;
+  for (int i = 0; i < 4; ++i) out[i] = rob ? robin[(x_axis ? kRobinXLo : kRobinYLo) + i] : ((i & 1) ? -0.0 : 1.0);
+}
 // A source's gain schedule as the launchers take it (launch_tb below): the gain
 // array and the position word, both in the launch's memory space.
 struct GainRef {
@@ -106,6 +131,17 @@ void launch_wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k, hip
 // where it holds the last (hi); a slab off that edge is left alone.
 void launch_ins_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1, hipStream_t stream);
 void launch_ins_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool hi, hipStream_t stream);
+// Robin frame images (the ghost values a * C + b in the form `arith` names: 0
+// the product rounded then the add, 1 one fma), pairs as (a_lo, b_lo, a_hi,
+// b_hi) in the field's dtype. rob_rows: the whole padded row -1 from row 0 where
+// the slab holds the global first row (lo) and row nrows from row nrows - 1
+// where it holds the last (hi). rob_cols: columns -1 and ncols of rows [r0, r1)
+// (ghost / frame rows allowed). Rows first, then the columns over the frame
+// rows too, gives the golden's corner entries. Capturable.
+void launch_rob_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool hi, const double* pairs, int arith,
+                     hipStream_t stream);
+void launch_rob_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1, const double* pairs,
+                     int arith, hipStream_t stream);
 
 // dst(rows [row_begin,row_end)) = k FTCS steps of src. `src`/`dst` are
 // allocation bases laid out per `L`. Requires k <= L.halo and the k ghost rows
@@ -141,15 +177,20 @@ void launch_ins_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool h
 // pos: a device word, read when the kernel runs, so a captured launch takes the
 // position of its replay. Every rect runs tb_kernel_gain, tb_kernel_src's
 // launch shape. {}: the source as it is.
+// robin (optional, after gain; needed with kBcRobinX / kBcRobinY in bc): the 8
+// values of the Robin walls' pairs in the field's dtype (kRobinXLo ..), read on
+// the host when the launch is made and passed to tb_kernel_rob by value, so a
+// captured launch keeps them. Every launch that would run tb_kernel_ins runs
+// tb_kernel_rob: arith 0 / 1, depths 1..kMaxTBRob, no source / rmap / faces.
 void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
                int64_t row_end, int k, double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0,
                int arith = 0, int bc = 0, const void* source = nullptr, const void* rmap = nullptr,
-               const void* rx = nullptr, const void* ry = nullptr, GainRef gain = {});
+               const void* rx = nullptr, const void* ry = nullptr, GainRef gain = {}, const double* robin = nullptr);
 // Same for TWO disjoint row ranges [rb0, re0) and [rb1, re1) in one launch.
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
                 int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0,
                 int arith = 0, int bc = 0, const void* source = nullptr, const void* rmap = nullptr,
-                const void* rx = nullptr, const void* ry = nullptr, GainRef gain = {});
+                const void* rx = nullptr, const void* ry = nullptr, GainRef gain = {}, const double* robin = nullptr);
 
 // Split schedule of one cycle (k steps over the whole slab) into two launches
 // on two streams:
@@ -228,12 +269,12 @@ bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i);
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
                       hipStream_t stream, int arith = 0, int bc = 0, const void* source = nullptr,
                       const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr,
-                      GainRef gain = {});
+                      GainRef gain = {}, const double* robin = nullptr);
 // queue: 2 device counters (zeroed once) for plans with flags & kPlanDynamic (dynamic items)
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
                   double r, hipStream_t stream, int arith = 0, uint32_t* queue = nullptr, int bc = 0,
                   const void* source = nullptr, const void* rmap = nullptr, const void* rx = nullptr,
-                  const void* ry = nullptr, GainRef gain = {});
+                  const void* ry = nullptr, GainRef gain = {}, const double* robin = nullptr);
 
 // Initial / boundary condition kinds (covers every IC of the reference
 // variants, see models/presets.py for the mapping).

@@ -52,10 +52,17 @@ struct ProbeArgs {
   const void* gain;
   const int64_t* gain_pos;  // the solver's position word (nullptr: 0)
   int64_t gain_pos0;
+  // Robin walls (robin != 0; plain mode, arith exact / fma): the operand beyond a
+  // wall line is the ghost value a * C + b with the wall's pair, in the field's
+  // dtype: rob = {r0 a, b, r1 a, b, c0 a, b, c1 a, b}; an insulated axis beside
+  // a Robin one holds (1, -0.0)
+  int32_t robin;
+  double rob[8];
 };
 
 // The frame and wall lines of a slab under boundary bits `bc`.
-inline void probe_bounds(ProbeArgs& a, const SlabLayout& L, int bc) {
+// (robin: the launchers' pairs, kernels.hpp — read only with a Robin axis in bc)
+inline void probe_bounds(ProbeArgs& a, const SlabLayout& L, int bc, const double* robin = nullptr) {
   const SlabLayout Lk = bc_layout(L, bc);
   const int64_t dc = L.cpad - Lk.cpad;  // the widened grid's column 0 is real column -dc
   a.L = L;
@@ -64,14 +71,28 @@ inline void probe_bounds(ProbeArgs& a, const SlabLayout& L, int bc) {
   a.frame_c0 = -1 - dc;
   a.frame_c1 = Lk.ncols - dc;
   const int64_t none = INT64_MIN;
-  a.wall_r0 = (bc & kBcInsulatedX) ? -L.row0 : none;
-  a.wall_r1 = (bc & kBcInsulatedX) ? L.nrows_global - 1 - L.row0 : none;
-  a.wall_c0 = (bc & kBcInsulatedY) ? 0 : none;
-  a.wall_c1 = (bc & kBcInsulatedY) ? L.ncols - 1 : none;
+  a.wall_r0 = (bc & kBcWallX) ? -L.row0 : none;
+  a.wall_r1 = (bc & kBcWallX) ? L.nrows_global - 1 - L.row0 : none;
+  a.wall_c0 = (bc & kBcWallY) ? 0 : none;
+  a.wall_c1 = (bc & kBcWallY) ? L.ncols - 1 : none;
+  a.robin = (bc & kBcRobin) ? 1 : 0;
+  for (int i = 0; i < 8; ++i) a.rob[i] = (i & 1) ? -0.0 : 1.0;
+  if (a.robin) {
+    HEAT2D_REQUIRE(robin, "probe_cone: a Robin axis needs the walls' pairs");
+    wall_pairs(bc, true, robin, a.rob);
+    wall_pairs(bc, false, robin, a.rob + 4);
+  }
 }
 
 __host__ __device__ inline float probe_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __host__ __device__ inline double probe_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+// The value beyond a Robin wall from the adjacent point c: a * c + b, the product
+// rounded, then the add; AR 1: one fma (the march's tb_impl.hpp rob_ghost).
+template <typename T, int AR>
+__host__ __device__ inline T probe_ghost(double a, T c, double b) {
+  if (AR == 1) return probe_fma((T)a, c, (T)b);
+  return (T)a * c + (T)b;
+}
 
 // One point's update (compiled with contraction off: every operation below
 // rounds on its own unless it is written as an fma). c: centre; s, e, n, w:
@@ -103,7 +124,8 @@ __host__ __device__ inline T probe_update(T c, T s, T e, T n, T w, const T* coef
 
 // Level s of one probe's cone, point `idx` of the (2 (k - s) + 1)^2 updated at
 // that level: from plane `in` into plane `out` (kProbeSide x kProbeSide).
-template <typename T, int MODE, int AR, bool GAIN = false>
+// ROB: the operand beyond a wall line is the wall's ghost value (ProbeArgs::rob).
+template <typename T, int MODE, int AR, bool GAIN = false, bool ROB = false>
 __host__ __device__ inline void probe_point(const ProbeArgs& a, int64_t ci, int64_t cj, int s, int idx, const T* in,
                                             T* out) {
   const int w = 2 * (a.k - s) + 1;
@@ -116,10 +138,18 @@ __host__ __device__ inline void probe_point(const ProbeArgs& a, int64_t ci, int6
     out[at] = c;  // a Dirichlet frame line (or the unread image line of an insulated axis)
     return;
   }
-  const T so = row == a.wall_r1 ? c : in[at + kProbeSide];
-  const T ea = col == a.wall_c1 ? c : in[at + 1];
-  const T no = row == a.wall_r0 ? c : in[at - kProbeSide];
-  const T we = col == a.wall_c0 ? c : in[at - 1];
+  T so, ea, no, we;
+  if (ROB) {
+    so = row == a.wall_r1 ? probe_ghost<T, AR>(a.rob[2], c, a.rob[3]) : in[at + kProbeSide];
+    ea = col == a.wall_c1 ? probe_ghost<T, AR>(a.rob[6], c, a.rob[7]) : in[at + 1];
+    no = row == a.wall_r0 ? probe_ghost<T, AR>(a.rob[0], c, a.rob[1]) : in[at - kProbeSide];
+    we = col == a.wall_c0 ? probe_ghost<T, AR>(a.rob[4], c, a.rob[5]) : in[at - 1];
+  } else {
+    so = row == a.wall_r1 ? c : in[at + kProbeSide];
+    ea = col == a.wall_c1 ? c : in[at + 1];
+    no = row == a.wall_r0 ? c : in[at - kProbeSide];
+    we = col == a.wall_c0 ? c : in[at - 1];
+  }
   T coef[4];
   const int64_t o = a.L.offset(row, col);
   if (MODE == kProbeFaces) {

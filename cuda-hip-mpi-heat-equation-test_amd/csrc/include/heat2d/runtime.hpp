@@ -84,12 +84,22 @@ struct SolverConfig {
   // copy_swap, no source, no rmap; the depth is clamped to kMaxTBDiv. 0: today's solver.
   int32_t faces;
   int32_t pad1;
+  // bc_x / bc_y 3, Robin (convective) walls in the insulated geometry: the
+  // value beyond a wall is the ghost a * C + b of the adjacent owned point C
+  // (the product rounded, then the add; arith fma: one rounding), formed at
+  // every fused level. The pairs (kernels.hpp kRobinXLo ..): {x_lo a, b, x_hi
+  // a, b, y_lo a, b, y_hi a, b}, read for the Robin axes, finite, converted to
+  // the run's dtype by the solver. arith exact / fma (auto: fma when r is a
+  // power of two, else exact — never jacobi), engine "tb", no copy_swap, no
+  // source / rmap / faces; the depth is clamped to kMaxTBRob.
+  double robin[8];
 };
-constexpr int32_t kBcDirichlet = 0, kBcPeriodic = 1, kBcInsulated = 2;
+constexpr int32_t kBcDirichlet = 0, kBcPeriodic = 1, kBcInsulated = 2, kBcRobinKind = 3;
 // the kernels' bit set (kernels.hpp kBcPeriodicX / ... / kBcInsulatedY) of a config
 inline int config_bc(const SolverConfig& c) {
   return (c.bc_x == kBcPeriodic ? kern::kBcPeriodicX : 0) | (c.bc_y == kBcPeriodic ? kern::kBcPeriodicY : 0) |
-         (c.bc_x == kBcInsulated ? kern::kBcInsulatedX : 0) | (c.bc_y == kBcInsulated ? kern::kBcInsulatedY : 0);
+         (c.bc_x == kBcInsulated ? kern::kBcInsulatedX : 0) | (c.bc_y == kBcInsulated ? kern::kBcInsulatedY : 0) |
+         (c.bc_x == kBcRobinKind ? kern::kBcRobinX : 0) | (c.bc_y == kBcRobinKind ? kern::kBcRobinY : 0);
 }
 
 // ---------------------------------------------------------------- transports
@@ -268,12 +278,16 @@ std::shared_ptr<Transport> make_ipc_loop_transport(int device);
 namespace cpu {
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
         int64_t row_end, int k, double r, int arith = 0, int bc = 0, const void* source = nullptr,
-        const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr, kern::GainRef gain = {});
+        const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr, kern::GainRef gain = {},
+        const double* robin = nullptr);
 void wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1);
 void wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k);
 // insulated frame images (kern::launch_ins_cols / launch_ins_rows)
 void ins_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1);
 void ins_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool hi);
+// Robin frame images (kern::launch_rob_cols / launch_rob_rows)
+void rob_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1, const double* pairs, int arith);
+void rob_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool hi, const double* pairs, int arith);
 void init(DType dt, void* field, const SlabLayout& L, const kern::IcParams& ic,
           const double* xcoord, const double* ycoord);
 void stats(DType dt, const void* field, const void* other, const SlabLayout& L, double out[6]);
@@ -620,6 +634,8 @@ class Solver {
   void* gain_buf_ = nullptr;
   int64_t* gain_posw_ = nullptr;
   int64_t gain_len_ = 0, gain_pos_ = 0;
+  // the Robin walls' pairs in the run's dtype (nullptr without a Robin axis)
+  const double* robin() const { return (bc_ & kern::kBcRobin) ? cfg_.robin : nullptr; }
   kern::GainRef gain() const { return gain_on() ? kern::GainRef{gain_buf_, gain_posw_ + cur_} : kern::GainRef{}; }
   void free_gain();
   // both position words <- gain_pos_ (synchronised): wherever cur_ is set outside a cycle,

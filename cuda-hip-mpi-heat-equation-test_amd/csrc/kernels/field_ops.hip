@@ -292,6 +292,35 @@ __global__ __launch_bounds__(256) void ins_cols_kernel(T* __restrict__ f, SlabLa
   }
 }
 
+// Robin walls: the frame entries as ghost values a * C + b of the adjacent owned
+// point (AR 1: one fma; else the product rounded, then the add — this unit is
+// built with -ffp-contract=off). rob_cols: columns -1 and ncols of rows
+// [r0, r1), one thread per (row, side). rob_rows: a whole padded row `dst` from
+// the row `src` beside it, one thread per element.
+template <typename T, int AR>
+__device__ __forceinline__ T rob_image(T a, T c, T b) {
+  if constexpr (AR == 1 && sizeof(T) == 4) return __builtin_fmaf(a, c, b);
+  else if constexpr (AR == 1) return __builtin_fma(a, c, b);
+  else return a * c + b;
+}
+template <typename T, int AR>
+__global__ __launch_bounds__(256) void rob_cols_kernel(T* __restrict__ f, SlabLayout L, int64_t r0, int64_t r1, T a_lo,
+                                                       T b_lo, T a_hi, T b_hi) {
+  const int64_t total = (r1 - r0) * 2;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+    T* row = f + L.offset(r0 + (t >> 1), 0);
+    if (t & 1) row[L.ncols] = rob_image<T, AR>(a_hi, row[L.ncols - 1], b_hi);
+    else row[-1] = rob_image<T, AR>(a_lo, row[0], b_lo);
+  }
+}
+template <typename T, int AR>
+__global__ __launch_bounds__(256) void rob_rows_kernel(T* __restrict__ dst, const T* __restrict__ src, int64_t n, T a,
+                                                       T b) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = rob_image<T, AR>(a, src[i], b);
+}
+
 // Periodic x on one rank: whole padded rows [nrows-k, nrows) -> [-k, 0) and
 // [0, k) -> [nrows, nrows+k), 16 B per lane (n16 vectors per block of k rows;
 // k <= nrows: sources and destinations are disjoint).
@@ -445,6 +474,52 @@ void launch_ins_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool h
   if (hi && L.row0 + L.nrows == L.nrows_global) {
     hipLaunchKernelGGL(copy16_kernel, dim3(grid_for(n16)), dim3(256), 0, stream, row(L.nrows - 1), row(L.nrows), n16);
     check_launch("ins_rows");
+  }
+}
+
+namespace {
+template <typename T>
+void rob_cols_t(T* f, const SlabLayout& L, int64_t r0, int64_t r1, const double* p, int arith, hipStream_t stream) {
+  const unsigned g = grid_for((r1 - r0) * 2);
+  if (arith == 1)
+    hipLaunchKernelGGL((rob_cols_kernel<T, 1>), dim3(g), dim3(256), 0, stream, f, L, r0, r1, (T)p[0], (T)p[1], (T)p[2], (T)p[3]);
+  else
+    hipLaunchKernelGGL((rob_cols_kernel<T, 0>), dim3(g), dim3(256), 0, stream, f, L, r0, r1, (T)p[0], (T)p[1], (T)p[2], (T)p[3]);
+}
+template <typename T>
+void rob_row_t(T* f, const SlabLayout& L, int64_t to, int64_t from, double a, double b, int arith, hipStream_t stream) {
+  T* dst = f + L.offset(to, -L.cpad);
+  const T* src = f + L.offset(from, -L.cpad);
+  const unsigned g = grid_for(L.pitch);
+  if (arith == 1) hipLaunchKernelGGL((rob_rows_kernel<T, 1>), dim3(g), dim3(256), 0, stream, dst, src, L.pitch, (T)a, (T)b);
+  else hipLaunchKernelGGL((rob_rows_kernel<T, 0>), dim3(g), dim3(256), 0, stream, dst, src, L.pitch, (T)a, (T)b);
+}
+}  // namespace
+
+void launch_rob_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1, const double* pairs,
+                     int arith, hipStream_t stream) {
+  if (r1 <= r0) return;
+  HEAT2D_REQUIRE(pairs && (arith == 0 || arith == 1), "rob_cols: the walls' pairs and arith 0 (exact) or 1 (fma)");
+  HEAT2D_REQUIRE(r0 >= -L.halo && r1 <= L.nrows + L.halo, "rob_cols: rows outside the allocation");
+  HEAT2D_REQUIRE(L.ncols >= 1 && L.cpad >= 1 && L.col_hi() > L.ncols, "rob_cols: no room for the frame columns");
+  if (dt == DType::F32) rob_cols_t(static_cast<float*>(field), L, r0, r1, pairs, arith, stream);
+  else rob_cols_t(static_cast<double*>(field), L, r0, r1, pairs, arith, stream);
+  check_launch("rob_cols");
+}
+
+void launch_rob_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool hi, const double* pairs, int arith,
+                     hipStream_t stream) {
+  HEAT2D_REQUIRE(pairs && (arith == 0 || arith == 1), "rob_rows: the walls' pairs and arith 0 (exact) or 1 (fma)");
+  HEAT2D_REQUIRE(L.halo >= 1 && L.nrows >= 1, "rob_rows: no room for the frame rows");
+  if (lo && L.row0 == 0) {
+    if (dt == DType::F32) rob_row_t(static_cast<float*>(field), L, -1, 0, pairs[0], pairs[1], arith, stream);
+    else rob_row_t(static_cast<double*>(field), L, -1, 0, pairs[0], pairs[1], arith, stream);
+    check_launch("rob_rows");
+  }
+  if (hi && L.row0 + L.nrows == L.nrows_global) {
+    if (dt == DType::F32) rob_row_t(static_cast<float*>(field), L, L.nrows, L.nrows - 1, pairs[2], pairs[3], arith, stream);
+    else rob_row_t(static_cast<double*>(field), L, L.nrows, L.nrows - 1, pairs[2], pairs[3], arith, stream);
+    check_launch("rob_rows");
   }
 }
 

@@ -275,9 +275,29 @@ int64_t choose_bands(int64_t rows, int64_t ns, int64_t simds, int k, int64_t pri
 }
 
 // Insulated edges (kBcInsulatedX / kBcInsulatedY): the kernel argument of tb_kernel_ins and its occupancy
-constexpr int kBcAll = kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY;
+// (a Robin axis has the insulated walls: tb_kernel_rob takes the same edges beside its pairs)
+constexpr int kBcAll = kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY | kBcRobinX | kBcRobinY;
 int ins_edges(int bc) {
-  return ((bc & kBcInsulatedX) ? (kInsRowLo | kInsRowHi) : 0) | ((bc & kBcInsulatedY) ? (kInsColLo | kInsColHi) : 0);
+  return ((bc & kBcWallX) ? (kInsRowLo | kInsRowHi) : 0) | ((bc & kBcWallY) ? (kInsColLo | kInsColHi) : 0);
+}
+// Robin walls (tb_kernel_rob): resident 256-thread workgroups per CU
+int occupancy_rob(DType dt, int k, int arith) {
+  HEAT2D_REQUIRE(arith == 0 || arith == 1, "Robin walls need arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 would need b scaled per level");
+  if (arith == 1) return dt == DType::F32 ? occupancy_blocks_rob<float, 1>(k) : occupancy_blocks_rob<double, 1>(k);
+  return dt == DType::F32 ? occupancy_blocks_rob<float, 0>(k) : occupancy_blocks_rob<double, 0>(k);
+}
+// the pairs of the launch as the kernel takes them (insulated walls of a launch with a Robin axis: (1, -0.0))
+template <typename T>
+RobCoef<T> rob_coef(int bc, const double* robin) {
+  double x[4], y[4];
+  wall_pairs(bc, true, robin, x);
+  wall_pairs(bc, false, robin, y);
+  RobCoef<T> g;
+  g.a[kRobN] = (T)x[0]; g.b[kRobN] = (T)x[1];
+  g.a[kRobS] = (T)x[2]; g.b[kRobS] = (T)x[3];
+  g.a[kRobW] = (T)y[0]; g.b[kRobW] = (T)y[1];
+  g.a[kRobE] = (T)y[2]; g.b[kRobE] = (T)y[3];
+  return g;
 }
 int occupancy_ins(DType dt, int k, int arith) {
   return with_ar(arith, [&](auto ar) {
@@ -324,9 +344,13 @@ int occupancy_div(DType dt, int k, int arith) {
 // frame row of a slab at the wall — one fill per run of rows the rects cover
 // (rects of one launch share rows strip by strip, or are disjoint bands):
 // never a row another launch writes. Same stream as the launch.
+// With a Robin axis (robin != nullptr) every wall's frame entries are ghost
+// values in the form `arith` names (an insulated axis beside it: (1, -0.0), the
+// image), the wall rows first and then the wall columns over the frame rows
+// just written too: the golden's x first, then y over the filled rows.
 void fill_frames(DType dt, void* dst, const SlabLayout& L0, const TbRect* rects, int nrect, int bc,
-                 hipStream_t stream) {
-  if (!(bc & (kBcPeriodicY | kBcInsulatedX | kBcInsulatedY))) return;
+                 hipStream_t stream, const double* robin = nullptr, int arith = 0) {
+  if (!(bc & (kBcPeriodicY | kBcWallX | kBcWallY))) return;
   int64_t lo[2 * kMaxRects], hi[2 * kMaxRects];
   int n = 0;
   for (int i = 0; i < nrect; ++i) {
@@ -347,6 +371,19 @@ void fill_frames(DType dt, void* dst, const SlabLayout& L0, const TbRect* rects,
     lo[n] = b;
     hi[n] = t;
     ++n;
+  }
+  if (bc & kBcRobin) {
+    double px[4], py[4];
+    wall_pairs(bc, true, robin, px);
+    wall_pairs(bc, false, robin, py);
+    for (int j = 0; j < n; ++j) {
+      const bool tlo = (bc & kBcWallX) && L0.row0 == 0 && lo[j] <= 0 && hi[j] > 0;
+      const bool thi = (bc & kBcWallX) && L0.row0 + L0.nrows == L0.nrows_global && lo[j] < L0.nrows && hi[j] >= L0.nrows;
+      if (bc & kBcPeriodicY) launch_wrap_cols(dt, dst, L0, lo[j], hi[j], stream);  // (the wall rows carry them on)
+      if (bc & kBcWallX) launch_rob_rows(dt, dst, L0, tlo, thi, px, arith, stream);
+      if (bc & kBcWallY) launch_rob_cols(dt, dst, L0, lo[j] - (tlo ? 1 : 0), hi[j] + (thi ? 1 : 0), py, arith, stream);
+    }
+    return;
   }
   for (int j = 0; j < n; ++j) {
     if (bc & kBcPeriodicY) launch_wrap_cols(dt, dst, L0, lo[j], hi[j], stream);
@@ -370,7 +407,7 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
                        const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
                        double* partials, uint32_t* queue, int bc, bool pipe, const void* source = nullptr,
                        const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr,
-                       GainRef gain = {}) {
+                       GainRef gain = {}, const double* robin = nullptr) {
   // rx / ry != nullptr (the per-face diffusion numbers in the field's layout; Dirichlet axes only):
   // every launch, interior ones too, runs tb_kernel_div (ring 4, the general kernel's four edge kinds)
   // on at most as many waves as that kernel keeps resident; `r` is not used.
@@ -410,6 +447,12 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
   if (ins) {
     HEAT2D_REQUIRE(!partials, "the fused-statistics kernel has no insulated boundaries");
     HEAT2D_REQUIRE(arith != 3, "insulated boundaries have no arith 3 (fast) kernels");
+  }
+  const bool rob = ins && (bc & kBcRobin);  // a Robin axis: every wall of the launch on tb_kernel_rob
+  if (bc & kBcRobin) {
+    HEAT2D_REQUIRE(robin, "a Robin axis needs the walls' pairs (robin)");
+    HEAT2D_REQUIRE(arith == 0 || arith == 1, "Robin walls need arith 0 (exact) or 1 (fma)");
+    HEAT2D_REQUIRE(k <= kMaxTBRob, "temporal depth exceeds the Robin-wall kernels' deepest pass (kMaxTBRob)");
   }
   const SlabLayout L = bc_layout(L0, bc);
   check_layout(dt, L, k);  // (the shifted rows must still fit the march's 32-bit row index)
@@ -509,6 +552,18 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
       if (arith == 1) dispatch_src<double, 1>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, r, q64, stream);
       else dispatch_src<double, 0>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, r, q64, stream);
     }
+  } else if (rob) {
+    if (dt == DType::F32) {
+      const float *s32 = static_cast<const float*>(src) + o;
+      const RobCoef<float> g = rob_coef<float>(bc, robin);
+      if (arith == 1) dispatch_rob<float, 1>(k, nblocks, s32, static_cast<float*>(dst) + o, a, (float)r, ins, g, stream);
+      else dispatch_rob<float, 0>(k, nblocks, s32, static_cast<float*>(dst) + o, a, (float)r, ins, g, stream);
+    } else {
+      const double *s64 = static_cast<const double*>(src) + o;
+      const RobCoef<double> g = rob_coef<double>(bc, robin);
+      if (arith == 1) dispatch_rob<double, 1>(k, nblocks, s64, static_cast<double*>(dst) + o, a, r, ins, g, stream);
+      else dispatch_rob<double, 0>(k, nblocks, s64, static_cast<double*>(dst) + o, a, r, ins, g, stream);
+    }
   } else if (ins) {
     with_ar(arith, [&](auto ar) {
       constexpr int AR = decltype(ar)::value;
@@ -554,14 +609,18 @@ int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0,
                      const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
                      double* partials = nullptr, uint32_t* queue = nullptr, int bc = 0, bool pipe = false,
                      const void* source = nullptr, const void* rmap = nullptr, const void* rx = nullptr,
-                     const void* ry = nullptr, GainRef gain = {}) {
-  HEAT2D_REQUIRE((bc & ~kBcAll) == 0, "bc must be a set of kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY");
+                     const void* ry = nullptr, GainRef gain = {}, const double* robin = nullptr) {
+  HEAT2D_REQUIRE((bc & ~kBcAll) == 0,
+                 "bc must be a set of kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY | kBcRobinX | kBcRobinY");
   HEAT2D_REQUIRE(!((bc & kBcPeriodicX) && (bc & kBcInsulatedX)) && !((bc & kBcPeriodicY) && (bc & kBcInsulatedY)),
                  "an axis is periodic or insulated, not both");
-  if (!(main && (bc & kBcInsulatedY))) {
+  HEAT2D_REQUIRE(!((bc & kBcRobinX) && (bc & (kBcPeriodicX | kBcInsulatedX))) &&
+                     !((bc & kBcRobinY) && (bc & (kBcPeriodicY | kBcInsulatedY))),
+                 "an axis has one boundary kind: Robin, periodic or insulated");
+  if (!(main && (bc & kBcWallY))) {
     const int64_t nw = launch_rects_1(dt, src, dst, L0, k, ring, main, rects, nrect, nwaves, r, stream, arith, partials,
-                                      queue, bc, pipe, source, rmap, rx, ry, gain);
-    fill_frames(dt, dst, L0, rects, nrect, bc, stream);
+                                      queue, bc, pipe, source, rmap, rx, ry, gain, robin);
+    fill_frames(dt, dst, L0, rects, nrect, bc, stream, robin, arith);
     return nw;
   }
   HEAT2D_REQUIRE(!source && !rmap && !rx && !ry,
@@ -576,7 +635,7 @@ int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0,
   const int64_t KA = halo_cols(dt, k), ncols = bc_layout(L0, bc).ncols;
   int64_t sF = ns;
   while (sF > 1 && (sF - 1) * U + U + KA > ncols) --sF;
-  const int64_t slots = (int64_t)cu_count() * occupancy_ins(dt, k, arith) * 4;
+  const int64_t slots = (int64_t)cu_count() * ((bc & kBcRobin) ? occupancy_rob(dt, k, arith) : occupancy_ins(dt, k, arith)) * 4;
   TbRect in[kMainRects], fr[2 * kMainRects];
   int ni = 0, nf = 0;
   for (int i = 0; i < nrect; ++i) {
@@ -599,11 +658,12 @@ int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0,
   }
   int64_t nw = 0;
   if (ni > 0)
-    nw = launch_rects_1(dt, src, dst, L0, k, ring, true, in, ni, nwaves, r, stream, arith, nullptr, queue, bc, false);
+    nw = launch_rects_1(dt, src, dst, L0, k, ring, true, in, ni, nwaves, r, stream, arith, nullptr, queue, bc, false,
+                        nullptr, nullptr, nullptr, nullptr, {}, robin);
   for (int i = 0; i < nf; i += kMaxRects)
     launch_rects_1(dt, src, dst, L0, k, 4, false, fr + i, std::min(nf - i, kMaxRects), slots, r, stream, arith, nullptr,
-                   nullptr, bc, false);
-  fill_frames(dt, dst, L0, rects, nrect, bc, stream);
+                   nullptr, bc, false, nullptr, nullptr, nullptr, nullptr, {}, robin);
+  fill_frames(dt, dst, L0, rects, nrect, bc, stream, robin, arith);
   return nw;
 }
 
@@ -651,13 +711,15 @@ TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end
 
 void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end, int k,
                double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc, const void* source,
-               const void* rmap, const void* rx, const void* ry, GainRef gain) {
-  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith, bc, source, rmap, rx, ry, gain);
+               const void* rmap, const void* rx, const void* ry, GainRef gain, const double* robin) {
+  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith, bc, source, rmap, rx, ry, gain,
+             robin);
 }
 
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
                 int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc,
-                const void* source, const void* rmap, const void* rx, const void* ry, GainRef gain) {
+                const void* source, const void* rmap, const void* rx, const void* ry, GainRef gain,
+                const double* robin) {
   check_layout(dt, L, k);
   const int64_t n0 = std::max<int64_t>(0, re0 - rb0), n1 = std::max<int64_t>(0, re1 - rb1);
   if (n0 + n1 == 0) return;
@@ -672,7 +734,7 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
     if (n0 > 0) rects[nr++] = TbRect{rb0, re0, 0, p.nstrips, -std::min<int64_t>(s0, n0 * p.nstrips)};
     if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, -std::min<int64_t>(std::max<int64_t>(1, ns - s0), n1 * p.nstrips)};
     launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, p.nwaves, r, stream, arith, nullptr, nullptr, bc,
-                 false, source, rmap, rx, ry, gain);
+                 false, source, rmap, rx, ry, gain, robin);
     return;
   }
   const int64_t nb = std::max<int64_t>(p.ntiles, (n0 > 0) + (n1 > 0));
@@ -681,7 +743,7 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
   if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, std::min<int64_t>(nb - nb0, n1)};
   const int64_t slots = (int64_t)(cus > 0 ? cus : cu_count()) * p.blocks_per_cu * 4;
   launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, slots, r, stream, arith, nullptr, nullptr, bc, false,
-               source, rmap, rx, ry, gain);
+               source, rmap, rx, ry, gain, robin);
 }
 
 // r = 1/4 kernels (arith 2): an interior item costs 3 adds + 2 DPP moves per
@@ -956,19 +1018,19 @@ bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i) {
 
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
                       hipStream_t stream, int arith, int bc, const void* source, const void* rmap, const void* rx,
-                      const void* ry, GainRef gain) {
+                      const void* ry, GainRef gain, const double* robin) {
   HEAT2D_REQUIRE(i >= 0 && i < p.nedge, "edge rect index");
   const TbRect& R = p.edge[i];
   const bool on_main = edges_on_main(bc_layout(L, bc), p.k, &R, 1);
   const int64_t items = R.nb > 0 ? R.nb * (R.s1 - R.s0) : -R.nb;
   const int64_t slots = (int64_t)cu_count() * occupancy(dt, p.ring, on_main, p.k, arith) * 4;
   launch_rects(dt, src, dst, L, p.k, p.ring, on_main, &R, 1, std::min<int64_t>(items, slots), r, stream, arith,
-               nullptr, nullptr, bc, false, source, rmap, rx, ry, gain);
+               nullptr, nullptr, bc, false, source, rmap, rx, ry, gain, robin);
 }
 
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
                   double r, hipStream_t stream, int arith, uint32_t* queue, int bc, const void* source,
-                  const void* rmap, const void* rx, const void* ry, GainRef gain) {
+                  const void* rmap, const void* rx, const void* ry, GainRef gain, const double* robin) {
   HEAT2D_REQUIRE(!(rx || ry) || !(p.flags & kPlanPipe), "face coefficients have no wave-pair kernel (no pipe plans)");
   HEAT2D_REQUIRE(!source || !(p.flags & kPlanPipe), "a heat source has no wave-pair kernel (no pipe plans)");
   HEAT2D_REQUIRE(!rmap || !(p.flags & kPlanPipe), "a diffusivity map has no wave-pair kernel (no pipe plans)");
@@ -981,15 +1043,15 @@ void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, con
   if (p.valid == 2) {  // single general launch over the whole slab (no edge part)
     if (main_part)
       launch_rects(dt, src, dst, L, p.k, p.ring, false, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc, false,
-                   source, rmap, rx, ry, gain);
+                   source, rmap, rx, ry, gain, robin);
     return;
   }
   if (main_part)
     launch_rects(dt, src, dst, L, p.k, p.ring, true, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc,
-                 (p.flags & kPlanPipe) != 0, source, rmap, rx, ry, gain);
+                 (p.flags & kPlanPipe) != 0, source, rmap, rx, ry, gain, robin);
   else
     launch_rects(dt, src, dst, L, p.k, p.ring, edges_on_main(bc_layout(L, bc), p.k, p.edge, p.nedge), p.edge, p.nedge,
-                 p.edge_waves, r, stream, arith, nullptr, nullptr, bc, false, source, rmap, rx, ry, gain);
+                 p.edge_waves, r, stream, arith, nullptr, nullptr, bc, false, source, rmap, rx, ry, gain, robin);
 }
 
 }  // namespace kern

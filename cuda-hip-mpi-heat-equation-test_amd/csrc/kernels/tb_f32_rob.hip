@@ -1,0 +1,11 @@
+// Instantiation unit: the general temporal-blocked stencil with Robin walls
+// (float, ring 4, reference arithmetic AR = 0; see tb_impl.hpp tb_kernel_rob / March ROB).
+#include "tb_impl.hpp"
+
+namespace heat2d {
+namespace kern {
+namespace tbimpl {
+H2D_ROB_UNIT(float, 0, H2D_TB_CASES_F32DEEP)
+}  // namespace tbimpl
+}  // namespace kern
+}  // namespace heat2d

@@ -1,0 +1,11 @@
+// Instantiation unit: the general temporal-blocked stencil with Robin walls
+// (double, ring 4, reference arithmetic AR = 0; see tb_impl.hpp tb_kernel_rob / March ROB).
+#include "tb_impl.hpp"
+
+namespace heat2d {
+namespace kern {
+namespace tbimpl {
+H2D_ROB_UNIT(double, 0, H2D_TB_CASES_DEEP)
+}  // namespace tbimpl
+}  // namespace kern
+}  // namespace heat2d

@@ -327,6 +327,29 @@ struct WallState<true> {
   bool wall_w;
   uint32_t wall_e;
 };
+// ROB (tb_kernel_rob, on top of INS: Robin / convective walls): the operand
+// from beyond a wall is the affine ghost value G = a * C + b of the point's own
+// value C (the product rounded, then the add; AR 1: fma(a, C, b), one rounding)
+// with the wall's own pair (a, b), formed at every level from that level's C —
+// a frame refreshed once per pass would be stale from level 2 on. (1, -0.0) is
+// the insulated wall, bit for bit. The four pairs are wave-uniform (the
+// kernel's extra argument). (Empty unless ROB, as the states around it.)
+template <typename T>
+struct RobCoef {
+  T a[4], b[4];  // 0: first row's wall (north), 1: last row's (south), 2: first column's (west), 3: last column's (east)
+};
+constexpr int kRobN = 0, kRobS = 1, kRobW = 2, kRobE = 3;
+template <typename T, bool ROB>
+struct RobState {};
+template <typename T>
+struct RobState<T, true> {
+  RobCoef<T> g;
+};
+template <int AR, typename T>
+__device__ __forceinline__ T rob_ghost(T a, T c, T b) {
+  if constexpr (AR == 1) return fma_t(a, c, b);
+  else return a * c + b;
+}
 // SRC (tb_kernel_src, a heat source S added at every level: T' = update + S,
 // one separately rounded add per point and level): at march row m level s
 // works on row m + off(s), so K source rows are live at once and every row is
@@ -461,8 +484,11 @@ struct GainState<T, K, true> {
   T gs[K];  // gs[s - 1]: the gain of level s
 };
 template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false,
-          bool SRC = false, bool VAR = false, bool DIV = false, bool GAIN = false>
-struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, DIV>, GainState<T, K, GAIN> {
+          bool SRC = false, bool VAR = false, bool DIV = false, bool GAIN = false, bool ROB = false>
+struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, DIV>, GainState<T, K, GAIN>,
+               RobState<T, ROB> {
+  static_assert(!ROB || (INS && (AR == 0 || AR == 1) && !SRC && !VAR && !DIV),
+                "Robin walls: the insulated march's substitution sites, unscaled arithmetic, no source, map or faces");
   using S = TbShape<T, NV, K>;
   static constexpr int V = S::V;
   static constexpr int VM = S::VM;
@@ -572,6 +598,24 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, 
         if constexpr (AR == 1) part[e] = fma_t((*rx)[e], de, p);
         else part[e] = p + (*rx)[e] * de;
       }
+    } else if constexpr (ROB) {
+      // (the ghost of the row wall only on the wall row: a wave-uniform branch)
+      const bool swall = (EK & 1) && row == this->wall_hi;  // wave-uniform
+      T south[V];
+      if (swall) {
+#pragma unroll
+        for (int e = 0; e < V; ++e) south[e] = rob_ghost<AR>(this->g.a[kRobS], C[e], this->g.b[kRobS]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < V; ++e) south[e] = Sx[e];
+      }
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        T east = e < V - 1 ? C[e + 1] : eastL;
+        if constexpr ((EK & 2) != 0)
+          east = ((this->wall_e >> e) & 1u) ? rob_ghost<AR>(this->g.a[kRobE], C[e], this->g.b[kRobE]) : east;
+        part[e] = south[e] + east;
+      }
     } else if constexpr (INS) {
       const bool swall = (EK & 1) && row == this->wall_hi;  // wave-uniform
 #pragma unroll
@@ -616,7 +660,12 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, 
     for (int e = 0; e < V; ++e) {
       T west = e > 0 ? C[e - 1] : west0;
       T north = N[e];
-      if constexpr (INS) {
+      if constexpr (ROB) {
+        if ((EK & 2) && e == 0) west = this->wall_w ? rob_ghost<AR>(this->g.a[kRobW], C[0], this->g.b[kRobW]) : west;
+        if (EK & 1) {
+          if (row == this->wall_lo) north = rob_ghost<AR>(this->g.a[kRobN], C[e], this->g.b[kRobN]);  // wave-uniform
+        }
+      } else if constexpr (INS) {
         if ((EK & 2) && e == 0) west = this->wall_w ? C[0] : west;
         if (EK & 1) north = row == this->wall_lo ? C[e] : north;  // wave-uniform
       }
@@ -859,8 +908,10 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, 
 // level adds it with two packed adds (see SrcState).
 // VAR: a map row sits there in the same order and is the Row `re` of the level.
 template <int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false, bool SRC = false,
-          bool VAR = false, bool GAIN = false>
-struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC || VAR>, GainState<float, K, GAIN> {
+          bool VAR = false, bool GAIN = false, bool ROB = false>
+struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC || VAR>, GainState<float, K, GAIN>, RobState<float, ROB> {
+  static_assert(!ROB || (INS && (AR == 0 || AR == 1) && !SRC && !VAR),
+                "Robin walls: the insulated march's substitution sites, unscaled arithmetic, no source or map");
   using F2 = float __attribute__((ext_vector_type(2)));
   using VT = float __attribute__((ext_vector_type(4)));
   using U4 = unsigned int __attribute__((ext_vector_type(4)));
@@ -924,8 +975,29 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC || VAR>, GainState<float
   // part = S + E(C) (first partial sum of the reference order)
   // (row: the row the sum belongs to — INS only: the operands beyond an
   // insulated wall become the centre's, see March)
+  // ROB: the ghost values of a packed pair / one element beyond wall `side` (see RobState)
+  __device__ __forceinline__ F2 ghost2(int side, F2 c) const {
+    const F2 a2 = {this->g.a[side], this->g.a[side]}, b2 = {this->g.b[side], this->g.b[side]};
+    if constexpr (AR == 1) return __builtin_elementwise_fma(a2, c, b2);
+    else return a2 * c + b2;
+  }
+  __device__ __forceinline__ float ghost1(int side, float c) const {
+    return rob_ghost<AR>(this->g.a[side], c, this->g.b[side]);
+  }
   __device__ __forceinline__ Row partial(const Row& S, const Row& C, int32_t row) const {
-    if constexpr (INS) {
+    if constexpr (ROB) {
+      const bool swall = (EK & 1) && row == this->wall_hi;  // wave-uniform
+      Row E{C.b, F2{C.a.y, from_upper(C.a.x)}};             // east of (c0, c2), (c1, c3)
+      if constexpr ((EK & 2) != 0) {  // (wall_e: bit e = column c_e, memory order)
+        E.a.x = (this->wall_e & 1u) ? ghost1(kRobE, C.a.x) : E.a.x;
+        E.b.x = (this->wall_e & 2u) ? ghost1(kRobE, C.b.x) : E.b.x;
+        E.a.y = (this->wall_e & 4u) ? ghost1(kRobE, C.a.y) : E.a.y;
+        E.b.y = (this->wall_e & 8u) ? ghost1(kRobE, C.b.y) : E.b.y;
+      }
+      Row Sx = S;
+      if (swall) Sx = Row{ghost2(kRobS, C.a), ghost2(kRobS, C.b)};  // (only on the wall row)
+      return Row{Sx.a + E.a, Sx.b + E.b};
+    } else if constexpr (INS) {
       const bool swall = (EK & 1) && row == this->wall_hi;  // wave-uniform
       Row E{C.b, F2{C.a.y, from_upper(C.a.x)}};             // east of (c0, c2), (c1, c3)
       if constexpr ((EK & 2) != 0) {  // (wall_e: bit e = column c_e, memory order)
@@ -942,7 +1014,14 @@ struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC || VAR>, GainState<float
   }
   // ((part + N) + W): the reference's sum
   __device__ __forceinline__ Row sum4(const Row& part, const Row& C, const Row& N, int32_t row) const {
-    if constexpr (INS) {
+    if constexpr (ROB) {
+      const bool nwall = (EK & 1) && row == this->wall_lo;  // wave-uniform
+      float w0 = from_lower(C.b.y);                          // west of c0
+      if constexpr ((EK & 2) != 0) w0 = this->wall_w ? ghost1(kRobW, C.a.x) : w0;
+      Row Nx = N;
+      if (nwall) Nx = Row{ghost2(kRobN, C.a), ghost2(kRobN, C.b)};  // (only on the wall row)
+      return Row{(part.a + Nx.a) + F2{w0, C.b.x}, (part.b + Nx.b) + C.a};
+    } else if constexpr (INS) {
       const bool nwall = (EK & 1) && row == this->wall_lo;  // wave-uniform
       float w0 = from_lower(C.b.y);                          // west of c0
       if constexpr ((EK & 2) != 0) w0 = this->wall_w ? C.a.x : w0;
@@ -1203,10 +1282,11 @@ constexpr bool kPackedF32 = false;
 constexpr int kInsRowLo = 1, kInsRowHi = 2, kInsColLo = 4, kInsColHi = 8;
 
 template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, bool PS = false, int CLX = 0,
-          bool INS = false, bool SRC = false, bool VAR = false, bool DIV = false, bool GAIN = false>
+          bool INS = false, bool SRC = false, bool VAR = false, bool DIV = false, bool GAIN = false, bool ROB = false>
 __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r, int64_t strip, int64_t t0,
                                       int64_t t1, int lane, StatAcc* acc = nullptr, int ins = 0,
-                                      const T* qsrc = nullptr, const T* qsrc2 = nullptr, const T* gain = nullptr) {
+                                      const T* qsrc = nullptr, const T* qsrc2 = nullptr, const T* gain = nullptr,
+                                      const RobCoef<T>* rob = nullptr) {
   using S = TbShape<T, NV, K>;
   constexpr int V = S::V;
   constexpr int ES = (int)sizeof(T);
@@ -1220,8 +1300,8 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
   constexpr int CL = CLX > 0 ? (CLX < K ? CLX : K) : (ST ? K : chain_len<T, K>());
   // (DIV: the element-wise march in both dtypes)
   constexpr bool kPacked = kPackedF32<T, NV> && !DIV;
-  using W = typename std::conditional<kPacked, MarchF32<K, EK, RING, AR, ST, CL, INS, SRC, VAR, GAIN>,
-                                      March<T, NV, K, EK, RING, AR, ST, CL, INS, SRC, VAR, DIV, GAIN>>::type;
+  using W = typename std::conditional<kPacked, MarchF32<K, EK, RING, AR, ST, CL, INS, SRC, VAR, GAIN, ROB>,
+                                      March<T, NV, K, EK, RING, AR, ST, CL, INS, SRC, VAR, DIV, GAIN, ROB>>::type;
   W w;
   // row base = column col_lo (= -cpad) of row 0; offsets are relative to it
   w.srow = reinterpret_cast<const char*>(src + a.col_lo);
@@ -1271,6 +1351,7 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
     for (int e = 0; e < V; ++e) me |= ((ins & kInsColHi) && mycol + e == a.ncols - 1) ? (1u << e) : 0u;
     w.wall_e = me;
   }
+  if constexpr (ROB) w.g = *rob;  // the walls' pairs, wave-uniform (the kernel's argument)
   if constexpr (SRC || VAR) {  // the source buffer / the map (qsrc) has the field's layout
     w.qrow = reinterpret_cast<const char*>(qsrc + a.col_lo);
     w.qdelta = w.qrow - w.srow;
@@ -1537,6 +1618,42 @@ __global__ __launch_bounds__(256) void tb_kernel_ins(const T* __restrict__ src, 
   queue_exit(a);
 }
 
+// The general kernel with Robin walls (`g`: the four walls' pairs (a, b), an
+// argument of this kernel only, beside tb_kernel_ins's `ins` — TbArgs and every
+// other kernel stay as they are): tb_kernel_ins's items, kinds and march; an
+// item of kind 1 / 2 / 3 runs the march with the ghost value a * C + b (March
+// ROB) for the operand beyond every wall in `ins` it touches, a kind-0 item the
+// plain march. A wall with (1, -0.0) is an insulated one.
+template <typename T, int NV, int K, int RING, int AR>
+__global__ __launch_bounds__(256) void tb_kernel_rob(const T* __restrict__ src, T* __restrict__ dst, TbArgs a, T r,
+                                                     int ins, RobCoef<T> g) {
+  using S = TbShape<T, NV, K>;
+  const int lane = threadIdx.x & 63;
+  const int64_t wid = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (wid >= a.nwaves) return;  // whole wave exits; no barriers in this kernel
+  int64_t it = wid;
+  int32_t lin = tb_span<kMaxRects>(a, it).lin;
+  while (it < a.nitems) {
+    int64_t strip, t0, t1;
+    if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {
+      it = next_item(a, it);
+      if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;
+      continue;
+    }
+    lin += (int32_t)(t1 - t0);
+    const int64_t c0 = strip * S::U - S::KA;
+    const int ek = (((t0 - K < a.fixed_lo) || (t1 + K > a.fixed_hi)) ? 1 : 0) |
+                   (((c0 < 0) || (c0 + S::W > a.ncols)) ? 2 : 0);
+    switch (ek) {
+      case 0: march<T, NV, K, 0, RING, AR>(src, dst, a, r, strip, t0, t1, lane); break;
+      case 1: march<T, NV, K, 1, RING, AR, false, false, 0, true, false, false, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, ins, nullptr, nullptr, nullptr, &g); break;
+      case 2: march<T, NV, K, 2, RING, AR, false, false, 0, true, false, false, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, ins, nullptr, nullptr, nullptr, &g); break;
+      default: march<T, NV, K, 3, RING, AR, false, false, 0, true, false, false, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, ins, nullptr, nullptr, nullptr, &g); break;
+    }
+  }
+  queue_exit(a);
+}
+
 // The general kernel with a heat source (`q`: the source buffer, in the field's
 // layout, an argument of this kernel only — TbArgs and every other kernel stay
 // as they are): the same items and kinds; every item runs the march with the
@@ -1717,6 +1834,12 @@ template <typename T, int AR>
 void dispatch_ins(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, int ins, hipStream_t s);
 template <typename T, int AR>
 int occupancy_blocks_ins(int k);
+// Robin-wall kernels: general kernel, ring 4, exact / fma (tb_<dtype>_rob[_fma].hip)
+template <typename T, int AR>
+void dispatch_rob(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, int ins, const RobCoef<T>& g,
+                  hipStream_t s);
+template <typename T, int AR>
+int occupancy_blocks_rob(int k);
 // heat-source kernels: general kernel, ring 4, depths 1..kMaxTBSrc (tb_<dtype>_src[_fma].hip)
 template <typename T, int AR>
 void dispatch_src(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, T r, const T* q, hipStream_t s);
@@ -1865,6 +1988,52 @@ int blocks_per_cu_ins() {
     return 1;                                                                                                 \
   }
 
+template <typename T, int K, int AR>
+int blocks_per_cu_rob() {
+  static std::mutex mu;
+  static std::map<int, int> cache;  // device -> blocks/CU
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> g(mu);
+  auto it = cache.find(dev);
+  if (it != cache.end()) return it->second;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tb_kernel_rob<T, 1, K, 4, AR>),
+                                                   256, 0) != hipSuccess ||
+      nb <= 0)
+    nb = 1;
+  cache[dev] = nb;
+  return nb;
+}
+#define H2D_ROB_CASE(T, RING, MAIN, AR, KK)                                                                         \
+  case KK:                                                                                                          \
+    hipLaunchKernelGGL((tb_kernel_rob<T, 1, KK, 4, AR>), dim3(nblocks), dim3(256), 0, s, src, dst, a, r, ins, g); \
+    return;
+#define H2D_ROB_OCC_CASE(T, RING, MAIN, AR, KK) \
+  case KK:                                      \
+    return blocks_per_cu_rob<T, KK, AR>();
+#define H2D_ROB_UNIT(T, AR, DEEP)                                                                             \
+  template <>                                                                                                 \
+  void dispatch_rob<T, AR>(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, int ins,      \
+                           const RobCoef<T>& g, hipStream_t s) {                                              \
+    switch (k) {                                                                                              \
+      H2D_TB_CASES(H2D_ROB_CASE, T, 4, false, AR)                                                             \
+      DEEP(H2D_ROB_CASE, T, 4, false, AR)                                                                     \
+      default:                                                                                                \
+        break;                                                                                                \
+    }                                                                                                         \
+    HEAT2D_REQUIRE(false, "temporal depth not instantiated for the Robin-wall kernel");                       \
+  }                                                                                                           \
+  template <>                                                                                                 \
+  int occupancy_blocks_rob<T, AR>(int k) {                                                                    \
+    switch (k) {                                                                                              \
+      H2D_TB_CASES(H2D_ROB_OCC_CASE, T, 4, false, AR)                                                         \
+      DEEP(H2D_ROB_OCC_CASE, T, 4, false, AR)                                                                 \
+      default:                                                                                                \
+        break;                                                                                                \
+    }                                                                                                         \
+    return 1;                                                                                                 \
+  }
 
 // resident waves (one-wave workgroups) per CU of one tb_kernel_src instance
 template <typename T, int K, int AR>

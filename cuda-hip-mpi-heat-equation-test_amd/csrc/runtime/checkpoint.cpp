@@ -226,8 +226,53 @@ void write_rank(const std::string& dir, const std::string& name, int rank, Solve
   fsync_path(path);
 }
 
+namespace {
+const char* const kRobinKeys[4] = {"x_lo", "x_hi", "y_lo", "y_hi"};
+// " \"robin\": {\"x_lo\": [\"0x1.ap-1\", \"0x1.7ae148p-2\"], ...},\n" ("" without a recorded side)
+std::string robin_json(const Meta& m) {
+  if (!m.robin_sides) return "";
+  std::string o = " \"robin\": {";
+  bool first = true;
+  for (int k = 0; k < 4; ++k) {
+    if (!(m.robin_sides >> k & 1)) continue;
+    char b[128];
+    std::snprintf(b, sizeof(b), "%s\"%s\": [\"%a\", \"%a\"]", first ? "" : ", ", kRobinKeys[k], m.robin[2 * k], m.robin[2 * k + 1]);
+    o += b;
+    first = false;
+  }
+  return o + "},\n";
+}
+// the "robin" object of a meta.json (either writer's layout): every side it names, two quoted hex floats each
+void read_robin(const std::string& js, Meta& m) {
+  size_t p = js.find("\"robin\"");
+  if (p == std::string::npos) return;
+  p = js.find('{', p);
+  HEAT2D_REQUIRE(p != std::string::npos, "malformed meta.json: \"robin\" is no object");
+  const size_t end = js.find('}', p);
+  HEAT2D_REQUIRE(end != std::string::npos, "malformed meta.json: \"robin\" is not closed");
+  const std::string obj = js.substr(p, end - p);
+  for (int k = 0; k < 4; ++k) {
+    size_t q = obj.find(std::string("\"") + kRobinKeys[k] + "\"");
+    if (q == std::string::npos) continue;
+    q = obj.find('[', q);
+    HEAT2D_REQUIRE(q != std::string::npos, "malformed meta.json: a Robin side is no pair");
+    for (int v = 0; v < 2; ++v) {
+      const size_t a = obj.find('"', q + 1);
+      const size_t b = a == std::string::npos ? a : obj.find('"', a + 1);
+      HEAT2D_REQUIRE(b != std::string::npos, "malformed meta.json: a Robin side is no pair of strings");
+      const std::string t = obj.substr(a + 1, b - a - 1);
+      char* e = nullptr;
+      m.robin[2 * k + v] = std::strtod(t.c_str(), &e);
+      HEAT2D_REQUIRE(e && e != t.c_str() && *e == '\0', "malformed meta.json: a Robin value is no number (" + t + ")");
+      q = b;
+    }
+    m.robin_sides |= 1 << k;
+  }
+}
+}  // namespace
+
 void write_meta(const std::string& dir, const std::string& name, const Meta& m) {
-  char buf[1280];
+  char buf[1792];
   std::snprintf(buf, sizeof(buf),
                 "{\n \"format\": \"%s\",\n \"step\": %lld,\n \"nranks\": %d,\n \"dtype\": \"%s\",\n"
                 " \"n_owned\": %lld,\n \"n_input\": %lld,\n \"convention\": \"%s\",\n \"sigma\": %.17g,\n"
@@ -243,7 +288,9 @@ void write_meta(const std::string& dir, const std::string& name, const Meta& m) 
                  // (and the key of the face coefficients only with them)
                  (m.faces_sha256.empty() ? "" : " \"faces_sha256\": \"" + m.faces_sha256 + "\",\n") +
                  // (and the key of the source's gain schedule only with one)
-                 (m.source_gain_sha256.empty() ? "" : " \"source_gain_sha256\": \"" + m.source_gain_sha256 + "\",\n")).c_str());
+                 (m.source_gain_sha256.empty() ? "" : " \"source_gain_sha256\": \"" + m.source_gain_sha256 + "\",\n") +
+                 // (and the key of the Robin walls' pairs only with a Robin axis)
+                 robin_json(m)).c_str());
   write_atomic(join(join(dir, name), "meta.json"), buf);  // + fsync of the step directory (rank files' entries)
   write_atomic(join(dir, "latest"), name + "\n");  // the commit point
   // prune: keep the two newest complete saves, ordered by (step, generation)
@@ -319,8 +366,13 @@ Meta read_meta(const std::string& dir) {
     while (!m.faces_sha256.empty() && (m.faces_sha256.back() == ' ' || m.faces_sha256.back() == '\r')) m.faces_sha256.pop_back();
     if (m.faces_sha256 == "null") m.faces_sha256.clear();
   }
-  auto bc_ok = [](const std::string& v) { return v == "dirichlet" || v == "periodic" || v == "insulated"; };
-  HEAT2D_REQUIRE(bc_ok(m.bc_x) && bc_ok(m.bc_y), dir + ": meta.json: bc_x / bc_y must be dirichlet, periodic or insulated");
+  read_robin(js, m);
+  auto bc_ok = [](const std::string& v) { return v == "dirichlet" || v == "periodic" || v == "insulated" || v == "robin"; };
+  HEAT2D_REQUIRE(bc_ok(m.bc_x) && bc_ok(m.bc_y),
+                 dir + ": meta.json: bc_x / bc_y must be dirichlet, periodic, insulated or robin");
+  for (int k = 0; k < 4; ++k)
+    HEAT2D_REQUIRE((((k < 2 ? m.bc_x : m.bc_y) == "robin") == ((m.robin_sides >> k & 1) != 0)),
+                   dir + ": meta.json: \"robin\" must hold a pair exactly for the sides of the robin axes");
   HEAT2D_REQUIRE(m.nranks >= 1 && m.step >= 0 && m.n_owned >= 1, dir + ": inconsistent meta.json");
   return m;
 }

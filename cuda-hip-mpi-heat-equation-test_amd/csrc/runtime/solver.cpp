@@ -172,6 +172,24 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
     K = std::min<int>(K, kMaxTBDiv);  // the conservative-form kernels' deepest pass
     if (cfg_.arith < 0) cfg_.arith = 0;  // auto: exact
   }
+  HEAT2D_REQUIRE(cfg_.bc_x >= 0 && cfg_.bc_x <= 3 && cfg_.bc_y >= 0 && cfg_.bc_y <= 3,
+                 "bc_x / bc_y must be 0 (dirichlet), 1 (periodic), 2 (insulated) or 3 (robin)");
+  if (cfg_.bc_x == kBcRobinKind || cfg_.bc_y == kBcRobinKind) {
+    // (auto below resolves to fma or exact, never to jacobi)
+    HEAT2D_REQUIRE(cfg_.arith != 2 && cfg_.arith != 3,
+                   "Robin walls have no arith jacobi / fast: their scaled levels would need b scaled per level (use "
+                   "exact, fma or auto)");
+    HEAT2D_REQUIRE(cfg_.engine == 0, "Robin walls need the temporal-blocked engine (engine \"jit\" is Dirichlet only)");
+    HEAT2D_REQUIRE(!cfg_.copy_swap, "Robin walls have no copy-swap mode (Dirichlet only)");
+    for (int i = 0; i < 8; ++i) {
+      const bool used = (i < 4 ? cfg_.bc_x : cfg_.bc_y) == kBcRobinKind;
+      // the run's dtype; a side that is not Robin: the insulated wall's pair
+      const double v = !used ? ((i & 1) ? -0.0 : 1.0) : (cfg_.dtype == 0 ? (double)(float)cfg_.robin[i] : cfg_.robin[i]);
+      HEAT2D_REQUIRE(std::isfinite(v), "the Robin pairs (a, b) must be finite in the run's dtype");
+      cfg_.robin[i] = v;
+    }
+    K = std::min<int>(K, kMaxTBRob);  // the Robin kernels' deepest pass
+  }
   if (cfg_.arith < 0) {
     // auto: the contracted form when it is bitwise identical to the reference
     // rounding — r an exact power of two (sigma = 0.25 in every shipped
@@ -183,12 +201,10 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
                  "arith must be 0 (reference rounding), 1 (fma), 2 (jacobi, r = 1/4), 3 (fast) or -1 (auto)");
   HEAT2D_REQUIRE(cfg_.arith != 2 || cfg_.r == 0.25, "arith 2 (jacobi) needs r == 1/4 exactly (sigma = 0.25)");
   HEAT2D_REQUIRE(cfg_.arith != 3 || cfg_.r > 0, "arith 3 (fast) needs r > 0");
-  HEAT2D_REQUIRE(cfg_.bc_x >= 0 && cfg_.bc_x <= 2 && cfg_.bc_y >= 0 && cfg_.bc_y <= 2,
-                 "bc_x / bc_y must be 0 (dirichlet), 1 (periodic) or 2 (insulated)");
   bc_ = config_bc(cfg_);
   if (bc_) {
     const bool ins = (bc_ & (kern::kBcInsulatedX | kern::kBcInsulatedY)) != 0;
-    const std::string what = ins ? "insulated boundaries" : "periodic boundaries";
+    const std::string what = (bc_ & kern::kBcRobin) ? "Robin walls" : ins ? "insulated boundaries" : "periodic boundaries";
     HEAT2D_REQUIRE(cfg_.engine == 0, what + " need the temporal-blocked engine (engine \"jit\" is Dirichlet only)");
     HEAT2D_REQUIRE(!cfg_.copy_swap, what + " have no copy-swap mode (Dirichlet only)");
     HEAT2D_REQUIRE(cfg_.slab_rows_global == 0, what + ": no middle-slab rehearsal (slab_rows_global)");
@@ -387,6 +403,20 @@ void Solver::wrap_cols_all(void* field) {
     if (hip_) kern::launch_wrap_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo, s_compute_);
     else cpu::wrap_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo);
   }
+  if (bc_ & kern::kBcRobin) {  // the ghost values: the wall rows, then the columns over every row (the golden's order)
+    double px[4], py[4];
+    kern::wall_pairs(bc_, true, cfg_.robin, px);
+    kern::wall_pairs(bc_, false, cfg_.robin, py);
+    if (bc_ & kern::kBcWallX) {
+      if (hip_) kern::launch_rob_rows(dtype(), field, L_, true, true, px, cfg_.arith, s_compute_);
+      else cpu::rob_rows(dtype(), field, L_, true, true, px, cfg_.arith);
+    }
+    if (bc_ & kern::kBcWallY) {
+      if (hip_) kern::launch_rob_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo, py, cfg_.arith, s_compute_);
+      else cpu::rob_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo, py, cfg_.arith);
+    }
+    return;
+  }
   if (cfg_.bc_y == kBcInsulated) {
     if (hip_) kern::launch_ins_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo, s_compute_);
     else cpu::ins_cols(dtype(), field, L_, -L_.halo, L_.nrows + L_.halo);
@@ -400,16 +430,16 @@ void Solver::wrap_cols_all(void* field) {
 bool Solver::pipe_ok(int k) const {
   // (nor with a heat source: the source kernel is the one-wave general one)
   // (nor with a diffusivity map, for the same reason)
-  return kern::pipe_available(dtype(), k, cfg_.arith) && !(bc_ & kern::kBcInsulatedY) && !cfg_.source && !cfg_.rmap &&
+  return kern::pipe_available(dtype(), k, cfg_.arith) && !(bc_ & kern::kBcWallY) && !cfg_.source && !cfg_.rmap &&
          !cfg_.faces;  // (nor with face coefficients)
 }
 
 void Solver::launch_tb(const void* src, void* dst, int64_t rb, int64_t re, int k) {
   if (re <= rb) return;
   if (hip_)
-    kern::launch_tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, s_compute_, cfg_.tile_rows, compute_cus_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, s_compute_, cfg_.tile_rows, compute_cus_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
   else
-    cpu::tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    cpu::tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
 }
 
 void Solver::exchange_on(void* field, int64_t k, hipStream_t s) {
@@ -422,9 +452,14 @@ void Solver::exchange_on(void* field, int64_t k, hipStream_t s) {
       else cpu::wrap_cols(dtype(), field, L_, r0, r0 + k);
     }
   }
-  if (cfg_.bc_y == kBcInsulated && !tr_->whole_rows()) {  // ... nor their frame columns' images
+  if ((bc_ & kern::kBcWallY) && !tr_->whole_rows()) {  // ... nor their frame columns' images
+    double py[4];
+    kern::wall_pairs(bc_, false, cfg_.robin, py);
     for (int64_t r0 : {-k, L_.nrows}) {
-      if (hip_) kern::launch_ins_cols(dtype(), field, L_, r0, r0 + k, s);
+      if (bc_ & kern::kBcRobin) {
+        if (hip_) kern::launch_rob_cols(dtype(), field, L_, r0, r0 + k, py, cfg_.arith, s);
+        else cpu::rob_cols(dtype(), field, L_, r0, r0 + k, py, cfg_.arith);
+      } else if (hip_) kern::launch_ins_cols(dtype(), field, L_, r0, r0 + k, s);
       else cpu::ins_cols(dtype(), field, L_, r0, r0 + k);
     }
   }
@@ -537,7 +572,7 @@ void Solver::cycle_finish() {
     if (pe) H2D_HIP(hipEventRecord(pe->ev[5], s_comm_));
     if (pend_frame_ >= 0) {  // the edge rank's frame-side band (launch_overlap), after the exchange
       kern::launch_edge_rect(dtype(), buf_[cur_], dst, L_, split_plan_banded(pend_k_, pend_frame_b_), pend_frame_, cfg_.r,
-                             s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+                             s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
       // the next cycle's compute-stream work waits for it (and so for the
       // exchange ahead of it); ev_bnd_, posted to the transport, is left alone
       H2D_HIP(hipEventRecord(ev_frame_, s_comm_));
@@ -803,8 +838,8 @@ void Solver::trial_cycle(const kern::SplitPlan& c) {
   last_k_ = 0;  // the other buffer no longer holds T_{n-1}: stats(residual) reports NaN
   if (c.valid == 3) {  // edge-first: both parts in order on the compute stream
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
-    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain());
-    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
     return;
@@ -812,15 +847,15 @@ void Solver::trial_cycle(const kern::SplitPlan& c) {
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
   H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));
   if (c.flags & kern::kPlanLead) {  // lead: the band launch issued first
-    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain());
-    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
     return;
   }
-  kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+  kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
   H2D_HIP(hipEventRecord(ev_int_, s_compute_));
-  kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+  kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
   H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
 }
 
@@ -1225,9 +1260,9 @@ void Solver::launch_overlap(int k, int64_t B) {
     H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));     // main part c-1
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_comm_));
     launch_cycle_aux(k, s_comm_);
-    kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_comm_));
@@ -1244,12 +1279,12 @@ void Solver::launch_overlap(int k, int64_t B) {
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_comm_, 0));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_compute_));
     launch_cycle_aux(k, s_compute_);
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
     if (tr_->exchanges()) tr_->post(dst, L_, ev_bnd_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     pend_ = Pending::EdgeFirst;
@@ -1261,23 +1296,23 @@ void Solver::launch_overlap(int k, int64_t B) {
   launch_cycle_aux(k, s_comm_);  // (ahead of the band launch in every order below)
   if (lead) {
     // lead: the band launch first (comm stream), then the interior beside it
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
   } else if (sp.valid) {
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
   } else {  // slab too thin / narrow to split: all of it beside the exchange
     if (pe) {
       H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
       H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     }
-    kern::launch_tb(dtype(), src, dst, L_, 0, L_.nrows, k, cfg_.r, s_comm_, 0, 0, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain());
+    kern::launch_tb(dtype(), src, dst, L_, 0, L_.nrows, k, cfg_.r, s_comm_, 0, 0, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
   }
   if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_comm_));
   H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
@@ -1983,7 +2018,7 @@ void Solver::step_stats(int64_t n, double out[6]) {
   // (periodic y: the fused-statistics march would count its ghost columns;
   // insulated axes: the fused-statistics kernel has no insulated edges)
   // (a heat source: the fused-statistics kernel has no source term)
-  if (!hip_ || jit_ || cfg_.copy_swap || cfg_.bc_y || cfg_.bc_x == kBcInsulated || cfg_.source || cfg_.rmap || cfg_.faces) {
+  if (!hip_ || jit_ || cfg_.copy_swap || cfg_.bc_y || cfg_.bc_x == kBcInsulated || cfg_.bc_x == kBcRobinKind || cfg_.source || cfg_.rmap || cfg_.faces) {
     step(n - 1);
     step(1);
     stats(out, true);
@@ -2438,7 +2473,7 @@ void Solver::launch_cycle_aux(int k, hipStream_t stream) {
   a.P = (int64_t)probe_idx_.size();
   a.r = cfg_.r;
   a.k = k;
-  kern::probe_bounds(a, L_, bc_);
+  kern::probe_bounds(a, L_, bc_, robin());
   if (hip_) {
     a.pts = d_probe_pts_;
     a.base = d_probe_base_;

@@ -211,6 +211,51 @@ def faces_from_k(problem: Problem, k_xy, mean: str = "harmonic") -> tuple:
     return rx, ry
 
 
+def robin_from_h(problem: Problem, h_over_k: float, t_inf: float) -> tuple:
+    """The Robin pair (a, b) of a convective wall, -k du/dn = h (u_wall - t_inf)
+    with the wall value u_wall = (C + G) / 2 half a cell outside the adjacent
+    owned point C and the outward derivative (G - C) / dx: with beta =
+    h_over_k * dx (dx: the problem's grid spacing), a = (2 - beta) / (2 + beta)
+    and b = 2 beta t_inf / (2 + beta). Computed in float64. beta = 0 is the
+    insulated wall (1, 0); beta -> inf approaches the wall at t_inf, (-1, 2 t_inf)."""
+    beta = np.float64(h_over_k) * np.float64(problem.delta)
+    return float((2.0 - beta) / (2.0 + beta)), float(2.0 * beta * np.float64(t_inf) / (2.0 + beta))
+
+
+def robin_from_flux(problem: Problem, q_over_k: float) -> tuple:
+    """The Robin pair of a prescribed inward heat flux q through the wall,
+    k du/dn = q: G = C + (q / k) dx, i.e. (1.0, q_over_k * dx), in float64."""
+    return 1.0, float(np.float64(q_over_k) * np.float64(problem.delta))
+
+
+def robin_wall_temperature(t_wall: float) -> tuple:
+    """The Robin pair of a fixed temperature AT the wall (half a cell outside
+    the adjacent owned point, not at the frame point): (C + G) / 2 = t_wall,
+    i.e. (-1.0, 2 * t_wall), in float64."""
+    return -1.0, float(2.0 * np.float64(t_wall))
+
+
+def _robin_info(h, bc_x: str, bc_y: str) -> dict:
+    """info()["robin"]: the pairs the native solver runs (converted to the
+    run's dtype) for the sides of its Robin axes, and the depth clamp of the
+    Robin kernels (0 without a Robin axis)."""
+    v, m = (C.c_double * 8)(), C.c_int32()
+    N.call("heat2d_solver_robin", h, v, C.byref(m))
+    sides = [s for ax, bc in (("x", bc_x), ("y", bc_y)) if bc == "robin" for s in (ax + "_lo", ax + "_hi")]
+    out = {s: (float(v[2 * N.ROBIN_SIDES.index(s)]), float(v[2 * N.ROBIN_SIDES.index(s) + 1])) for s in sides}
+    out["max_tb"] = int(m.value)
+    return out
+
+
+def _set_robin(cfg, robin, bc_x: str, bc_y: str, np_dtype) -> dict:
+    """Check ``robin=`` against the axes (ValueError: a missing or surplus side,
+    an entry that is not finite) and put the converted pairs into the config."""
+    arr, pairs = N.robin_array(robin, bc_x, bc_y, np_dtype)
+    for i in range(8):
+        cfg.robin[i] = arr[i]
+    return pairs
+
+
 def _arith(h) -> int:
     """The arithmetic form (ops._native.ARITH code) a native solver runs: "auto" resolved."""
     v = C.c_int32()
@@ -275,6 +320,23 @@ class HeatSolver:
             on more than one rank periodic x runs on the loopback, host-thread
             and torch.distributed (host-staged) transports (insulated x: every
             transport); "insulated" not with arith "fast".
+            "robin": a Robin (convective) wall in the insulated geometry, with
+            ``robin=`` (below).
+        robin: ``{"x_lo": (a, b), "x_hi": (a, b), "y_lo": (a, b), "y_hi": (a, b)}``
+            for exactly the sides of the axes that are "robin" (x_lo: the wall
+            before the first owned row, x_hi: after the last; y_*: columns); a
+            missing or surplus key raises ValueError. The value beyond a wall
+            is the ghost G = a * C + b of the adjacent owned point C (the
+            product rounded, then the add; arith "fma": fma(a, C, b)), formed
+            at every fused level, so K fused levels have the bits of K single
+            steps of models.reference.ftcs(robin=) at any depth, plan and rank
+            count. a and b finite, converted to the run's dtype
+            (:func:`robin_from_h`, :func:`robin_from_flux`,
+            :func:`robin_wall_temperature`); (1, -0.0) is the insulated wall,
+            bit for bit. arith "exact" / "fma" ("auto": fma when r is a power
+            of two, else exact — never jacobi), engine "tb", no copy_swap, no
+            source / rmap / faces; info()["robin"] holds the converted pairs
+            and the depth clamp.
         source: a heat source, u_t = nu lap(u) + f: the GLOBAL frame-inclusive
             array (rows + 2) x (n + 2) of the per-step increment S = dt * f (the
             solver does no scaling; converted to the field's dtype; its frame
@@ -349,7 +411,7 @@ class HeatSolver:
                  comm_cus: int = 0, autotune: int = -1, engine: str = "tb", arith: str = "auto",
                  slab_row0: Optional[int] = None, edge_shift: int = 0, bc_x: str = "dirichlet",
                  bc_y: str = "dirichlet", source=None, rmap=None, faces=None, probes=None,
-                 probe_steps: Optional[int] = None, source_gain=None):
+                 probe_steps: Optional[int] = None, source_gain=None, robin=None):
         self.problem = problem
         self.edge_shift = 0 if bc_x == "periodic" else int(edge_shift)  # (periodic x: no edge slabs)
         self.bc_x, self.bc_y = bc_x, bc_y
@@ -387,6 +449,7 @@ class HeatSolver:
         cfg.edge_shift = self.edge_shift
         cfg.bc_x = N.bc_code(bc_x, "bc_x")
         cfg.bc_y = N.bc_code(bc_y, "bc_y")
+        self.robin = _set_robin(cfg, robin, bc_x, bc_y, self.np_dtype)  # the converted pairs of the Robin sides
         if engine not in ("tb", "jit"):
             raise ValueError("engine must be 'tb' (temporal-blocked kernels) or 'jit' (hipRTC, one step per launch)")
         cfg.engine = 1 if engine == "jit" else 0
@@ -555,7 +618,8 @@ class HeatSolver:
         return {"tb": tb.value, "band": band.value, "steps": steps.value, "field": field.value,
                 "stream": stream.value, "backend": self.backend, "transport": self.transport.name,
                 "arith": _arith(self._h),  # the resolved code: 0 exact, 1 fma, 2 jacobi, 3 fast
-                "bc_x": self._bc()[0], "bc_y": self._bc()[1],  # "dirichlet" | "periodic" | "insulated", as the native solver runs
+                "bc_x": self._bc()[0], "bc_y": self._bc()[1],  # "dirichlet" | "periodic" | "insulated" | "robin", as the native solver runs
+                "robin": _robin_info(self._h, *self._bc()),  # the converted pairs of the Robin sides, "max_tb"
                 "source": _source_info(self._h),
                 "source_gain": _gain_info(self._h),  # {"set", "length", "position"}
                 "rmap": _rmap_info(self._h),
@@ -721,7 +785,7 @@ class HeatSolver:
         rows -1 .. nrows (the global frame rows on the first / last rank, else
         the neighbours' rows) and columns -1 .. ncols. On a periodic axis the
         frame entries are wrap images of the owned points, on an insulated one
-        images of the adjacent owned point."""
+        images of the adjacent owned point, on a Robin one its ghost values."""
         out = np.empty((self.nrows + 2, self.ncols + 2), dtype=self.np_dtype)
         N.call("heat2d_solver_download_region", self._h, -1, self.nrows + 1, -1, self.ncols + 1,
                out.ctypes.data_as(C.c_void_p), self.ncols + 2)
@@ -731,8 +795,8 @@ class HeatSolver:
         """Set this rank's owned rows (collective: followed by a halo exchange).
         ``arr``: the owned points (nrows, ncols), or the frame-inclusive local
         field (nrows + 2, ncols + 2) — then the frame lines of a Dirichlet axis
-        are set too, and the entries on a periodic or insulated axis are ignored
-        (they become wrap / edge images of the owned points)."""
+        are set too, and the entries on a periodic, insulated or Robin axis are
+        ignored (they become wrap / edge images / ghost values of the owned points)."""
         a = np.ascontiguousarray(arr, dtype=self.np_dtype)
         if a.shape == (self.nrows + 2, self.ncols + 2):
             N.call("heat2d_solver_upload_field", self._h, a.ctypes.data_as(C.c_void_p), self.ncols + 2)
@@ -799,7 +863,7 @@ class LoopbackGroup:
                  tb: int = 0, tile_rows: int = 0, device: Optional[int] = None, arith: str = "auto",
                  overlap: bool = True, autotune: int = -1, comm_cus: int = 0, edge_shift: int = 0,
                  bc_x: str = "dirichlet", bc_y: str = "dirichlet", source=None, rmap=None, faces=None,
-                 probes=None, probe_steps: Optional[int] = None, source_gain=None):
+                 probes=None, probe_steps: Optional[int] = None, source_gain=None, robin=None):
         self.problem = problem
         self.bc_x, self.bc_y = bc_x, bc_y
         self.backend = resolve_backend(backend)
@@ -823,6 +887,7 @@ class LoopbackGroup:
         cfg.edge_shift = int(edge_shift)
         cfg.bc_x = N.bc_code(bc_x, "bc_x")
         cfg.bc_y = N.bc_code(bc_y, "bc_y")
+        self.robin = _set_robin(cfg, robin, bc_x, bc_y, NP_DTYPES[self.dtype])  # Robin walls (HeatSolver robin=)
         cfg.source = int(source is not None)  # a heat source (HeatSolver source=): each member slices its rows
         cfg.rmap = int(rmap is not None)  # a diffusivity map (HeatSolver rmap=): likewise
         cfg.faces = int(faces is not None)  # face coefficients (HeatSolver faces=): likewise
@@ -966,6 +1031,10 @@ class LoopbackGroup:
 
     def cycle_hist(self, i: int, reset: bool = False) -> dict:
         return _cycle_hist(self._member(i), reset)
+
+    def robin_info(self, i: int = 0) -> dict:
+        """info()["robin"] of member i."""
+        return _robin_info(self._member(i), self.bc_x, self.bc_y)
 
     def arith_code(self, i: int) -> int:
         """The arithmetic form member i runs ("auto" resolved; as HeatSolver.info()["arith"])."""

@@ -47,9 +47,63 @@ def initial_field(problem: Problem, dtype=np.float64) -> np.ndarray:
 
 
 _PAD_MODE = {"periodic": "wrap", "insulated": "edge"}
+_ROBIN_SIDES = {"bc_x": ("x_lo", "x_hi"), "bc_y": ("y_lo", "y_hi")}
 
 
-def wrap_frame(T: np.ndarray, bc_x: str = "dirichlet", bc_y: str = "dirichlet") -> np.ndarray:
+def robin_pairs(robin, bc_x: str, bc_y: str, dtype) -> dict:
+    """The (a, b) pairs of the Robin sides, checked and converted to ``dtype``:
+    ``robin`` maps exactly the sides of the axes that are "robin" ("x_lo" /
+    "x_hi": the wall before the first / after the last owned row, "y_lo" /
+    "y_hi": the same for columns) to a finite pair. A missing or surplus key,
+    or an entry that is not finite, raises ValueError."""
+    want = [k for name, bc in (("bc_x", bc_x), ("bc_y", bc_y)) if bc == "robin" for k in _ROBIN_SIDES[name]]
+    have = {} if robin is None else dict(robin)
+    missing = [k for k in want if k not in have]
+    surplus = sorted(k for k in have if k not in want)
+    if missing:
+        raise ValueError(f"robin= lacks the pair of {', '.join(missing)} (every side of a \"robin\" axis needs one)")
+    if surplus:
+        raise ValueError(f"robin= has a pair for {', '.join(map(str, surplus))}, which is no side of a \"robin\" axis")
+    t = np.dtype(dtype).type
+    out = {}
+    for k in want:
+        try:
+            a, b = have[k]
+        except (TypeError, ValueError):
+            raise ValueError(f"robin[{k!r}] must be a pair (a, b)") from None
+        with np.errstate(over="ignore"):
+            a, b = t(a), t(b)
+        if not (np.isfinite(a) and np.isfinite(b)):
+            raise ValueError(f"robin[{k!r}] must be finite in the run's dtype, got ({a}, {b})")
+        out[k] = (a, b)
+    return out
+
+
+def robin_ghost(C: np.ndarray, a, b, arith: str = "exact") -> np.ndarray:
+    """The value beyond a Robin wall from the adjacent owned points C:
+    exact: a * C + b (the product rounded, then the add); fma: one rounding."""
+    t = C.dtype.type
+    if arith == "fma":
+        a, b = t(a), t(b)
+        g = fma(np.broadcast_to(a, C.shape), C, np.broadcast_to(b, C.shape))
+        # :func:`fma` emulates the normal range and returns +0.0 for every zero; a hardware fma returns -0.0
+        # where the product and the addend are both negative zeros (so that (1, -0.0) keeps a -0.0)
+        neg = (g == 0) & (b == 0) & np.signbit(b) & ((C == 0) | (a == 0)) & (np.signbit(C) ^ np.signbit(a))
+        return np.where(neg, t(-0.0), g).astype(C.dtype, copy=False)
+    if arith != "exact":
+        raise ValueError("a Robin wall needs arith 'exact' or 'fma'")
+    return t(a) * C + t(b)
+
+
+def _pad_axis(out: np.ndarray, axis: int, bc: str, lo, hi, arith: str) -> np.ndarray:
+    if bc != "robin":
+        return np.pad(out, ((1, 1), (0, 0)) if axis == 0 else ((0, 0), (1, 1)), mode=_PAD_MODE[bc])
+    first, last = (out[:1], out[-1:]) if axis == 0 else (out[:, :1], out[:, -1:])
+    return np.concatenate([robin_ghost(first, *lo, arith), out, robin_ghost(last, *hi, arith)], axis=axis)
+
+
+def wrap_frame(T: np.ndarray, bc_x: str = "dirichlet", bc_y: str = "dirichlet", robin=None,
+               arith: str = "exact") -> np.ndarray:
     """The frame-inclusive field with its frame entries on periodic axes
     replaced by wrap images of the owned points (``np.pad(mode="wrap")``) and on
     insulated axes by images of the adjacent owned point (``mode="edge"``: the
@@ -57,18 +111,24 @@ def wrap_frame(T: np.ndarray, bc_x: str = "dirichlet", bc_y: str = "dirichlet") 
     T[n+1] = T[n]). With only y periodic / insulated the Dirichlet frame rows
     get images at their ends too: the point (0, -1) reads (-1, -1) / (0, 0).
     x is padded first, then y over the padded rows. Dirichlet on both axes: T
-    itself."""
+    itself.
+    "robin" (with ``robin=``, :func:`robin_pairs`): the insulated geometry with
+    the affine ghost value G = a * C + b of the adjacent owned point C in place
+    of its image, formed in the form ``arith`` names (:func:`robin_ghost`);
+    x first, then y over the filled rows, so the corner entries are the y ghost
+    of the x ghost (no owned point reads them)."""
     for name, bc in (("bc_x", bc_x), ("bc_y", bc_y)):
-        if bc not in ("dirichlet", "periodic", "insulated"):
-            raise ValueError(f"{name} must be 'dirichlet', 'periodic' or 'insulated', got {bc!r}")
+        if bc not in ("dirichlet", "periodic", "insulated", "robin"):
+            raise ValueError(f"{name} must be 'dirichlet', 'periodic', 'insulated' or 'robin', got {bc!r}")
+    rb = robin_pairs(robin, bc_x, bc_y, T.dtype)
     px, py = bc_x != "dirichlet", bc_y != "dirichlet"
     if not (px or py):
         return T
     out = T[(1 if px else 0):(-1 if px else None), (1 if py else 0):(-1 if py else None)]
     if px:
-        out = np.pad(out, ((1, 1), (0, 0)), mode=_PAD_MODE[bc_x])
+        out = _pad_axis(out, 0, bc_x, rb.get("x_lo"), rb.get("x_hi"), arith)
     if py:
-        out = np.pad(out, ((0, 0), (1, 1)), mode=_PAD_MODE[bc_y])
+        out = _pad_axis(out, 1, bc_y, rb.get("y_lo"), rb.get("y_hi"), arith)
     return out
 
 
@@ -213,7 +273,8 @@ def _ftcs_step_faces(T: np.ndarray, arith: str, faces) -> np.ndarray:
 
 
 def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
-              source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None, gain=None) -> np.ndarray:
+              source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None, gain=None,
+              robin=None) -> np.ndarray:
     """One FTCS step of a frame-inclusive field. On a Dirichlet axis the frame
     is kept fixed; on a periodic or insulated one it is refreshed from the
     owned points before the step (:func:`wrap_frame`) — the update and its
@@ -234,7 +295,15 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
     "fma", no source, no rmap): the conservative form (:func:`_ftcs_step_faces`);
     ``r`` is then not used. None: today's function.
     gain (with source=): this step's gain of a time-dependent source
-    (:func:`_ftcs_step_source`). None: the source as it is."""
+    (:func:`_ftcs_step_source`). None: the source as it is.
+    robin (the pairs of the "robin" axes, :func:`robin_pairs`; arith "exact" or
+    "fma"): before the step the frame entry next to an owned point C on a Robin
+    side is set to the ghost value a * C + b ("fma": fma(a, C, b)), then the
+    unchanged update runs — with a Robin axis "fma" is the contracted update
+    with a single rounding, fma(r, fma(-4, C, sum), C), as with a source."""
+    has_robin = bc_x == "robin" or bc_y == "robin"
+    if has_robin and arith not in ("exact", "fma"):
+        raise ValueError("a Robin wall needs arith 'exact' or 'fma' (the scaled levels of jacobi / fast would need b scaled per level)")
     if gain is not None and source is None:
         raise ValueError("gain= scales a heat source: pass source=")
     if faces is not None:
@@ -255,7 +324,7 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
         if bc_x != "dirichlet" or bc_y != "dirichlet":
             raise ValueError("a heat source needs Dirichlet boundaries on both axes")
         return _ftcs_step_source(T, r, arith, source, gain)
-    T = wrap_frame(T, bc_x, bc_y)
+    T = wrap_frame(T, bc_x, bc_y, robin, arith if has_robin else "exact")
     r = T.dtype.type(r)
     four = T.dtype.type(4)
     c = T[1:-1, 1:-1]
@@ -268,6 +337,9 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
         if r != 0.25:
             raise ValueError("arith 'jacobi' needs r == 1/4")
         out[1:-1, 1:-1] = r * (((south + east) + north) + west)
+    elif has_robin and arith == "fma":
+        total = ((south + east) + north) + west
+        out[1:-1, 1:-1] = fma(np.broadcast_to(r, c.shape), fma(np.broadcast_to(-four, c.shape), c, total), c)
     else:
         out[1:-1, 1:-1] = c + r * ((((south + east) + north) + west) - four * c)
     return out
@@ -276,9 +348,11 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
 def ftcs(problem: Problem, nsteps: int | None = None, dtype=np.float64, T0: np.ndarray | None = None,
          arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
          source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None,
-         source_gain=None, gain_start: int = 0) -> np.ndarray:
+         source_gain=None, gain_start: int = 0, robin=None) -> np.ndarray:
     """Run FTCS; returns the frame-inclusive field (frame entries on periodic
-    / insulated axes: wrap / edge images of the returned owned points).
+    / insulated axes: wrap / edge images of the returned owned points; on Robin
+    axes their ghost values).
+    robin: the pairs of the "robin" axes (:func:`ftcs_step`).
     source: a heat source added at every step (:func:`ftcs_step`).
     rmap: a diffusivity map in place of problem.r (:func:`ftcs_step`).
     faces: (RX, RY) per-face diffusion numbers, the conservative form (:func:`ftcs_step`).
@@ -304,9 +378,10 @@ def ftcs(problem: Problem, nsteps: int | None = None, dtype=np.float64, T0: np.n
         for _ in range(n):
             T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source)
         return T
+    has_robin = bc_x == "robin" or bc_y == "robin"
     for _ in range(n):
-        T = ftcs_step(T, problem.r, arith, bc_x, bc_y)
-    return wrap_frame(T, bc_x, bc_y)
+        T = ftcs_step(T, problem.r, arith, bc_x, bc_y, robin=robin)
+    return wrap_frame(T, bc_x, bc_y, robin, arith if has_robin else "exact")
 
 
 def _gain_array(source_gain, dtype, source, start: int, nsteps: int) -> np.ndarray:
@@ -327,7 +402,7 @@ def _gain_array(source_gain, dtype, source, start: int, nsteps: int) -> np.ndarr
 def probe_history(problem: Problem, nsteps: int, probes, dtype=np.float64, T0: np.ndarray | None = None,
                   arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
                   source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None,
-                  source_gain=None, gain_start: int = 0) -> np.ndarray:
+                  source_gain=None, gain_start: int = 0, robin=None) -> np.ndarray:
     """The golden of the solver's probe points: the (nsteps, P) array whose row
     q holds the values :func:`ftcs_step` leaves at ``probes`` after step q + 1.
     ``probes``: P owned points (i, j) in frame-inclusive indices, 1 <= i, j <= n,
@@ -346,7 +421,7 @@ def probe_history(problem: Problem, nsteps: int, probes, dtype=np.float64, T0: n
     G = None if source_gain is None else _gain_array(source_gain, T.dtype, source, gain_start, nsteps)
     for q in range(nsteps):
         T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source, rmap, faces,
-                      gain=None if G is None else G[gain_start + q])
+                      gain=None if G is None else G[gain_start + q], robin=robin)
         H[q] = T[p[:, 0], p[:, 1]]
     return H
 

@@ -43,15 +43,32 @@ def arith_code(arith: str, r: float) -> int:
 BACKEND_HIP, BACKEND_CPU = 0, 1
 # boundary condition of an axis (Config.bc_x / bc_y); the raw ops take the bit
 # set BC_PERIODIC_X | BC_PERIODIC_Y | BC_INSULATED_X | BC_INSULATED_Y (kernels.hpp)
-BC = {"dirichlet": 0, "periodic": 1, "insulated": 2}
+BC = {"dirichlet": 0, "periodic": 1, "insulated": 2, "robin": 3}
 BC_NAMES = {v: k for k, v in BC.items()}
-BC_PERIODIC_X, BC_PERIODIC_Y, BC_INSULATED_X, BC_INSULATED_Y = 1, 2, 4, 8
+BC_PERIODIC_X, BC_PERIODIC_Y, BC_INSULATED_X, BC_INSULATED_Y, BC_ROBIN_X, BC_ROBIN_Y = 1, 2, 4, 8, 16, 32
+# the sides of the Robin pairs in Config.robin / the raw ops' array: (a, b) each
+ROBIN_SIDES = ("x_lo", "x_hi", "y_lo", "y_hi")
 
 
 def bc_bits(bc_x: str, bc_y: str) -> int:
     """The raw ops' bit set of a pair of axis names."""
     x, y = bc_code(bc_x, "bc_x"), bc_code(bc_y, "bc_y")
-    return ((BC_PERIODIC_X, BC_INSULATED_X)[x - 1] if x else 0) | ((BC_PERIODIC_Y, BC_INSULATED_Y)[y - 1] if y else 0)
+    return (((BC_PERIODIC_X, BC_INSULATED_X, BC_ROBIN_X)[x - 1] if x else 0) |
+            ((BC_PERIODIC_Y, BC_INSULATED_Y, BC_ROBIN_Y)[y - 1] if y else 0))
+
+
+def robin_array(robin, bc_x: str, bc_y: str, np_dtype):
+    """The 8 doubles the native side takes for ``robin=``: the pairs of the sides
+    of the "robin" axes, checked (exactly those keys, finite) and converted to
+    the run's dtype (models.reference.robin_pairs); (1, -0.0), the insulated
+    wall, on every other side. Returns (array, {side: (a, b)} of the converted pairs)."""
+    from ..models.reference import robin_pairs
+    pairs = robin_pairs(robin, bc_x, bc_y, np_dtype)
+    arr = (C.c_double * 8)(*([1.0, -0.0] * 4))
+    for i, side in enumerate(ROBIN_SIDES):
+        if side in pairs:
+            arr[2 * i], arr[2 * i + 1] = float(pairs[side][0]), float(pairs[side][1])
+    return arr, {k: (float(a), float(b)) for k, (a, b) in pairs.items()}
 
 
 def bc_code(name: str, what: str = "bc") -> int:
@@ -102,6 +119,7 @@ class Config(C.Structure):
         ("source", C.c_int32),  # 1: the solver carries a heat source
         ("rmap", C.c_int32),  # 1: the solver carries a diffusivity map
         ("faces", C.c_int32), ("pad1", C.c_int32),  # faces = 1: the solver carries per-face diffusion numbers
+        ("robin", C.c_double * 8),  # the Robin walls' pairs: x_lo a, b, x_hi a, b, y_lo a, b, y_hi a, b
     ]
 
 
@@ -161,6 +179,14 @@ _SIGS = {
     "heat2d_solver_plans_made": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "heat2d_tb": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, _P, _I64, C.c_int]),
     "heat2d_tb_bc": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, _P, _I64, C.c_int, C.c_int]),
+    "heat2d_tb_rob": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, _P, _I64, C.c_int, C.c_int,
+                                C.POINTER(C.c_double)]),
+    "heat2d_cpu_tb_rob": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_double, C.c_int, C.c_int,
+                                    C.POINTER(C.c_double)]),
+    "heat2d_max_tb_rob": (C.c_int, []),
+    "heat2d_probe_cone_rob": (C.c_int, [C.c_int, _P, _LP, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), _P,
+                                        _I64, _P, _P, C.c_int]),
+    "heat2d_solver_robin": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "heat2d_wrap_cols": (C.c_int, [C.c_int, _P, _LP, _I64, _I64, _P, C.c_int]),
     "heat2d_wrap_rows": (C.c_int, [C.c_int, _P, _LP, _I64, _P, C.c_int]),
     "heat2d_init_field": (C.c_int, [C.c_int, _P, _LP, C.POINTER(IcParams), _P, _P, _P]),
@@ -400,6 +426,11 @@ def plan_cache_path() -> str:
 
 def max_tb() -> int:
     return int(lib().heat2d_max_tb())
+
+
+def max_tb_rob() -> int:
+    """Deepest pass of the Robin-wall kernels (common.hpp kMaxTBRob)."""
+    return int(lib().heat2d_max_tb_rob())
 
 
 def device_count() -> int:

@@ -88,7 +88,7 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
             rows: Optional[tuple[int, int]] = None, tile_rows: int = 0, arith: str = "exact",
             bc_x: str = "dirichlet", bc_y: str = "dirichlet", source: Optional[torch.Tensor] = None,
             rmap: Optional[torch.Tensor] = None, faces: Optional[tuple] = None,
-            gain: Optional[torch.Tensor] = None, gain_pos: int = 0) -> None:
+            gain: Optional[torch.Tensor] = None, gain_pos: int = 0, robin=None) -> None:
     """dst[rows] = k FTCS steps of src (temporal-blocked kernel). The k ghost rows
     around ``rows`` must be valid in ``src``; Dirichlet rows/cols are kept.
     ``arith``: "exact" (reference rounding), "fma" (contracted update) or
@@ -123,7 +123,14 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
     dtype and device, finite and >= 0; level s of the pass adds
     ``gain[gain_pos + s - 1] * source`` — the product rounded, then the add;
     arith "fma": one fma (csrc/kernels/tb_impl.hpp ``tb_kernel_gain``). It must
-    hold at least ``gain_pos + k`` entries."""
+    hold at least ``gain_pos + k`` entries.
+    ``"robin"`` on either axis, with ``robin={"x_lo": (a, b), ...}`` for exactly
+    the sides of the Robin axes: at a point next to a Robin wall the operand
+    from beyond it is a * C + b of the point's own value C, at every fused
+    level (arith "fma": fma(a, C, b)); the frame of the rows written gets the
+    ghost values in ``dst``. Arith "exact" / "fma" / "auto", no ``source`` /
+    ``rmap`` / ``faces``; on the device k is at most ``N.max_tb_rob()``
+    (csrc/kernels/tb_impl.hpp ``tb_kernel_rob``)."""
     if gain is not None:
         if source is None:
             raise RuntimeError("gain= scales a heat source: pass source=")
@@ -179,6 +186,12 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
         raise ValueError("src/dst dtype/device mismatch")
     if src.data_ptr() == dst.data_ptr():
         raise ValueError("tb_step is out-of-place (ping-pong fields)")
+    has_robin = bc_x == "robin" or bc_y == "robin"
+    if has_robin or robin is not None:
+        rob_arr, _ = N.robin_array(robin, bc_x, bc_y, np.float32 if src.dtype == torch.float32 else np.float64)
+    if has_robin and arith not in ("exact", "fma", "auto"):
+        raise ValueError("Robin walls need arith 'exact', 'fma' or 'auto' (the scaled levels of jacobi / fast would need b "
+                         "scaled per level)")
     rb, re = (0, layout.nrows) if rows is None else rows
     ar = N.arith_code(arith, r)
     bc = N.bc_bits(bc_x, bc_y)
@@ -210,6 +223,14 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
         else:
             N.call("heat2d_cpu_tb_src", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
                    C.byref(layout), rb, re, k, r, ar, C.c_void_p(source.data_ptr()))
+        return
+    if has_robin:
+        if src.is_cuda:
+            N.call("heat2d_tb_rob", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                   C.byref(layout), rb, re, k, r, _stream(src), tile_rows, ar, bc, rob_arr)
+        else:
+            N.call("heat2d_cpu_tb_rob", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                   C.byref(layout), rb, re, k, r, ar, bc, rob_arr)
         return
     if src.is_cuda:
         N.call("heat2d_tb_bc", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
@@ -246,7 +267,7 @@ def probe_points(points, nrows_global: int, ncols: int) -> np.ndarray:
 def probe_cone(src: torch.Tensor, layout: N.Layout, k: int, r: float, points, arith: str = "exact",
                bc_x: str = "dirichlet", bc_y: str = "dirichlet", source: Optional[torch.Tensor] = None,
                rmap: Optional[torch.Tensor] = None, faces: Optional[tuple] = None,
-               gain: Optional[torch.Tensor] = None) -> torch.Tensor:
+               gain: Optional[torch.Tensor] = None, robin=None) -> torch.Tensor:
     """The probe-cone kernel alone (csrc/kernels/probe_cone.hip; CPU tensors:
     its twin): the values at ``points`` after each of the next k steps of
     ``src``, a (k, P) tensor of src's dtype and device — row s - 1 holds level
@@ -255,6 +276,8 @@ def probe_cone(src: torch.Tensor, layout: N.Layout, k: int, r: float, points, ar
     ``arith`` ("exact" / "fma" / "jacobi"), ``bc_x`` / ``bc_y`` and the
     coefficient buffers are :func:`tb_step`'s. ``gain`` (with ``source``): the
     k gains of the levels, level s scaled by ``gain[s - 1]`` (``probe_cone_gain``).
+    ``robin`` (with a "robin" axis, as :func:`tb_step`): the plain cone with the
+    ghost value at the walls (``probe_cone_rob``), arith "exact" / "fma".
     Nothing is written but the result."""
     if gain is not None:
         if source is None:
@@ -287,6 +310,11 @@ def probe_cone(src: torch.Tensor, layout: N.Layout, k: int, r: float, points, ar
             raise ValueError("a heat source, a diffusivity map and face coefficients need Dirichlet boundaries")
         if arith == "jacobi":
             raise ValueError("a heat source, a diffusivity map and face coefficients need arith 'exact' or 'fma'")
+    has_robin = bc_x == "robin" or bc_y == "robin"
+    if has_robin or robin is not None:
+        rob_arr, _ = N.robin_array(robin, bc_x, bc_y, np.float32 if src.dtype == torch.float32 else np.float64)
+    if has_robin and arith not in ("exact", "fma"):
+        raise ValueError("probe_cone: Robin walls need arith 'exact' or 'fma'")
     ar = N.arith_code(arith, r)
     out = torch.empty((k, len(pts)), dtype=src.dtype, device=src.device)
     if len(pts) == 0:
@@ -297,6 +325,13 @@ def probe_cone(src: torch.Tensor, layout: N.Layout, k: int, r: float, points, ar
         N.call("heat2d_probe_cone_gain", dtype_code(src), C.c_void_p(src.data_ptr()), C.byref(layout), int(k), float(r),
                ar, ptr[0], C.c_void_p(gain.data_ptr()), C.c_void_p(dpts.data_ptr()), len(pts),
                C.c_void_p(out.data_ptr()), _stream(src), int(src.is_cuda))
+        if src.is_cuda:
+            torch.cuda.current_stream(src.device).synchronize()  # keep dpts alive until done
+        return out
+    if has_robin:
+        N.call("heat2d_probe_cone_rob", dtype_code(src), C.c_void_p(src.data_ptr()), C.byref(layout), int(k), float(r),
+               ar, N.bc_bits(bc_x, bc_y), rob_arr, C.c_void_p(dpts.data_ptr()), len(pts), C.c_void_p(out.data_ptr()),
+               _stream(src), int(src.is_cuda))
         if src.is_cuda:
             torch.cuda.current_stream(src.device).synchronize()  # keep dpts alive until done
         return out

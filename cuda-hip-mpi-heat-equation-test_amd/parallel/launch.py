@@ -52,13 +52,22 @@ def build_parser():
                          "number, auto (GPU ranks: measured before the run — every rank times its own slab on a "
                          "1-rank loop exchange, uniform and shifted, parallel/select.balance_edges, as bench.py "
                          "does) or measure (the same on any backend)")
-    ap.add_argument("--bc-x", default=None, choices=["dirichlet", "periodic", "insulated"],
+    ap.add_argument("--bc-x", default=None, choices=["dirichlet", "periodic", "insulated", "robin"],
                     help="boundary condition of the x (row) axis, the one decomposed over ranks (default: "
                          "dirichlet, or a restart's checkpointed setting; a flag that contradicts the checkpoint "
                          "fails). periodic on more than one rank: host-staged halos (--transport auto picks them); "
-                         "insulated: a zero-flux wall, any transport")
-    ap.add_argument("--bc-y", default=None, choices=["dirichlet", "periodic", "insulated"],
-                    help="boundary condition of the y (column) axis")
+                         "insulated: a zero-flux wall, any transport; robin: a convective wall in the insulated "
+                         "geometry, ghost = A * C + B of the adjacent owned point, with --robin-x-lo / --robin-x-hi")
+    ap.add_argument("--bc-y", default=None, choices=["dirichlet", "periodic", "insulated", "robin"],
+                    help="boundary condition of the y (column) axis (robin: with --robin-y-lo / --robin-y-hi)")
+    for side, what in (("x-lo", "before the first owned row"), ("x-hi", "after the last owned row"),
+                       ("y-lo", "before the first owned column"), ("y-hi", "after the last owned column")):
+        ap.add_argument(f"--robin-{side}", default=None, metavar="A,B", type=_robin_pair,
+                        help=f"the pair (a, b) of the Robin wall {what}: both finite, converted to the run's dtype; "
+                             "needed exactly for the sides of a robin axis (a negative A: --robin-...=A,B). |a| > 1 draws a "
+                             "stability warning. "
+                             "Checkpoints record the converted pairs exactly; a restart takes them from there and a "
+                             "contradicting flag fails")
     ap.add_argument("--source", default=None, metavar="FILE.npy",
                     help="heat source u_t = nu lap(u) + f: the frame-inclusive (n+2) x (n+2) array of the per-step "
                          "increment dt * f (converted to the run's dtype; a wrong shape fails), added at every step "
@@ -108,6 +117,15 @@ def build_parser():
     ap.add_argument("--share-gpu", action="store_true",
                     help="every rank on GPU 0 (--transport peer or auto): the multi-process path on one GPU")
     return ap
+
+
+def _robin_pair(text: str):
+    """'A,B' -> (a, b): the argument of --robin-x-lo and its kin."""
+    try:
+        a, b = (float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected A,B (two numbers), got {text!r}") from None
+    return a, b
 
 
 def _dist_setup(backend: str, share_gpu: bool = False):
@@ -301,7 +319,7 @@ def run(argv=None) -> int:
             raise SystemExit(f"heat2d: --probes {a.probes}: {e}")
     # (with a source auto stays with the solver: fma when r is a power of two, else exact — never jacobi)
     if arith == "auto" and prob.r == 0.25 and prob.ic.sterbenz_safe() and not a.restart and engine == "tb" \
-            and source is None:
+            and source is None and "robin" not in (a.bc_x, a.bc_y):  # (Robin walls: auto stays with the solver too)
         arith = "jacobi"  # bitwise the reference rounding on this IC (the CLI's auto does the same)
 
     def make_transport(kind):
@@ -316,6 +334,33 @@ def run(argv=None) -> int:
             bc[k] = saved.get(k, "dirichlet")
             if flag is not None and flag != bc[k]:
                 raise SystemExit(f"heat2d: --{k.replace('_', '-')} {flag} conflicts with the checkpoint's {k} = {bc[k]}")
+    # Robin walls: the sides' pairs from the flags, or a restart checkpoint's (a contradicting flag fails)
+    import numpy as np
+    from heat2d.models.reference import robin_pairs
+    np_dtype = np.float64 if a.dtype == "fp64" else np.float32
+    flags = {side: getattr(a, "robin_" + side) for side in ("x_lo", "x_hi", "y_lo", "y_hi")}
+    given = {k: v for k, v in flags.items() if v is not None}
+    if a.restart:
+        robin = checkpoint.robin_from_meta(saved)
+        for k, v in given.items():
+            conv = tuple(float(np_dtype(x)) for x in v)
+            if k not in robin or conv != robin[k]:
+                raise SystemExit(f"heat2d: --robin-{k.replace('_', '-')} {v[0]},{v[1]} conflicts with the checkpoint's "
+                                 f"{k} = {robin.get(k)}")
+    else:
+        robin = given
+    try:
+        robin = {k: (float(p[0]), float(p[1])) for k, p in robin_pairs(robin, bc["bc_x"], bc["bc_y"], np_dtype).items()}
+    except ValueError as e:
+        raise SystemExit(f"heat2d: {e} (--robin-x-lo A,B --robin-x-hi A,B --robin-y-lo A,B --robin-y-hi A,B)")
+    if robin:
+        big = {k: p[0] for k, p in robin.items() if abs(p[0]) > 1}
+        if big and root:
+            print(f"warning: Robin |a| > 1 at {', '.join(f'{k} (a = {v:.6g})' for k, v in big.items())}: the wall "
+                  "amplifies, FTCS may be unstable", file=sys.stderr)
+        if arith in ("jacobi", "fast"):
+            raise SystemExit(f"heat2d: --arith {arith} has no Robin walls (their scaled levels would need b scaled per "
+                             "level): use exact, fma or auto")
     if bc["bc_x"] == "periodic" and world > 1 and backend == "hip" and a.transport in ("rccl", "peer"):
         raise SystemExit(f"heat2d: --transport {a.transport} does not pair the first rank with the last: periodic x "
                          "on more than one rank needs --transport host (or auto)")
@@ -344,7 +389,8 @@ def run(argv=None) -> int:
         return HeatSolver(prob, dtype=a.dtype, backend=backend, tb=a.tb, overlap=not a.no_overlap,
                           copy_swap=a.copy_swap, managed=a.managed or var.managed, graph=a.graph, transport=tr,
                           device=local if backend == "hip" else None, engine=engine, arith=arith,
-                          edge_shift=edge_shift, source=source, rmap=rmap, faces=faces, source_gain=source_gain, **bc)
+                          edge_shift=edge_shift, source=source, rmap=rmap, faces=faces, source_gain=source_gain,
+                          robin=robin or None, **bc)
 
     tr, s, kind, fallback = _make_solver(kinds, make_transport, make_solver, world)
     if fallback and root and not a.quiet:

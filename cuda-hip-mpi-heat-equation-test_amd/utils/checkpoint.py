@@ -131,6 +131,10 @@ def save(solver, directory: str, step: Optional[int] = None, extra: Optional[dic
         # restart continues at G[step] and must be given the same schedule
         if getattr(solver, "source_gain_sha256", None) is not None:
             meta["source_gain_sha256"] = solver.source_gain_sha256
+        # ... and the Robin walls' pairs, exactly: the values converted to the run's dtype as hex floats
+        # (HeatSolver.robin); the key only with a Robin axis
+        if getattr(solver, "robin", None):
+            meta["robin"] = robin_to_meta(solver.robin)
         meta.update(extra or {})
         _write_atomic(os.path.join(sd, "meta.json"), json.dumps(meta, indent=1))
         _write_atomic(os.path.join(directory, "latest"), os.path.basename(sd) + "\n")  # the commit point
@@ -138,6 +142,16 @@ def save(solver, directory: str, step: Optional[int] = None, extra: Optional[dic
         for d in steps[:max(0, steps.index(os.path.basename(sd)) - 1)]:  # keep the two newest
             shutil.rmtree(os.path.join(directory, d), ignore_errors=True)
     _barrier(solver)
+
+
+def robin_to_meta(pairs: dict) -> dict:
+    """{side: [a.hex(), b.hex()]} of the converted Robin pairs: what meta.json records."""
+    return {k: [float(a).hex(), float(b).hex()] for k, (a, b) in sorted(pairs.items())}
+
+
+def robin_from_meta(meta: dict) -> dict:
+    """The Robin pairs a checkpoint recorded, {side: (a, b)} ({} without a Robin axis)."""
+    return {k: (float.fromhex(a), float.fromhex(b)) for k, (a, b) in meta.get("robin", {}).items()}
 
 
 def resolve(directory: str) -> str:
@@ -169,6 +183,10 @@ def load(solver, directory: str) -> dict:
     for k in ("bc_x", "bc_y"):  # (older saves: dirichlet)
         if meta.get(k, "dirichlet") != getattr(solver, k, "dirichlet"):
             raise ValueError(f"checkpoint {k} = {meta.get(k, 'dirichlet')} != solver {k} = {getattr(solver, k, 'dirichlet')}")
+    # (by value: the two drivers spell a hex float differently)
+    have, saved = {k: tuple(v) for k, v in (getattr(solver, "robin", None) or {}).items()}, robin_from_meta(meta)
+    if have != saved:
+        raise ValueError(f"the restart's Robin pairs differ from the checkpoint's ({have} != {saved})")
     have, saved = getattr(solver, "source_sha256", None), meta.get("source_sha256")  # (older saves: none)
     if saved != have:
         if saved is None:
