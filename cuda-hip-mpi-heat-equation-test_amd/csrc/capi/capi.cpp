@@ -194,14 +194,19 @@ int heat2d_plan_split(int dtype, const heat2d_layout* L, int k, int64_t band, he
 int heat2d_tb(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
               double r, void* stream, int64_t tile_rows, int arith) {
   return guarded([&] {
-    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, arith);
+    kern::TbTerms t;
+    t.arith = arith;
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, t);
   });
 }
 
 int heat2d_tb_bc(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                  double r, void* stream, int64_t tile_rows, int arith, int bc) {
   return guarded([&] {
-    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, arith, bc);
+    kern::TbTerms t;
+    t.arith = arith;
+    t.bc = bc;
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, t);
   });
 }
 
@@ -209,8 +214,11 @@ int heat2d_tb_rob(int dtype, const void* src, void* dst, const heat2d_layout* L,
                   double r, void* stream, int64_t tile_rows, int arith, int bc, const double* robin) {
   return guarded([&] {
     HEAT2D_REQUIRE(robin != nullptr, "heat2d_tb_rob needs the walls' pairs");
-    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, arith, bc, nullptr,
-                    nullptr, nullptr, nullptr, {}, robin);
+    kern::TbTerms t;
+    t.arith = arith;
+    t.bc = bc;
+    t.robin = robin;
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, t);
   });
 }
 
@@ -218,7 +226,11 @@ int heat2d_cpu_tb_rob(int dtype, const void* src, void* dst, const heat2d_layout
                       double r, int arith, int bc, const double* robin) {
   return guarded([&] {
     HEAT2D_REQUIRE(robin != nullptr, "heat2d_cpu_tb_rob needs the walls' pairs");
-    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, arith, bc, nullptr, nullptr, nullptr, nullptr, {}, robin);
+    kern::TbTerms t;
+    t.arith = arith;
+    t.bc = bc;
+    t.robin = robin;
+    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, t);
   });
 }
 
@@ -227,29 +239,43 @@ int heat2d_max_tb_rob(void) { return kMaxTBRob; }
 int heat2d_tb_src(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                   double r, void* stream, int64_t tile_rows, int arith, const void* source) {
   return guarded([&] {
-    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, arith, 0, source);
+    kern::TbTerms t;
+    t.arith = arith;
+    t.source = source;
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, t);
   });
 }
 
 int heat2d_cpu_tb_src(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                       double r, int arith, const void* source) {
-  return guarded([&] { cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, arith, 0, source); });
+  return guarded([&] {
+    kern::TbTerms t;
+    t.arith = arith;
+    t.source = source;
+    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, t);
+  });
 }
 
 int heat2d_tb_gain(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                    double r, void* stream, int64_t tile_rows, int arith, const void* source, const void* gain,
                    const int64_t* gain_pos) {
   return guarded([&] {
-    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, arith, 0, source,
-                    nullptr, nullptr, nullptr, kern::GainRef{gain, gain_pos});
+    kern::TbTerms t;
+    t.arith = arith;
+    t.source = source;
+    t.gain = kern::GainRef{gain, gain_pos};
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, as_stream(stream), tile_rows, 0, t);
   });
 }
 
 int heat2d_cpu_tb_gain(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                        double r, int arith, const void* source, const void* gain, const int64_t* gain_pos) {
   return guarded([&] {
-    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, arith, 0, source, nullptr, nullptr, nullptr,
-            kern::GainRef{gain, gain_pos});
+    kern::TbTerms t;
+    t.arith = arith;
+    t.source = source;
+    t.gain = kern::GainRef{gain, gain_pos};
+    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, t);
   });
 }
 
@@ -257,7 +283,10 @@ int heat2d_tb_var(int dtype, const void* src, void* dst, const heat2d_layout* L,
                   void* stream, int64_t tile_rows, int arith, const void* rmap) {
   return guarded([&] {
     HEAT2D_REQUIRE(rmap != nullptr, "heat2d_tb_var needs a diffusivity-map buffer");
-    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, as_stream(stream), tile_rows, 0, arith, 0, nullptr, rmap);
+    kern::TbTerms t;
+    t.arith = arith;
+    t.rmap = rmap;
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, as_stream(stream), tile_rows, 0, t);
   });
 }
 
@@ -265,7 +294,10 @@ int heat2d_cpu_tb_var(int dtype, const void* src, void* dst, const heat2d_layout
                       int arith, const void* rmap) {
   return guarded([&] {
     HEAT2D_REQUIRE(rmap != nullptr, "heat2d_cpu_tb_var needs a diffusivity-map buffer");
-    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, arith, 0, nullptr, rmap);
+    kern::TbTerms t;
+    t.arith = arith;
+    t.rmap = rmap;
+    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, t);
   });
 }
 
@@ -273,7 +305,11 @@ int heat2d_tb_div(int dtype, const void* src, void* dst, const heat2d_layout* L,
                   void* stream, int64_t tile_rows, int arith, const void* rx, const void* ry) {
   return guarded([&] {
     HEAT2D_REQUIRE(rx != nullptr && ry != nullptr, "heat2d_tb_div needs both face-coefficient buffers");
-    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, as_stream(stream), tile_rows, 0, arith, 0, nullptr, nullptr, rx, ry);
+    kern::TbTerms t;
+    t.arith = arith;
+    t.rx = rx;
+    t.ry = ry;
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, as_stream(stream), tile_rows, 0, t);
   });
 }
 
@@ -281,7 +317,11 @@ int heat2d_cpu_tb_div(int dtype, const void* src, void* dst, const heat2d_layout
                       int arith, const void* rx, const void* ry) {
   return guarded([&] {
     HEAT2D_REQUIRE(rx != nullptr && ry != nullptr, "heat2d_cpu_tb_div needs both face-coefficient buffers");
-    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, arith, 0, nullptr, nullptr, rx, ry);
+    kern::TbTerms t;
+    t.arith = arith;
+    t.rx = rx;
+    t.ry = ry;
+    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, t);
   });
 }
 
@@ -332,12 +372,21 @@ int heat2d_unpack_rows(int dtype, void* field, const heat2d_layout* L, int64_t r
 
 int heat2d_cpu_tb(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                   double r, int arith) {
-  return guarded([&] { cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, arith); });
+  return guarded([&] {
+    kern::TbTerms t;
+    t.arith = arith;
+    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, t);
+  });
 }
 
 int heat2d_cpu_tb_bc(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                      double r, int arith, int bc) {
-  return guarded([&] { cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, arith, bc); });
+  return guarded([&] {
+    kern::TbTerms t;
+    t.arith = arith;
+    t.bc = bc;
+    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, r, t);
+  });
 }
 
 int heat2d_cpu_init_field(int dtype, void* field, const heat2d_layout* L, const heat2d_ic* ic, const double* xc,

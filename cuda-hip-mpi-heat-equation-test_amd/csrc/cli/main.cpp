@@ -85,7 +85,7 @@ struct Args {
   // --robin-x-lo / --robin-x-hi / --robin-y-lo / --robin-y-hi A,B: the pair (a, b) of a Robin wall, ghost =
   // a * C + b (SolverConfig::robin, sides in that order); needed exactly for the sides of the robin axes,
   // or taken from a restart's checkpoint
-  bool robin_set[4] = {false, false, false, false};
+  bool robin_set[4] = {};
   double robin[8] = {1.0, -0.0, 1.0, -0.0, 1.0, -0.0, 1.0, -0.0};
   // --source FILE.npy: heat source, the frame-inclusive (n+2) x (n+2) per-step increment dt * f
   // (SolverConfig::source; converted to the run's dtype, a wrong shape fails)

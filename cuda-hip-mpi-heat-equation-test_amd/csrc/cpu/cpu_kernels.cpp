@@ -393,8 +393,12 @@ int num_threads() {
 }
 
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end,
-        int k, double r, int arith, int bc, const void* source, const void* rmap, const void* rx, const void* ry,
-        kern::GainRef gain, const double* robin) {
+        int k, double r, const kern::TbTerms& terms) {
+  int arith = terms.arith;
+  const int bc = terms.bc;
+  const void *source = terms.source, *rmap = terms.rmap, *rx = terms.rx, *ry = terms.ry;
+  const kern::GainRef gain = terms.gain;
+  const double* robin = terms.robin;
   HEAT2D_REQUIRE(k >= 1 && k <= L.halo, "k out of range");
   HEAT2D_REQUIRE(arith >= 0 && arith <= 3, "arith must be 0, 1, 2 or 3");
   HEAT2D_REQUIRE(arith != 2 || r == 0.25, "arith 2 (jacobi) needs r == 1/4 exactly");

@@ -32,13 +32,13 @@ struct TbPlan {
 // rows, < 0 -tile_rows segments (TbRect nb < 0; ntiles = -segments); cus > 0 plans for a
 // stream restricted to that many CUs (comm-reserving CU mask).
 // arith: 0 = reference arithmetic (every op rounded), 1 = contracted fma form,
-// 2 = r == 1/4: (S + E + N + W) / 4 (tb_impl.hpp, March); every launcher below
-// takes it last.
+// 2 = r == 1/4: (S + E + N + W) / 4 (tb_impl.hpp, March); the launchers below
+// take it in their TbTerms.
 TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end, int k,
                int64_t tile_rows = 0, int cus = 0, int arith = 0);
 
-// Boundary conditions (SolverConfig::bc_x / bc_y as one bit set): every stencil
-// launcher below takes it after arith. 0 = the Dirichlet frame on both axes.
+// Boundary conditions (SolverConfig::bc_x / bc_y as one bit set, TbTerms::bc
+// below). 0 = the Dirichlet frame on both axes.
 //   kBcPeriodicX: no row is pinned — the slab is marched as a middle slab
 //     whatever its place in the grid (bc_layout); its ghost rows are wrap
 //     images, kept by the halo exchange (one rank: launch_wrap_rows).
@@ -68,11 +68,11 @@ TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end
 //   kBcRobinX / kBcRobinY: a Robin (convective) wall in the insulated
 //     geometry: the value beyond the wall is the affine ghost G = a * C + b of
 //     the adjacent owned point C (the product rounded, then the add; arith 1:
-//     fma(a, C, b)), with a pair (a, b) per wall (`robin`, the launchers' last
-//     argument). G depends on the level's own C, so it is formed inside the
-//     march at every level: tb_kernel_rob (tb_impl.hpp March ROB) takes the
-//     place of tb_kernel_ins in every launch, and an insulated wall on the
-//     other axis runs on it as (1, -0.0), which returns every C unchanged.
+//     fma(a, C, b)), with a pair (a, b) per wall (TbTerms::robin). G depends on
+//     the level's own C, so it is formed inside the march at every level:
+//     tb_kernel_rob (tb_impl.hpp, March with kFeatRob) takes the place of
+//     tb_kernel_ins in every launch, and an insulated wall on the other axis
+//     runs on it as (1, -0.0), which returns every C unchanged.
 //     The launchers write the ghost values into the frame of the rows they
 //     wrote (launch_rob_rows, then launch_rob_cols over the frame rows too:
 //     the golden's x first, then y). Arith 0 / 1, depths 1..kMaxTBRob.
@@ -91,7 +91,7 @@ inline void wall_pairs(int bc, bool x_axis, const double* robin, double out[4]) 
   const bool rob = (bc & (x_axis ? kBcRobinX : kBcRobinY)) != 0;
   for (int i = 0; i < 4; ++i) out[i] = rob ? robin[(x_axis ? kRobinXLo : kRobinYLo) + i] : ((i & 1) ? -0.0 : 1.0);
 }
-// A source's gain schedule as the launchers take it (launch_tb below): the gain
+// A source's gain schedule as the launchers take it (TbTerms::gain below): the gain
 // array and the position word, both in the launch's memory space.
 struct GainRef {
   const void* g = nullptr;
@@ -143,54 +143,68 @@ void launch_rob_rows(DType dt, void* field, const SlabLayout& L, bool lo, bool h
 void launch_rob_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1, const double* pairs,
                      int arith, hipStream_t stream);
 
+// The terms of a stencil launch: the arithmetic form, the boundary kinds and the
+// optional buffers of the features. Every stencil launcher below (and its CPU
+// twin cpu::tb) takes one; a default-constructed one is the plain Dirichlet
+// march in reference arithmetic. Which terms go together, and in which kernel
+// family a launch runs: stencil_tb.hip select_family.
+struct TbTerms {
+  // 0 = reference arithmetic (every op rounded), 1 = contracted fma form,
+  // 2 = r == 1/4, 3 = any r with scaled levels (plan_tb above)
+  int arith = 0;
+  // the boundary kinds, kBcPeriodicX | ... | kBcRobinY above; 0 = the Dirichlet frame on both axes
+  int bc = 0;
+  // A heat source S in the field's layout and dtype, added at every fused level,
+  // T' = update(T) + S (one separately rounded add per point and level) — the
+  // per-step increment dt * f, holding -0.0 in every frame row / column and pad
+  // entry so that pinned points keep their bits. With a source every rect of the
+  // launch runs tb_kernel_src (tb_impl.hpp): Dirichlet on both axes, arith 0 / 1,
+  // depths 1..kMaxTBSrc, no wave-pair plans. nullptr: no source.
+  const void* source = nullptr;
+  // The per-point diffusion number R in the field's layout and dtype, the
+  // multiplier of every point's update at every fused level,
+  // T' = C + R * (sum - 4C) — `r` is then not used. It holds +0.0 in every frame
+  // row / column, pad entry and row outside the grid: that is the pinning, and a
+  // 0 at an owned point holds that point. With a map every rect of the launch
+  // runs tb_kernel_var (tb_impl.hpp): Dirichlet on both axes, arith 0 / 1,
+  // depths 1..kMaxTBVar, no wave-pair plans, not together with a source.
+  const void* rmap = nullptr;
+  // Both or neither: the per-face diffusion numbers of the conservative form
+  // div(k grad u) in the field's layout and dtype — rx at (i, j) the face between
+  // (i, j) and (i, j+1), ry the face between (i, j) and (i+1, j) —,
+  // T' = C + (((ry*(S-C) + rx*(E-C)) + ry[i-1]*(N-C)) + rx[j-1]*(W-C)) at every
+  // fused level; `r` is then not used. They hold +0.0 in every pad entry and row
+  // outside the grid and keep the faces next to the frame (frame column -1 of rx,
+  // frame row -1 of ry). With faces every rect of the launch runs tb_kernel_div
+  // (tb_impl.hpp): Dirichlet on both axes, arith 0 / 1, depths 1..kMaxTBDiv, no
+  // wave-pair plans, not together with a source or a map.
+  const void *rx = nullptr, *ry = nullptr;
+  // Needs a source: a per-step gain schedule, level s of the pass adds
+  // g[*pos + s - 1] * S — the product rounded, then the add; arith 1:
+  // fma(g, S, update), one rounding. g: device array of the field's dtype,
+  // readable up to *pos + k entries (the solver pads it by kMaxTBSrc); pos: a
+  // device word, read when the kernel runs, so a captured launch takes the
+  // position of its replay. Every rect runs tb_kernel_gain, tb_kernel_src's
+  // launch shape. {}: the source as it is.
+  GainRef gain{};
+  // Needed with kBcRobinX / kBcRobinY in bc: the 8 values of the Robin walls'
+  // pairs in the field's dtype (kRobinXLo ..), read on the host when the launch
+  // is made and passed to tb_kernel_rob by value, so a captured launch keeps
+  // them. Every launch that would run tb_kernel_ins runs tb_kernel_rob: arith
+  // 0 / 1, depths 1..kMaxTBRob, no source / rmap / faces.
+  const double* robin = nullptr;
+};
+
 // dst(rows [row_begin,row_end)) = k FTCS steps of src. `src`/`dst` are
 // allocation bases laid out per `L`. Requires k <= L.halo and the k ghost rows
 // on both sides of the range to hold valid data at time t (Dirichlet rows are
 // recognised from L.row0 / L.nrows_global and kept fixed).
-// source (optional, every stencil launcher takes it last): a heat source S in
-// the field's layout and dtype, added at every fused level,
-// T' = update(T) + S (one separately rounded add per point and level) — the
-// per-step increment dt * f, holding -0.0 in every frame row / column and pad
-// entry so that pinned points keep their bits. With a source every rect of the
-// launch runs tb_kernel_src (tb_impl.hpp): Dirichlet on both axes, arith 0 / 1,
-// depths 1..kMaxTBSrc, no wave-pair plans. nullptr: today's dispatch.
-// rmap (optional, after source): the per-point diffusion number R in the
-// field's layout and dtype, the multiplier of every point's update at every
-// fused level, T' = C + R * (sum - 4C) — `r` is then not used. It holds +0.0
-// in every frame row / column, pad entry and row outside the grid: that is the
-// pinning, and a 0 at an owned point holds that point. With a map every rect of
-// the launch runs tb_kernel_var (tb_impl.hpp): Dirichlet on both axes, arith
-// 0 / 1, depths 1..kMaxTBVar, no wave-pair plans, not together with a source.
-// rx, ry (optional, after rmap; both or neither): the per-face diffusion numbers
-// of the conservative form div(k grad u) in the field's layout and dtype — rx at
-// (i, j) the face between (i, j) and (i, j+1), ry the face between (i, j) and
-// (i+1, j) —, T' = C + (((ry*(S-C) + rx*(E-C)) + ry[i-1]*(N-C)) + rx[j-1]*(W-C))
-// at every fused level; `r` is then not used. They hold +0.0 in every pad entry
-// and row outside the grid and keep the faces next to the frame (frame column
-// -1 of rx, frame row -1 of ry). With faces every rect of the launch runs
-// tb_kernel_div (tb_impl.hpp): Dirichlet on both axes, arith 0 / 1, depths
-// 1..kMaxTBDiv, no wave-pair plans, not together with a source or a map.
-// gain (optional, after ry; needs a source): a per-step gain schedule, level s
-// of the pass adds g[*pos + s - 1] * S — the product rounded, then the add;
-// arith 1: fma(g, S, update), one rounding. g: device array of the field's
-// dtype, readable up to *pos + k entries (the solver pads it by kMaxTBSrc);
-// pos: a device word, read when the kernel runs, so a captured launch takes the
-// position of its replay. Every rect runs tb_kernel_gain, tb_kernel_src's
-// launch shape. {}: the source as it is.
-// robin (optional, after gain; needed with kBcRobinX / kBcRobinY in bc): the 8
-// values of the Robin walls' pairs in the field's dtype (kRobinXLo ..), read on
-// the host when the launch is made and passed to tb_kernel_rob by value, so a
-// captured launch keeps them. Every launch that would run tb_kernel_ins runs
-// tb_kernel_rob: arith 0 / 1, depths 1..kMaxTBRob, no source / rmap / faces.
-void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
-               int64_t row_end, int k, double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0,
-               int arith = 0, int bc = 0, const void* source = nullptr, const void* rmap = nullptr,
-               const void* rx = nullptr, const void* ry = nullptr, GainRef gain = {}, const double* robin = nullptr);
+void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end, int k,
+               double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0, const TbTerms& terms = {});
 // Same for TWO disjoint row ranges [rb0, re0) and [rb1, re1) in one launch.
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
                 int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows = 0, int cus = 0,
-                int arith = 0, int bc = 0, const void* source = nullptr, const void* rmap = nullptr,
-                const void* rx = nullptr, const void* ry = nullptr, GainRef gain = {}, const double* robin = nullptr);
+                const TbTerms& terms = {});
 
 // Split schedule of one cycle (k steps over the whole slab) into two launches
 // on two streams:
@@ -267,14 +281,10 @@ bool edges_on_main(const SlabLayout& L, const SplitPlan& p);
 // stays clear of the global frame rows, else the general one (edge ranks).
 bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i);
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
-                      hipStream_t stream, int arith = 0, int bc = 0, const void* source = nullptr,
-                      const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr,
-                      GainRef gain = {}, const double* robin = nullptr);
+                      hipStream_t stream, const TbTerms& terms = {});
 // queue: 2 device counters (zeroed once) for plans with flags & kPlanDynamic (dynamic items)
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
-                  double r, hipStream_t stream, int arith = 0, uint32_t* queue = nullptr, int bc = 0,
-                  const void* source = nullptr, const void* rmap = nullptr, const void* rx = nullptr,
-                  const void* ry = nullptr, GainRef gain = {}, const double* robin = nullptr);
+                  double r, hipStream_t stream, const TbTerms& terms = {}, uint32_t* queue = nullptr);
 
 // Initial / boundary condition kinds (covers every IC of the reference
 // variants, see models/presets.py for the mapping).

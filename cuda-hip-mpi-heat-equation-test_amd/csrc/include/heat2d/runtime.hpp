@@ -277,9 +277,7 @@ std::shared_ptr<Transport> make_ipc_loop_transport(int device);
 
 namespace cpu {
 void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin,
-        int64_t row_end, int k, double r, int arith = 0, int bc = 0, const void* source = nullptr,
-        const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr, kern::GainRef gain = {},
-        const double* robin = nullptr);
+        int64_t row_end, int k, double r, const kern::TbTerms& terms = {});
 void wrap_cols(DType dt, void* field, const SlabLayout& L, int64_t r0, int64_t r1);
 void wrap_rows(DType dt, void* field, const SlabLayout& L, int64_t k);
 // insulated frame images (kern::launch_ins_cols / launch_ins_rows)
@@ -648,6 +646,20 @@ class Solver {
   bool faces_on_ = false;                   // set_faces has filled them
   const void* face_rx() const { return faces_on_ ? face_buf_[0] : nullptr; }
   const void* face_ry() const { return faces_on_ ? face_buf_[1] : nullptr; }
+  // The terms of a stencil launch of this solver. Built at the call: gain()
+  // names the position word of the current buffer parity (cur_).
+  kern::TbTerms terms() const {
+    kern::TbTerms t;
+    t.arith = cfg_.arith;
+    t.bc = bc_;
+    t.source = source();
+    t.rmap = rmap();
+    t.rx = face_rx();
+    t.ry = face_ry();
+    t.gain = gain();
+    t.robin = robin();
+    return t;
+  }
   void drop_graphs();         // captured graphs hold the kernels of the run with / without a source or map
   // probe points (set_probes): this rank's points as (local row, column) pairs,
   // the history and the device-resident row base (HIP) or their host twins

@@ -274,17 +274,28 @@ int64_t choose_bands(int64_t rows, int64_t ns, int64_t simds, int k, int64_t pri
   return best;
 }
 
-// Insulated edges (kBcInsulatedX / kBcInsulatedY): the kernel argument of tb_kernel_ins and its occupancy
+// with_ar for a family with fewer forms: arith 0..MAXAR, anything else rejected with the family's message
+template <int MAXAR, class F>
+decltype(auto) with_ar_upto(int arith, const char* msg, F&& f) {
+  HEAT2D_REQUIRE(arith >= 0 && arith <= MAXAR, msg);
+  if constexpr (MAXAR >= 2) {
+    if (arith == 2) return f(std::integral_constant<int, 2>{});
+  }
+  if (arith == 1) return f(std::integral_constant<int, 1>{});
+  return f(std::integral_constant<int, 0>{});
+}
+// f is called with a value of the field's element type
+template <class F>
+decltype(auto) with_dtype(DType dt, F&& f) {
+  if (dt == DType::F32) return f(float{});
+  return f(double{});
+}
+
+// Insulated edges (kBcInsulatedX / kBcInsulatedY): the kernel argument of tb_kernel_ins
 // (a Robin axis has the insulated walls: tb_kernel_rob takes the same edges beside its pairs)
 constexpr int kBcAll = kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY | kBcRobinX | kBcRobinY;
 int ins_edges(int bc) {
   return ((bc & kBcWallX) ? (kInsRowLo | kInsRowHi) : 0) | ((bc & kBcWallY) ? (kInsColLo | kInsColHi) : 0);
-}
-// Robin walls (tb_kernel_rob): resident 256-thread workgroups per CU
-int occupancy_rob(DType dt, int k, int arith) {
-  HEAT2D_REQUIRE(arith == 0 || arith == 1, "Robin walls need arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 would need b scaled per level");
-  if (arith == 1) return dt == DType::F32 ? occupancy_blocks_rob<float, 1>(k) : occupancy_blocks_rob<double, 1>(k);
-  return dt == DType::F32 ? occupancy_blocks_rob<float, 0>(k) : occupancy_blocks_rob<double, 0>(k);
 }
 // the pairs of the launch as the kernel takes them (insulated walls of a launch with a Robin axis: (1, -0.0))
 template <typename T>
@@ -299,44 +310,157 @@ RobCoef<T> rob_coef(int bc, const double* robin) {
   g.a[kRobE] = (T)y[2]; g.b[kRobE] = (T)y[3];
   return g;
 }
-int occupancy_ins(DType dt, int k, int arith) {
-  return with_ar(arith, [&](auto ar) {
-    constexpr int AR = decltype(ar)::value;
-    if constexpr (AR == 3) {
-      HEAT2D_REQUIRE(false, "insulated boundaries have no arith 3 (fast) kernels");
-      return 1;
-    } else {
-      return dt == DType::F32 ? occupancy_blocks_ins<float, AR>(k) : occupancy_blocks_ins<double, AR>(k);
-    }
+
+// The kernel family a launch runs (select_family). Plain: tb_kernel (general or
+// interior, any ring); Stats: its fused-statistics variant; Pipe: the wave-pair
+// kernel; the rest: the six feature families of tb_impl.hpp.
+enum class Family { Plain, Stats, Pipe, Ins, Rob, Src, Gain, Var, Div };
+// What the host needs to know of a feature family.
+struct FamilyInfo {
+  int max_k;             // deepest pass,
+  const char* too_deep;  // and the message beyond it (nullptr: kMaxTB, check_layout's)
+  int max_arith;         // arithmetic forms 0..max_arith,
+  const char* no_form;   // and the message for a form the family has no kernels for
+  // true: every launch, interior ones too, runs the family's (general) kernel, on at most as
+  // many waves as that kernel keeps resident; false: it stands in for general launches only
+  bool every_rect;
+  int waves;             // waves per workgroup: 4 (256 threads) or 1 (64)
+  int (*occupancy)(const FamilyInfo&, DType, int k, int arith);  // resident workgroups per CU
+  void (*launch)(const FamilyInfo&, DType, int k, const TbTerms&, const void* src, void* dst, int64_t origin,
+                 const TbArgs&, double r, int ins, hipStream_t);
+};
+template <class FAM, int MAXAR>
+int occupancy_family(const FamilyInfo& f, DType dt, int k, int arith) {
+  return with_dtype(dt, [&](auto z) {
+    return with_ar_upto<MAXAR>(arith, f.no_form, [&](auto ar) {
+      return occupancy_feat<FAM, decltype(z), decltype(ar)::value>(k);
+    });
   });
 }
-
-// Heat source with a gain schedule (tb_kernel_gain): resident waves per CU (one-wave workgroups)
-int occupancy_gain(DType dt, int k, int arith) {
-  HEAT2D_REQUIRE(arith == 0 || arith == 1, "a gain schedule needs arith 0 (exact) or 1 (fma)");
-  if (arith == 1) return dt == DType::F32 ? occupancy_waves_gain<float, 1>(k) : occupancy_waves_gain<double, 1>(k);
-  return dt == DType::F32 ? occupancy_waves_gain<float, 0>(k) : occupancy_waves_gain<double, 0>(k);
+// The launch of a feature family: the kernel takes its own part of the FeatArgs
+// (the one of source / rmap / rx that is set is its first buffer).
+template <class FAM, int MAXAR>
+void launch_family(const FamilyInfo& f, DType dt, int k, const TbTerms& t, const void* src, void* dst, int64_t o,
+                   const TbArgs& a, double r, int ins, hipStream_t stream) {
+  with_dtype(dt, [&](auto z) {
+    using T = decltype(z);
+    FeatArgs<T> x;
+    x.r = (T)r;
+    x.ins = ins;
+    if (t.bc & kBcRobin) x.rob = rob_coef<T>(t.bc, t.robin);
+    const void* q = t.source ? t.source : (t.rmap ? t.rmap : t.rx);
+    x.q = q ? static_cast<const T*>(q) + o : nullptr;
+    x.q2 = t.ry ? static_cast<const T*>(t.ry) + o : nullptr;
+    x.g = static_cast<const T*>(t.gain.g);
+    x.pos = t.gain.pos;
+    with_ar_upto<MAXAR>(t.arith, f.no_form, [&](auto ar) {
+      dispatch_feat<FAM, T, decltype(ar)::value>(k, (unsigned)a.nwaves, static_cast<const T*>(src) + o,
+                                                 static_cast<T*>(dst) + o, a, x, stream);
+    });
+  });
+}
+template <class FAM, int MAXAR>
+constexpr FamilyInfo family(int max_k, const char* too_deep, const char* no_form, bool every_rect) {
+  return FamilyInfo{max_k, too_deep, MAXAR, no_form, every_rect, FAM::kWaves, &occupancy_family<FAM, MAXAR>,
+                    &launch_family<FAM, MAXAR>};
+}
+// The family table (nullptr: tb_kernel and the wave-pair kernel, which have dispatchers of their own).
+const FamilyInfo* family_info(Family f) {
+  static constexpr FamilyInfo ins = family<FamIns, 2>(kMaxTB, nullptr, "insulated boundaries have no arith 3 (fast) kernels", false);
+  static constexpr FamilyInfo rob = family<FamRob, 1>(
+      kMaxTBRob, "temporal depth exceeds the Robin-wall kernels' deepest pass (kMaxTBRob)",
+      "Robin walls need arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 would need b scaled per level", false);
+  static constexpr FamilyInfo src = family<FamSrc, 1>(
+      kMaxTBSrc, "temporal depth exceeds the heat-source kernels' deepest pass (kMaxTBSrc)",
+      "a heat source needs arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 have no source kernels", true);
+  static constexpr FamilyInfo gain = family<FamGain, 1>(
+      kMaxTBSrc, "temporal depth exceeds the heat-source kernels' deepest pass (kMaxTBSrc)",
+      "a gain schedule needs arith 0 (exact) or 1 (fma)", true);
+  static constexpr FamilyInfo var = family<FamVar, 1>(
+      kMaxTBVar, "temporal depth exceeds the diffusivity-map kernels' deepest pass (kMaxTBVar)",
+      "a diffusivity map needs arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 assume one r", true);
+  static constexpr FamilyInfo div = family<FamDiv, 1>(
+      kMaxTBDiv, "temporal depth exceeds the conservative-form kernels' deepest pass (kMaxTBDiv)",
+      "face coefficients need arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 assume one r", true);
+  switch (f) {
+    case Family::Ins: return &ins;
+    case Family::Rob: return &rob;
+    case Family::Src: return &src;
+    case Family::Gain: return &gain;
+    case Family::Var: return &var;
+    case Family::Div: return &div;
+    default: return nullptr;
+  }
 }
 
-// Heat source (tb_kernel_src): resident waves per CU (one-wave workgroups)
-int occupancy_src(DType dt, int k, int arith) {
-  HEAT2D_REQUIRE(arith == 0 || arith == 1, "a heat source needs arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 have no source kernels");
-  if (arith == 1) return dt == DType::F32 ? occupancy_waves_src<float, 1>(k) : occupancy_waves_src<double, 1>(k);
-  return dt == DType::F32 ? occupancy_waves_src<float, 0>(k) : occupancy_waves_src<double, 0>(k);
-}
-
-// Diffusivity map (tb_kernel_var): resident waves per CU (one-wave workgroups)
-int occupancy_var(DType dt, int k, int arith) {
-  HEAT2D_REQUIRE(arith == 0 || arith == 1, "a diffusivity map needs arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 assume one r");
-  if (arith == 1) return dt == DType::F32 ? occupancy_waves_var<float, 1>(k) : occupancy_waves_var<double, 1>(k);
-  return dt == DType::F32 ? occupancy_waves_var<float, 0>(k) : occupancy_waves_var<double, 0>(k);
-}
-
-// Conservative form (tb_kernel_div): resident waves per CU (one-wave workgroups)
-int occupancy_div(DType dt, int k, int arith) {
-  HEAT2D_REQUIRE(arith == 0 || arith == 1, "face coefficients need arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 assume one r");
-  if (arith == 1) return dt == DType::F32 ? occupancy_waves_div<float, 1>(k) : occupancy_waves_div<double, 1>(k);
-  return dt == DType::F32 ? occupancy_waves_div<float, 0>(k) : occupancy_waves_div<double, 0>(k);
+// The one place that decides which kernel family a launch of depth k with terms
+// `t` runs — main: an interior (MAIN) launch, partials: with fused statistics,
+// pipe: on the wave-pair kernel — and that rejects every combination of terms no
+// kernel carries. Checks only; nothing is launched or queried.
+//   faces (rx, ry) / rmap / source [+ gain]: Div / Var / Src / Gain, every rect of
+//     the launch, interior ones too; one of the three at most, Dirichlet on both
+//     axes, arith 0 / 1, no statistics, no wave-pair kernel, depths to the family's.
+//   walls (insulated or Robin axes) under a general launch: Ins, or Rob with a
+//     Robin axis; an interior launch keeps tb_kernel (launch_rects carves the
+//     frame-column strips out of it).
+//   else Pipe / Stats / Plain as asked.
+Family select_family(DType dt, int k, const TbTerms& t, bool main, bool partials, bool pipe) {
+  const int bc = t.bc, arith = t.arith;
+  HEAT2D_REQUIRE((bc & ~kBcAll) == 0,
+                 "bc must be a set of kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY | kBcRobinX | kBcRobinY");
+  HEAT2D_REQUIRE(!((bc & kBcPeriodicX) && (bc & kBcInsulatedX)) && !((bc & kBcPeriodicY) && (bc & kBcInsulatedY)),
+                 "an axis is periodic or insulated, not both");
+  HEAT2D_REQUIRE(!((bc & kBcRobinX) && (bc & (kBcPeriodicX | kBcInsulatedX))) &&
+                     !((bc & kBcRobinY) && (bc & (kBcPeriodicY | kBcInsulatedY))),
+                 "an axis has one boundary kind: Robin, periodic or insulated");
+  Family fam = Family::Plain;
+  const char *dirichlet = nullptr, *alone = nullptr;  // the family's messages for a bc / for statistics or pipe
+  if (t.rx || t.ry) {
+    HEAT2D_REQUIRE(t.rx && t.ry, "face coefficients need both buffers (rx and ry)");
+    HEAT2D_REQUIRE(!t.source && !t.rmap, "face coefficients with a heat source or a diffusivity map: no kernel carries them together");
+    fam = Family::Div;
+    dirichlet = "face coefficients need Dirichlet boundaries on both axes";
+    alone = "face coefficients have no fused-statistics and no wave-pair kernel";
+  } else if (t.rmap) {
+    HEAT2D_REQUIRE(!t.source, "a diffusivity map and a heat source in one launch: no kernel carries both rings");
+    fam = Family::Var;
+    dirichlet = "a diffusivity map needs Dirichlet boundaries on both axes";
+    alone = "a diffusivity map has no fused-statistics and no wave-pair kernel";
+  } else if (t.source) {
+    fam = t.gain.g ? Family::Gain : Family::Src;  // (the source scaled per step: tb_kernel_gain, the same launch shape)
+    dirichlet = "a heat source needs Dirichlet boundaries on both axes";
+    alone = "a heat source has no fused-statistics and no wave-pair kernel";
+  }
+  if (fam != Family::Plain) {
+    HEAT2D_REQUIRE(bc == 0, dirichlet);
+    HEAT2D_REQUIRE(!partials && !pipe, alone);
+  }
+  HEAT2D_REQUIRE(!t.gain.g || (t.source && t.gain.pos), "a gain schedule needs a heat source and its position word");
+  if (fam == Family::Plain) {
+    HEAT2D_REQUIRE(!pipe || (main && !partials && pipe_available(dt, k, arith)), "no wave-pair kernel for this launch");
+    HEAT2D_REQUIRE(!(pipe && (bc & kBcWallY)), "insulated y: the wave-pair kernel's wide strips are not carved (no pipe plans)");
+    HEAT2D_REQUIRE(!(partials && (bc & kBcPeriodicY)), "the fused-statistics kernel has no periodic y");
+    // (interior launches: launch_rects keeps the walls out of them)
+    if (!main && ins_edges(bc)) {
+      HEAT2D_REQUIRE(!partials, "the fused-statistics kernel has no insulated boundaries");
+      HEAT2D_REQUIRE(arith != 3, "insulated boundaries have no arith 3 (fast) kernels");
+      fam = (bc & kBcRobin) ? Family::Rob : Family::Ins;  // a Robin axis: every wall of the launch on tb_kernel_rob
+    } else if (pipe) {
+      fam = Family::Pipe;
+    } else if (partials) {
+      fam = Family::Stats;
+    }
+  }
+  if (bc & kBcRobin) {  // (interior launches too: the frame fills behind them take the pairs)
+    HEAT2D_REQUIRE(t.robin, "a Robin axis needs the walls' pairs (robin)");
+    HEAT2D_REQUIRE(arith == 0 || arith == 1, "Robin walls need arith 0 (exact) or 1 (fma)");
+    HEAT2D_REQUIRE(k <= kMaxTBRob, "temporal depth exceeds the Robin-wall kernels' deepest pass (kMaxTBRob)");
+  }
+  if (const FamilyInfo* f = family_info(fam)) {
+    HEAT2D_REQUIRE(!f->too_deep || k <= f->max_k, f->too_deep);
+    HEAT2D_REQUIRE(arith >= 0 && arith <= f->max_arith, f->no_form);
+  }
+  return fam;
 }
 
 // The frame entries the launchers keep behind a stencil launch over `rects`:
@@ -344,12 +468,14 @@ int occupancy_div(DType dt, int k, int arith) {
 // frame row of a slab at the wall — one fill per run of rows the rects cover
 // (rects of one launch share rows strip by strip, or are disjoint bands):
 // never a row another launch writes. Same stream as the launch.
-// With a Robin axis (robin != nullptr) every wall's frame entries are ghost
-// values in the form `arith` names (an insulated axis beside it: (1, -0.0), the
+// With a Robin axis every wall's frame entries are ghost values (t.robin's
+// pairs) in the form t.arith names (an insulated axis beside it: (1, -0.0), the
 // image), the wall rows first and then the wall columns over the frame rows
 // just written too: the golden's x first, then y over the filled rows.
-void fill_frames(DType dt, void* dst, const SlabLayout& L0, const TbRect* rects, int nrect, int bc,
-                 hipStream_t stream, const double* robin = nullptr, int arith = 0) {
+void fill_frames(DType dt, void* dst, const SlabLayout& L0, const TbRect* rects, int nrect, const TbTerms& t,
+                 hipStream_t stream) {
+  const int bc = t.bc, arith = t.arith;
+  const double* robin = t.robin;
   if (!(bc & (kBcPeriodicY | kBcWallX | kBcWallY))) return;
   int64_t lo[2 * kMaxRects], hi[2 * kMaxRects];
   int n = 0;
@@ -394,72 +520,31 @@ void fill_frames(DType dt, void* dst, const SlabLayout& L0, const TbRect* rects,
       launch_ins_rows(dt, dst, L0, lo[j] <= 0 && hi[j] > 0, lo[j] < L0.nrows && hi[j] >= L0.nrows, stream);
 }
 
-// Launch `rects` (item counts from their nb and strip ranges) on `nwaves` waves.
-// partials != nullptr: the fused-statistics kernel (general, ring 4). Returns the waves launched.
-// bc: kernels.hpp kBcPeriodicX / ... / kBcInsulatedY; L is the slab's own
-// layout (the kernels see bc_layout(L, bc)). Insulated edges: a general launch
-// runs tb_kernel_ins (ring 4, whatever `ring` says) with the insulated edges as
-// its extra argument. The frame entries are refreshed by the caller (launch_rects).
-// source != nullptr (a buffer in the field's layout, Dirichlet axes only):
-// every launch, interior ones too, runs tb_kernel_src (general, ring 4) on at
-// most as many waves as that kernel keeps resident.
+// Launch `rects` (item counts from their nb and strip ranges) on `nwaves` waves of
+// the kernel family `fam` (select_family's answer for this launch; Stats: the
+// per-wave partials go to `partials`). Returns the waves launched.
+// L is the slab's own layout (the kernels see bc_layout(L, t.bc)). The feature
+// families run ring 4 whatever `ring` says; the ones that take every rect
+// (FamilyInfo::every_rect) run interior launches on their general kernel too, on at
+// most as many waves as it keeps resident. The frame entries are refreshed by the
+// caller (launch_rects).
 int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
-                       const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
-                       double* partials, uint32_t* queue, int bc, bool pipe, const void* source = nullptr,
-                       const void* rmap = nullptr, const void* rx = nullptr, const void* ry = nullptr,
-                       GainRef gain = {}, const double* robin = nullptr) {
-  // rx / ry != nullptr (the per-face diffusion numbers in the field's layout; Dirichlet axes only):
-  // every launch, interior ones too, runs tb_kernel_div (ring 4, the general kernel's four edge kinds)
-  // on at most as many waves as that kernel keeps resident; `r` is not used.
-  const bool faces = rx || ry;
-  if (faces) {
-    HEAT2D_REQUIRE(rx && ry, "face coefficients need both buffers (rx and ry)");
-    HEAT2D_REQUIRE(!source && !rmap, "face coefficients with a heat source or a diffusivity map: no kernel carries them together");
-    HEAT2D_REQUIRE(bc == 0, "face coefficients need Dirichlet boundaries on both axes");
-    HEAT2D_REQUIRE(!partials && !pipe, "face coefficients have no fused-statistics and no wave-pair kernel");
-    HEAT2D_REQUIRE(k <= kMaxTBDiv, "temporal depth exceeds the conservative-form kernels' deepest pass (kMaxTBDiv)");
-    nwaves = std::min<int64_t>(nwaves, (int64_t)cu_count() * occupancy_div(dt, k, arith));
+                       const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, const TbTerms& t,
+                       Family fam, double* partials, uint32_t* queue) {
+  const int bc = t.bc, arith = t.arith;
+  const FamilyInfo* fi = family_info(fam);
+  const bool pipe = fam == Family::Pipe, every_rect = fi && fi->every_rect;
+  if (every_rect) {
+    nwaves = std::min<int64_t>(nwaves, (int64_t)cu_count() * fi->occupancy(*fi, dt, k, arith));
     main = false;
   }
-  // rmap != nullptr (the per-point diffusion number in the field's layout, +0.0 at every pinned
-  // point; Dirichlet axes only): every launch, interior ones too, runs tb_kernel_var (ring 4) on at
-  // most as many waves as that kernel keeps resident; `r` is not used.
-  if (rmap) {
-    HEAT2D_REQUIRE(!source, "a diffusivity map and a heat source in one launch: no kernel carries both rings");
-    HEAT2D_REQUIRE(bc == 0, "a diffusivity map needs Dirichlet boundaries on both axes");
-    HEAT2D_REQUIRE(!partials && !pipe, "a diffusivity map has no fused-statistics and no wave-pair kernel");
-    HEAT2D_REQUIRE(k <= kMaxTBVar, "temporal depth exceeds the diffusivity-map kernels' deepest pass (kMaxTBVar)");
-    nwaves = std::min<int64_t>(nwaves, (int64_t)cu_count() * occupancy_var(dt, k, arith));
-    main = false;
-  }
-  if (source) {
-    HEAT2D_REQUIRE(bc == 0, "a heat source needs Dirichlet boundaries on both axes");
-    HEAT2D_REQUIRE(!partials && !pipe, "a heat source has no fused-statistics and no wave-pair kernel");
-    HEAT2D_REQUIRE(k <= kMaxTBSrc, "temporal depth exceeds the heat-source kernels' deepest pass (kMaxTBSrc)");
-    // (with a gain schedule the launch runs tb_kernel_gain: that instance's own occupancy)
-    nwaves = std::min<int64_t>(nwaves, (int64_t)cu_count() * (gain.g ? occupancy_gain(dt, k, arith) : occupancy_src(dt, k, arith)));
-    main = false;
-  }
-  HEAT2D_REQUIRE(!gain.g || (source && gain.pos), "a gain schedule needs a heat source and its position word");
   HEAT2D_REQUIRE(nrect >= 1 && nrect <= (main ? kMainRects : kMaxRects), "bad rect count");
-  HEAT2D_REQUIRE(!pipe || (main && !partials && pipe_available(dt, k, arith)), "no wave-pair kernel for this launch");
   const int ins = main ? 0 : ins_edges(bc);  // (interior launches: launch_rects keeps insulated edges out of them)
-  if (ins) {
-    HEAT2D_REQUIRE(!partials, "the fused-statistics kernel has no insulated boundaries");
-    HEAT2D_REQUIRE(arith != 3, "insulated boundaries have no arith 3 (fast) kernels");
-  }
-  const bool rob = ins && (bc & kBcRobin);  // a Robin axis: every wall of the launch on tb_kernel_rob
-  if (bc & kBcRobin) {
-    HEAT2D_REQUIRE(robin, "a Robin axis needs the walls' pairs (robin)");
-    HEAT2D_REQUIRE(arith == 0 || arith == 1, "Robin walls need arith 0 (exact) or 1 (fma)");
-    HEAT2D_REQUIRE(k <= kMaxTBRob, "temporal depth exceeds the Robin-wall kernels' deepest pass (kMaxTBRob)");
-  }
   const SlabLayout L = bc_layout(L0, bc);
   check_layout(dt, L, k);  // (the shifted rows must still fit the march's 32-bit row index)
   if (bc & kBcPeriodicY) {
     HEAT2D_REQUIRE(L0.ncols >= kWrapCols, "periodic y needs at least kWrapCols (24) owned columns");
     HEAT2D_REQUIRE(L0.cpad == kColPad && L0.col_hi() - L0.ncols >= kColPad, "periodic y needs make_layout's padding");
-    HEAT2D_REQUIRE(!partials, "the fused-statistics kernel has no periodic y");
   }
   TbArgs a{};
   a.pitch = L.pitch;
@@ -487,9 +572,9 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
   a.nitems = items;
   a.nwaves = std::max<int64_t>(1, std::min<int64_t>(nwaves, items));
   a.partials = partials;
-  // (the pair kernel and the heat-source kernel record no wave times: HEAT2D_WAVE_TIMES keeps
-  // the last other launch's)
-  a.wtimes = (pipe || source || rmap || faces) ? nullptr : wave_times_buf(a.nwaves);  // (nor the map / face kernels)
+  // (the pair kernel and the one-wave feature kernels record no wave times: HEAT2D_WAVE_TIMES
+  // keeps the last other launch's)
+  a.wtimes = (pipe || every_rect) ? nullptr : wave_times_buf(a.nwaves);
   if (arith == 3) {  // scaled levels (tb_impl.hpp AR 3): coefficients of this depth, in double
     HEAT2D_REQUIRE(r > 0.0, "arith 3 (fast) needs r > 0");
     a.fb = (1.0 - 4.0 * r) / r;
@@ -508,75 +593,9 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
       dispatch_pipe<decltype(ar)::value>(k, (unsigned)((a.nwaves + 1) / 2), static_cast<const double*>(src) + o,
                                          static_cast<double*>(dst) + o, a, r, status, stream);
     });
-  } else if (faces) {
-    if (dt == DType::F32) {
-      const float *s32 = static_cast<const float*>(src) + o, *x32 = static_cast<const float*>(rx) + o,
-                  *y32 = static_cast<const float*>(ry) + o;
-      if (arith == 1) dispatch_div<float, 1>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, x32, y32, stream);
-      else dispatch_div<float, 0>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, x32, y32, stream);
-    } else {
-      const double *s64 = static_cast<const double*>(src) + o, *x64 = static_cast<const double*>(rx) + o,
-                   *y64 = static_cast<const double*>(ry) + o;
-      if (arith == 1) dispatch_div<double, 1>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, x64, y64, stream);
-      else dispatch_div<double, 0>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, x64, y64, stream);
-    }
-  } else if (rmap) {
-    if (dt == DType::F32) {
-      const float *s32 = static_cast<const float*>(src) + o, *m32 = static_cast<const float*>(rmap) + o;
-      if (arith == 1) dispatch_var<float, 1>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, m32, stream);
-      else dispatch_var<float, 0>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, m32, stream);
-    } else {
-      const double *s64 = static_cast<const double*>(src) + o, *m64 = static_cast<const double*>(rmap) + o;
-      if (arith == 1) dispatch_var<double, 1>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, m64, stream);
-      else dispatch_var<double, 0>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, m64, stream);
-    }
-  } else if (source && gain.g) {  // the source scaled per step: tb_kernel_gain, the same launch shape
-    if (dt == DType::F32) {
-      const float *s32 = static_cast<const float*>(src) + o, *q32 = static_cast<const float*>(source) + o;
-      const float* g32 = static_cast<const float*>(gain.g);
-      if (arith == 1) dispatch_gain<float, 1>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, (float)r, q32, g32, gain.pos, stream);
-      else dispatch_gain<float, 0>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, (float)r, q32, g32, gain.pos, stream);
-    } else {
-      const double *s64 = static_cast<const double*>(src) + o, *q64 = static_cast<const double*>(source) + o;
-      const double* g64 = static_cast<const double*>(gain.g);
-      if (arith == 1) dispatch_gain<double, 1>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, r, q64, g64, gain.pos, stream);
-      else dispatch_gain<double, 0>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, r, q64, g64, gain.pos, stream);
-    }
-  } else if (source) {
-    if (dt == DType::F32) {
-      const float *s32 = static_cast<const float*>(src) + o, *q32 = static_cast<const float*>(source) + o;
-      if (arith == 1) dispatch_src<float, 1>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, (float)r, q32, stream);
-      else dispatch_src<float, 0>(k, (unsigned)a.nwaves, s32, static_cast<float*>(dst) + o, a, (float)r, q32, stream);
-    } else {
-      const double *s64 = static_cast<const double*>(src) + o, *q64 = static_cast<const double*>(source) + o;
-      if (arith == 1) dispatch_src<double, 1>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, r, q64, stream);
-      else dispatch_src<double, 0>(k, (unsigned)a.nwaves, s64, static_cast<double*>(dst) + o, a, r, q64, stream);
-    }
-  } else if (rob) {
-    if (dt == DType::F32) {
-      const float *s32 = static_cast<const float*>(src) + o;
-      const RobCoef<float> g = rob_coef<float>(bc, robin);
-      if (arith == 1) dispatch_rob<float, 1>(k, nblocks, s32, static_cast<float*>(dst) + o, a, (float)r, ins, g, stream);
-      else dispatch_rob<float, 0>(k, nblocks, s32, static_cast<float*>(dst) + o, a, (float)r, ins, g, stream);
-    } else {
-      const double *s64 = static_cast<const double*>(src) + o;
-      const RobCoef<double> g = rob_coef<double>(bc, robin);
-      if (arith == 1) dispatch_rob<double, 1>(k, nblocks, s64, static_cast<double*>(dst) + o, a, r, ins, g, stream);
-      else dispatch_rob<double, 0>(k, nblocks, s64, static_cast<double*>(dst) + o, a, r, ins, g, stream);
-    }
-  } else if (ins) {
-    with_ar(arith, [&](auto ar) {
-      constexpr int AR = decltype(ar)::value;
-      if constexpr (AR != 3) {
-        if (dt == DType::F32)
-          dispatch_ins<float, AR>(k, nblocks, static_cast<const float*>(src) + o, static_cast<float*>(dst) + o, a,
-                                  (float)r, ins, stream);
-        else
-          dispatch_ins<double, AR>(k, nblocks, static_cast<const double*>(src) + o, static_cast<double*>(dst) + o, a,
-                                   r, ins, stream);
-      }
-    });
-  } else if (partials) {
+  } else if (fi) {
+    fi->launch(*fi, dt, k, t, src, dst, o, a, r, ins, stream);
+  } else if (fam == Family::Stats) {
     HEAT2D_REQUIRE(a.nwaves <= max_stats_waves(), "statistics partials buffer too small");
     const float* s32 = static_cast<const float*>(src) + o;
     const double* s64 = static_cast<const double*>(src) + o;
@@ -606,26 +625,18 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
 // rects of tb_kernel_ins, on the same stream right behind it (disjoint
 // columns of the same rows).
 int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0, int k, int ring, bool main,
-                     const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, int arith,
-                     double* partials = nullptr, uint32_t* queue = nullptr, int bc = 0, bool pipe = false,
-                     const void* source = nullptr, const void* rmap = nullptr, const void* rx = nullptr,
-                     const void* ry = nullptr, GainRef gain = {}, const double* robin = nullptr) {
-  HEAT2D_REQUIRE((bc & ~kBcAll) == 0,
-                 "bc must be a set of kBcPeriodicX | kBcPeriodicY | kBcInsulatedX | kBcInsulatedY | kBcRobinX | kBcRobinY");
-  HEAT2D_REQUIRE(!((bc & kBcPeriodicX) && (bc & kBcInsulatedX)) && !((bc & kBcPeriodicY) && (bc & kBcInsulatedY)),
-                 "an axis is periodic or insulated, not both");
-  HEAT2D_REQUIRE(!((bc & kBcRobinX) && (bc & (kBcPeriodicX | kBcInsulatedX))) &&
-                     !((bc & kBcRobinY) && (bc & (kBcPeriodicY | kBcInsulatedY))),
-                 "an axis has one boundary kind: Robin, periodic or insulated");
+                     const TbRect* rects, int nrect, int64_t nwaves, double r, hipStream_t stream, const TbTerms& t,
+                     double* partials = nullptr, uint32_t* queue = nullptr, bool pipe = false) {
+  const int bc = t.bc;
+  const Family fam = select_family(dt, k, t, main, partials != nullptr, pipe);
   if (!(main && (bc & kBcWallY))) {
-    const int64_t nw = launch_rects_1(dt, src, dst, L0, k, ring, main, rects, nrect, nwaves, r, stream, arith, partials,
-                                      queue, bc, pipe, source, rmap, rx, ry, gain, robin);
-    fill_frames(dt, dst, L0, rects, nrect, bc, stream, robin, arith);
+    const int64_t nw = launch_rects_1(dt, src, dst, L0, k, ring, main, rects, nrect, nwaves, r, stream, t, fam, partials, queue);
+    fill_frames(dt, dst, L0, rects, nrect, t, stream);
     return nw;
   }
-  HEAT2D_REQUIRE(!source && !rmap && !rx && !ry,
-                 "a heat source / diffusivity map / face coefficients need Dirichlet boundaries on both axes");
-  HEAT2D_REQUIRE(!pipe, "insulated y: the wave-pair kernel's wide strips are not carved (no pipe plans)");
+  // (walls: select_family has let no source, map, faces, statistics or pipe through)
+  const Family frame_fam = select_family(dt, k, t, false, false, false);
+  const FamilyInfo* ff = family_info(frame_fam);
   HEAT2D_REQUIRE(nrect >= 1 && nrect <= kMainRects, "bad rect count");
   const int64_t U = useful_width(dt, k);
   const int64_t ns = (bc_layout(L0, bc).ncols + U - 1) / U;
@@ -635,7 +646,7 @@ int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0,
   const int64_t KA = halo_cols(dt, k), ncols = bc_layout(L0, bc).ncols;
   int64_t sF = ns;
   while (sF > 1 && (sF - 1) * U + U + KA > ncols) --sF;
-  const int64_t slots = (int64_t)cu_count() * ((bc & kBcRobin) ? occupancy_rob(dt, k, arith) : occupancy_ins(dt, k, arith)) * 4;
+  const int64_t slots = (int64_t)cu_count() * ff->occupancy(*ff, dt, k, t.arith) * ff->waves;
   TbRect in[kMainRects], fr[2 * kMainRects];
   int ni = 0, nf = 0;
   for (int i = 0; i < nrect; ++i) {
@@ -657,13 +668,11 @@ int64_t launch_rects(DType dt, const void* src, void* dst, const SlabLayout& L0,
                         R.nb > 0 ? R.nb : -std::min<int64_t>(rows * (i1 - i0), std::max<int64_t>(1, -R.nb - q * (w - (i1 - i0))))};
   }
   int64_t nw = 0;
-  if (ni > 0)
-    nw = launch_rects_1(dt, src, dst, L0, k, ring, true, in, ni, nwaves, r, stream, arith, nullptr, queue, bc, false,
-                        nullptr, nullptr, nullptr, nullptr, {}, robin);
+  if (ni > 0) nw = launch_rects_1(dt, src, dst, L0, k, ring, true, in, ni, nwaves, r, stream, t, fam, nullptr, queue);
   for (int i = 0; i < nf; i += kMaxRects)
-    launch_rects_1(dt, src, dst, L0, k, 4, false, fr + i, std::min(nf - i, kMaxRects), slots, r, stream, arith, nullptr,
-                   nullptr, bc, false, nullptr, nullptr, nullptr, nullptr, {}, robin);
-  fill_frames(dt, dst, L0, rects, nrect, bc, stream, robin, arith);
+    launch_rects_1(dt, src, dst, L0, k, 4, false, fr + i, std::min(nf - i, kMaxRects), slots, r, stream, t, frame_fam,
+                   nullptr, nullptr);
+  fill_frames(dt, dst, L0, rects, nrect, t, stream);
   return nw;
 }
 
@@ -710,22 +719,18 @@ TbPlan plan_tb(DType dt, const SlabLayout& L, int64_t row_begin, int64_t row_end
 }
 
 void launch_tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_begin, int64_t row_end, int k,
-               double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc, const void* source,
-               const void* rmap, const void* rx, const void* ry, GainRef gain, const double* robin) {
-  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, arith, bc, source, rmap, rx, ry, gain,
-             robin);
+               double r, hipStream_t stream, int64_t tile_rows, int cus, const TbTerms& t) {
+  launch_tb2(dt, src, dst, L, row_begin, row_end, 0, 0, k, r, stream, tile_rows, cus, t);
 }
 
 void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t rb0, int64_t re0, int64_t rb1,
-                int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows, int cus, int arith, int bc,
-                const void* source, const void* rmap, const void* rx, const void* ry, GainRef gain,
-                const double* robin) {
+                int64_t re1, int k, double r, hipStream_t stream, int64_t tile_rows, int cus, const TbTerms& t) {
   check_layout(dt, L, k);
   const int64_t n0 = std::max<int64_t>(0, re0 - rb0), n1 = std::max<int64_t>(0, re1 - rb1);
   if (n0 + n1 == 0) return;
   // plan over the concatenated rows, then give each range its share of bands
   // (strips of the grid the kernels see)
-  const TbPlan p = plan_tb(dt, bc_layout(L, bc), 0, std::min<int64_t>(n0 + n1, L.nrows), k, tile_rows, cus, arith);
+  const TbPlan p = plan_tb(dt, bc_layout(L, t.bc), 0, std::min<int64_t>(n0 + n1, L.nrows), k, tile_rows, cus, t.arith);
   TbRect rects[2];
   int nr = 0;
   if (p.ntiles < 0) {  // segments, shared out over the two ranges by rows
@@ -733,8 +738,7 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
     const int64_t s0 = n1 == 0 ? ns : (n0 == 0 ? 0 : std::max<int64_t>(1, (ns * n0 + (n0 + n1) / 2) / (n0 + n1)));
     if (n0 > 0) rects[nr++] = TbRect{rb0, re0, 0, p.nstrips, -std::min<int64_t>(s0, n0 * p.nstrips)};
     if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, -std::min<int64_t>(std::max<int64_t>(1, ns - s0), n1 * p.nstrips)};
-    launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, p.nwaves, r, stream, arith, nullptr, nullptr, bc,
-                 false, source, rmap, rx, ry, gain, robin);
+    launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, p.nwaves, r, stream, t);
     return;
   }
   const int64_t nb = std::max<int64_t>(p.ntiles, (n0 > 0) + (n1 > 0));
@@ -742,8 +746,7 @@ void launch_tb2(DType dt, const void* src, void* dst, const SlabLayout& L, int64
   if (n0 > 0) rects[nr++] = TbRect{rb0, re0, 0, p.nstrips, std::min<int64_t>(nb0, n0)};
   if (n1 > 0) rects[nr++] = TbRect{rb1, re1, 0, p.nstrips, std::min<int64_t>(nb - nb0, n1)};
   const int64_t slots = (int64_t)(cus > 0 ? cus : cu_count()) * p.blocks_per_cu * 4;
-  launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, slots, r, stream, arith, nullptr, nullptr, bc, false,
-               source, rmap, rx, ry, gain, robin);
+  launch_rects(dt, src, dst, L, k, p.prefetch, false, rects, nr, slots, r, stream, t);
 }
 
 // r = 1/4 kernels (arith 2): an interior item costs 3 adds + 2 DPP moves per
@@ -992,7 +995,10 @@ void launch_tb_stats(DType dt, const void* src, void* dst, const SlabLayout& L, 
   const int64_t nb = std::max<int64_t>(
       1, std::min<int64_t>(choose_bands(L.nrows, ns, balance_units(dt, 0, occupancy_stats(dt, k, arith)), k), L.nrows));
   const TbRect rect{0, L.nrows, 0, ns, nb};
-  const int64_t nw = launch_rects(dt, src, dst, L, k, 4, false, &rect, 1, slots, r, stream, arith, partials, nullptr, bc);
+  TbTerms t;
+  t.arith = arith;
+  t.bc = bc;
+  const int64_t nw = launch_rects(dt, src, dst, L, k, 4, false, &rect, 1, slots, r, stream, t, partials);
   launch_reduce_partials(partials, nw, out6, stream);
 }
 
@@ -1017,41 +1023,35 @@ bool edge_rect_on_main(const SlabLayout& L, const SplitPlan& p, int i) {
 }
 
 void launch_edge_rect(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, int i, double r,
-                      hipStream_t stream, int arith, int bc, const void* source, const void* rmap, const void* rx,
-                      const void* ry, GainRef gain, const double* robin) {
+                      hipStream_t stream, const TbTerms& t) {
   HEAT2D_REQUIRE(i >= 0 && i < p.nedge, "edge rect index");
   const TbRect& R = p.edge[i];
-  const bool on_main = edges_on_main(bc_layout(L, bc), p.k, &R, 1);
+  const bool on_main = edges_on_main(bc_layout(L, t.bc), p.k, &R, 1);
   const int64_t items = R.nb > 0 ? R.nb * (R.s1 - R.s0) : -R.nb;
-  const int64_t slots = (int64_t)cu_count() * occupancy(dt, p.ring, on_main, p.k, arith) * 4;
-  launch_rects(dt, src, dst, L, p.k, p.ring, on_main, &R, 1, std::min<int64_t>(items, slots), r, stream, arith,
-               nullptr, nullptr, bc, false, source, rmap, rx, ry, gain, robin);
+  const int64_t slots = (int64_t)cu_count() * occupancy(dt, p.ring, on_main, p.k, t.arith) * 4;
+  launch_rects(dt, src, dst, L, p.k, p.ring, on_main, &R, 1, std::min<int64_t>(items, slots), r, stream, t);
 }
 
 void launch_split(DType dt, const void* src, void* dst, const SlabLayout& L, const SplitPlan& p, bool main_part,
-                  double r, hipStream_t stream, int arith, uint32_t* queue, int bc, const void* source,
-                  const void* rmap, const void* rx, const void* ry, GainRef gain, const double* robin) {
-  HEAT2D_REQUIRE(!(rx || ry) || !(p.flags & kPlanPipe), "face coefficients have no wave-pair kernel (no pipe plans)");
-  HEAT2D_REQUIRE(!source || !(p.flags & kPlanPipe), "a heat source has no wave-pair kernel (no pipe plans)");
-  HEAT2D_REQUIRE(!rmap || !(p.flags & kPlanPipe), "a diffusivity map has no wave-pair kernel (no pipe plans)");
+                  double r, hipStream_t stream, const TbTerms& t, uint32_t* queue) {
   // (SplitPlan::flags & kPlanDynamic: the main part takes its items from the dynamic queue)
   uint32_t* q = (p.flags & kPlanDynamic) ? queue : nullptr;
   HEAT2D_REQUIRE(p.valid, "invalid split plan");
+  const bool pipe = (p.flags & kPlanPipe) != 0;
+  // a pipe plan: either part is rejected with the terms its main launch rejects
+  if (pipe) select_family(dt, p.k, t, true, false, true);
   // the main part: p.main, or its frame-strip-weighted rects (weight_main)
   const TbRect* mr = p.nrects > 0 ? p.rects : &p.main;
   const int nm = p.nrects > 0 ? p.nrects : 1;
   if (p.valid == 2) {  // single general launch over the whole slab (no edge part)
-    if (main_part)
-      launch_rects(dt, src, dst, L, p.k, p.ring, false, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc, false,
-                   source, rmap, rx, ry, gain, robin);
+    if (main_part) launch_rects(dt, src, dst, L, p.k, p.ring, false, mr, nm, p.main_waves, r, stream, t, nullptr, q);
     return;
   }
   if (main_part)
-    launch_rects(dt, src, dst, L, p.k, p.ring, true, mr, nm, p.main_waves, r, stream, arith, nullptr, q, bc,
-                 (p.flags & kPlanPipe) != 0, source, rmap, rx, ry, gain, robin);
+    launch_rects(dt, src, dst, L, p.k, p.ring, true, mr, nm, p.main_waves, r, stream, t, nullptr, q, pipe);
   else
-    launch_rects(dt, src, dst, L, p.k, p.ring, edges_on_main(bc_layout(L, bc), p.k, p.edge, p.nedge), p.edge, p.nedge,
-                 p.edge_waves, r, stream, arith, nullptr, nullptr, bc, false, source, rmap, rx, ry, gain, robin);
+    launch_rects(dt, src, dst, L, p.k, p.ring, edges_on_main(bc_layout(L, t.bc), p.k, p.edge, p.nedge), p.edge, p.nedge,
+                 p.edge_waves, r, stream, t);
 }
 
 }  // namespace kern

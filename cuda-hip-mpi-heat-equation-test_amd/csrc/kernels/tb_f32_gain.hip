@@ -6,8 +6,8 @@
 namespace heat2d {
 namespace kern {
 namespace tbimpl {
-H2D_GAIN_UNIT(float, 0)
-H2D_GAIN_UNIT(float, 1)
+H2D_FEAT_UNIT(FamGain, float, 0, H2D_NO_CASES)
+H2D_FEAT_UNIT(FamGain, float, 1, H2D_NO_CASES)
 }  // namespace tbimpl
 }  // namespace kern
 }  // namespace heat2d

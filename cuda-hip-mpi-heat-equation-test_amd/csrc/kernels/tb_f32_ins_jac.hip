@@ -5,7 +5,7 @@
 namespace heat2d {
 namespace kern {
 namespace tbimpl {
-H2D_INS_UNIT(float, 2, H2D_TB_CASES_F32DEEP)
+H2D_FEAT_UNIT(FamIns, float, 2, H2D_TB_CASES_F32DEEP)
 }  // namespace tbimpl
 }  // namespace kern
 }  // namespace heat2d

@@ -5,7 +5,7 @@
 namespace heat2d {
 namespace kern {
 namespace tbimpl {
-H2D_VAR_UNIT(float, 1)
+H2D_FEAT_UNIT(FamVar, float, 1, H2D_NO_CASES)
 }  // namespace tbimpl
 }  // namespace kern
 }  // namespace heat2d

@@ -5,7 +5,7 @@
 namespace heat2d {
 namespace kern {
 namespace tbimpl {
-H2D_DIV_UNIT(double, 0)
+H2D_FEAT_UNIT(FamDiv, double, 0, H2D_NO_CASES)
 }  // namespace tbimpl
 }  // namespace kern
 }  // namespace heat2d

@@ -6,8 +6,8 @@
 namespace heat2d {
 namespace kern {
 namespace tbimpl {
-H2D_GAIN_UNIT(double, 0)
-H2D_GAIN_UNIT(double, 1)
+H2D_FEAT_UNIT(FamGain, double, 0, H2D_NO_CASES)
+H2D_FEAT_UNIT(FamGain, double, 1, H2D_NO_CASES)
 }  // namespace tbimpl
 }  // namespace kern
 }  // namespace heat2d

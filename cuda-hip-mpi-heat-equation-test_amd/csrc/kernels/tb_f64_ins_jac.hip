@@ -5,7 +5,7 @@
 namespace heat2d {
 namespace kern {
 namespace tbimpl {
-H2D_INS_UNIT(double, 2, H2D_TB_CASES_DEEP)
+H2D_FEAT_UNIT(FamIns, double, 2, H2D_TB_CASES_DEEP)
 }  // namespace tbimpl
 }  // namespace kern
 }  // namespace heat2d

@@ -5,7 +5,7 @@
 namespace heat2d {
 namespace kern {
 namespace tbimpl {
-H2D_ROB_UNIT(double, 1, H2D_TB_CASES_DEEP)
+H2D_FEAT_UNIT(FamRob, double, 1, H2D_TB_CASES_DEEP)
 }  // namespace tbimpl
 }  // namespace kern
 }  // namespace heat2d

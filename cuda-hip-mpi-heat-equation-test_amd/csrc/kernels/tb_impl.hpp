@@ -483,10 +483,16 @@ template <typename T, int K>
 struct GainState<T, K, true> {
   T gs[K];  // gs[s - 1]: the gain of level s
 };
-template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false,
-          bool SRC = false, bool VAR = false, bool DIV = false, bool GAIN = false, bool ROB = false>
-struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, DIV>, GainState<T, K, GAIN>,
-               RobState<T, ROB> {
+// The features of a march, one bit each (FEAT, the last template argument of
+// March, MarchF32 and march<>): the sections INS .. GAIN above.
+constexpr int kFeatIns = 1, kFeatSrc = 2, kFeatVar = 4, kFeatDiv = 8, kFeatGain = 16, kFeatRob = 32;
+constexpr bool feat_has(int feat, int bit) { return (feat & bit) != 0; }
+template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, int CL = K, int FEAT = 0>
+struct March : WallState<feat_has(FEAT, kFeatIns)>, SrcState<K, RING, feat_has(FEAT, kFeatSrc | kFeatVar)>,
+               DivState<K, RING, feat_has(FEAT, kFeatDiv)>, GainState<T, K, feat_has(FEAT, kFeatGain)>,
+               RobState<T, feat_has(FEAT, kFeatRob)> {
+  static constexpr bool INS = feat_has(FEAT, kFeatIns), SRC = feat_has(FEAT, kFeatSrc), VAR = feat_has(FEAT, kFeatVar),
+                        DIV = feat_has(FEAT, kFeatDiv), GAIN = feat_has(FEAT, kFeatGain), ROB = feat_has(FEAT, kFeatRob);
   static_assert(!ROB || (INS && (AR == 0 || AR == 1) && !SRC && !VAR && !DIV),
                 "Robin walls: the insulated march's substitution sites, unscaled arithmetic, no source, map or faces");
   using S = TbShape<T, NV, K>;
@@ -907,9 +913,12 @@ struct March : WallState<INS>, SrcState<K, RING, SRC || VAR>, DivState<K, RING, 
 // SRC: a source row sits in LDS in the even/odd order (c0, c2, c1, c3), so a
 // level adds it with two packed adds (see SrcState).
 // VAR: a map row sits there in the same order and is the Row `re` of the level.
-template <int K, int EK, int RING, int AR, bool ST = false, int CL = K, bool INS = false, bool SRC = false,
-          bool VAR = false, bool GAIN = false, bool ROB = false>
-struct MarchF32 : WallState<INS>, SrcState<K, RING, SRC || VAR>, GainState<float, K, GAIN>, RobState<float, ROB> {
+template <int K, int EK, int RING, int AR, bool ST = false, int CL = K, int FEAT = 0>
+struct MarchF32 : WallState<feat_has(FEAT, kFeatIns)>, SrcState<K, RING, feat_has(FEAT, kFeatSrc | kFeatVar)>,
+                  GainState<float, K, feat_has(FEAT, kFeatGain)>, RobState<float, feat_has(FEAT, kFeatRob)> {
+  static_assert(!feat_has(FEAT, kFeatDiv), "face coefficients run the element-wise march");
+  static constexpr bool INS = feat_has(FEAT, kFeatIns), SRC = feat_has(FEAT, kFeatSrc), VAR = feat_has(FEAT, kFeatVar),
+                        GAIN = feat_has(FEAT, kFeatGain), ROB = feat_has(FEAT, kFeatRob);
   static_assert(!ROB || (INS && (AR == 0 || AR == 1) && !SRC && !VAR),
                 "Robin walls: the insulated march's substitution sites, unscaled arithmetic, no source or map");
   using F2 = float __attribute__((ext_vector_type(2)));
@@ -1281,12 +1290,22 @@ constexpr bool kPackedF32 = false;
 // Insulated edges of the grid (tb_kernel_ins's extra argument; March INS)
 constexpr int kInsRowLo = 1, kInsRowHi = 2, kInsColLo = 4, kInsColHi = 8;
 
+// What the feature marches take beside the plain march's arguments (FEAT; a plain march takes none):
+template <typename T>
+struct MarchExtra {
+  int ins = 0;                    // kFeatIns: the insulated / Robin walls of the grid (kInsRowLo ..)
+  const T* qsrc = nullptr;        // kFeatSrc: the source buffer; kFeatVar: the map; kFeatDiv: RX
+  const T* qsrc2 = nullptr;       // kFeatDiv: RY
+  const T* gain = nullptr;        // kFeatGain: the gain of the pass's level 1
+  const RobCoef<T>* rob = nullptr;  // kFeatRob: the walls' pairs
+};
 template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, bool PS = false, int CLX = 0,
-          bool INS = false, bool SRC = false, bool VAR = false, bool DIV = false, bool GAIN = false, bool ROB = false>
+          int FEAT = 0>
 __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r, int64_t strip, int64_t t0,
-                                      int64_t t1, int lane, StatAcc* acc = nullptr, int ins = 0,
-                                      const T* qsrc = nullptr, const T* qsrc2 = nullptr, const T* gain = nullptr,
-                                      const RobCoef<T>* rob = nullptr) {
+                                      int64_t t1, int lane, StatAcc* acc = nullptr,
+                                      const MarchExtra<T>* x = nullptr) {
+  constexpr bool INS = feat_has(FEAT, kFeatIns), SRC = feat_has(FEAT, kFeatSrc), VAR = feat_has(FEAT, kFeatVar),
+                 DIV = feat_has(FEAT, kFeatDiv), GAIN = feat_has(FEAT, kFeatGain), ROB = feat_has(FEAT, kFeatRob);
   using S = TbShape<T, NV, K>;
   constexpr int V = S::V;
   constexpr int ES = (int)sizeof(T);
@@ -1300,8 +1319,8 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
   constexpr int CL = CLX > 0 ? (CLX < K ? CLX : K) : (ST ? K : chain_len<T, K>());
   // (DIV: the element-wise march in both dtypes)
   constexpr bool kPacked = kPackedF32<T, NV> && !DIV;
-  using W = typename std::conditional<kPacked, MarchF32<K, EK, RING, AR, ST, CL, INS, SRC, VAR, GAIN, ROB>,
-                                      March<T, NV, K, EK, RING, AR, ST, CL, INS, SRC, VAR, DIV, GAIN, ROB>>::type;
+  using W = typename std::conditional<kPacked, MarchF32<K, EK, RING, AR, ST, CL, FEAT>,
+                                      March<T, NV, K, EK, RING, AR, ST, CL, FEAT>>::type;
   W w;
   // row base = column col_lo (= -cpad) of row 0; offsets are relative to it
   w.srow = reinterpret_cast<const char*>(src + a.col_lo);
@@ -1343,27 +1362,27 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
   if constexpr (INS) {
     // rows no march reaches stand for "no insulated wall" (row indices are < 2^31 - kMaxTB)
     constexpr int32_t kNoRow = (int32_t)0x80000000u;
-    w.wall_lo = (ins & kInsRowLo) ? w.fixed_lo : kNoRow;
-    w.wall_hi = (ins & kInsRowHi) ? w.fixed_hi - 1 : kNoRow;
-    w.wall_w = (ins & kInsColLo) && mycol == 0;
+    w.wall_lo = (x->ins & kInsRowLo) ? w.fixed_lo : kNoRow;
+    w.wall_hi = (x->ins & kInsRowHi) ? w.fixed_hi - 1 : kNoRow;
+    w.wall_w = (x->ins & kInsColLo) && mycol == 0;
     uint32_t me = 0;
 #pragma unroll
-    for (int e = 0; e < V; ++e) me |= ((ins & kInsColHi) && mycol + e == a.ncols - 1) ? (1u << e) : 0u;
+    for (int e = 0; e < V; ++e) me |= ((x->ins & kInsColHi) && mycol + e == a.ncols - 1) ? (1u << e) : 0u;
     w.wall_e = me;
   }
-  if constexpr (ROB) w.g = *rob;  // the walls' pairs, wave-uniform (the kernel's argument)
+  if constexpr (ROB) w.g = *x->rob;  // the walls' pairs, wave-uniform (the kernel's argument)
   if constexpr (SRC || VAR) {  // the source buffer / the map (qsrc) has the field's layout
-    w.qrow = reinterpret_cast<const char*>(qsrc + a.col_lo);
+    w.qrow = reinterpret_cast<const char*>(x->qsrc + a.col_lo);
     w.qdelta = w.qrow - w.srow;
     w.q_reset(lane);
   }
   if constexpr (GAIN) {  // the pass's K gains (gain: the entry of level 1), wave-uniform
 #pragma unroll
-    for (int s = 0; s < K; ++s) w.gs[s] = gain[s];
+    for (int s = 0; s < K; ++s) w.gs[s] = x->gain[s];
   }
   if constexpr (DIV) {  // RX (qsrc) and RY (qsrc2) have the field's layout
-    w.dxdelta = reinterpret_cast<const char*>(qsrc + a.col_lo) - w.srow;
-    w.dydelta = reinterpret_cast<const char*>(qsrc2 + a.col_lo) - w.srow;
+    w.dxdelta = reinterpret_cast<const char*>(x->qsrc + a.col_lo) - w.srow;
+    w.dydelta = reinterpret_cast<const char*>(x->qsrc2 + a.col_lo) - w.srow;
     w.d_reset(lane);
   }
   if constexpr (ST) {
@@ -1583,6 +1602,66 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VAR == kVar
   }
 }
 
+// The item loop of the feature kernels below (tb_kernel's general loop without
+// its wave times and statistics), shared as text: H2D_TB_WAVE(WPB) names the
+// wave's `lane` and id `wid` in a launch of WPB waves per workgroup (4: the
+// 256-thread kernels, 1: the one-wave ones) and ends a wave past the launch's;
+// H2D_TB_ITEMS(statement) runs the statement for every piece of the wave's
+// items, with (strip, t0, t1) and the piece's edge kind `ek` in scope;
+// H2D_BY_KIND(statement) runs it with the kind as the constant EK. All three
+// take `a` (the kernel's TbArgs) and T, NV, K from the enclosing kernel's
+// scope. H2D_TB_WAVE returns from the kernel, and H2D_TB_ITEMS ends with the
+// wave's queue_exit: it is the kernel's last statement. The statement argument
+// is pasted as written: no comma or semicolon of its own outside parentheses
+// other than between the two arms of an `if constexpr`. (Macros, not a function
+// taking the march as a callable: through a callable, a lambda or a stateless
+// functor alike, the optimised loop comes out with its address arithmetic in
+// another order, and 10 tb_kernel_ins / _rob / _div instances, nine of them
+// deep fp64 ones at their register limit, allocate up to 8 registers more or fewer.
+// The instances and their counts: profiles/r15/terms/README.md.)
+template <int WPB>
+__device__ __forceinline__ int64_t tb_wave() {
+  if constexpr (WPB == 1) return (int64_t)blockIdx.x;
+  else return (int64_t)blockIdx.x * WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+}
+template <int WPB>
+__device__ __forceinline__ int tb_lane() {
+  if constexpr (WPB == 1) return threadIdx.x;
+  else return threadIdx.x & 63;
+}
+#define H2D_TB_WAVE(WPB)                \
+  const int lane = tb_lane<WPB>();      \
+  const int64_t wid = tb_wave<WPB>();   \
+  if (wid >= a.nwaves) return; /* whole wave exits; no barriers in these kernels */
+#define H2D_TB_ITEMS(...)                                                              \
+  {                                                                                    \
+    using S = TbShape<T, NV, K>;                                                       \
+    int64_t it = wid;                                                                  \
+    int32_t lin = tb_span<kMaxRects>(a, it).lin;                                       \
+    while (it < a.nitems) {                                                            \
+      int64_t strip, t0, t1;                                                           \
+      if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {                           \
+        it = next_item(a, it);                                                         \
+        if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;                        \
+        continue;                                                                      \
+      }                                                                                \
+      lin += (int32_t)(t1 - t0);                                                       \
+      const int64_t c0 = strip * S::U - S::KA;                                         \
+      const int ek = (((t0 - K < a.fixed_lo) || (t1 + K > a.fixed_hi)) ? 1 : 0) |      \
+                     (((c0 < 0) || (c0 + S::W > a.ncols)) ? 2 : 0);                    \
+      (void)ek;                                                                        \
+      __VA_ARGS__;                                                                     \
+    }                                                                                  \
+    queue_exit(a);                                                                     \
+  }
+#define H2D_BY_KIND(...)                                \
+  switch (ek) {                                         \
+    case 0: { constexpr int EK = 0; __VA_ARGS__; } break; \
+    case 1: { constexpr int EK = 1; __VA_ARGS__; } break; \
+    case 2: { constexpr int EK = 2; __VA_ARGS__; } break; \
+    default: { constexpr int EK = 3; __VA_ARGS__; } break; \
+  }
+
 // The general kernel with insulated edges (`ins`: kInsRowLo | kInsRowHi |
 // kInsColLo | kInsColHi, an argument of this kernel only — TbArgs and every
 // tb_kernel instance stay as they are): the same items, kinds and march; an
@@ -1591,31 +1670,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VAR == kVar
 template <typename T, int NV, int K, int RING, int AR>
 __global__ __launch_bounds__(256) void tb_kernel_ins(const T* __restrict__ src, T* __restrict__ dst, TbArgs a, T r,
                                                      int ins) {
-  using S = TbShape<T, NV, K>;
-  const int lane = threadIdx.x & 63;
-  const int64_t wid = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (wid >= a.nwaves) return;  // whole wave exits; no barriers in this kernel
-  int64_t it = wid;
-  int32_t lin = tb_span<kMaxRects>(a, it).lin;
-  while (it < a.nitems) {
-    int64_t strip, t0, t1;
-    if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {
-      it = next_item(a, it);
-      if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;
-      continue;
-    }
-    lin += (int32_t)(t1 - t0);
-    const int64_t c0 = strip * S::U - S::KA;
-    const int ek = (((t0 - K < a.fixed_lo) || (t1 + K > a.fixed_hi)) ? 1 : 0) |
-                   (((c0 < 0) || (c0 + S::W > a.ncols)) ? 2 : 0);
-    switch (ek) {
-      case 0: march<T, NV, K, 0, RING, AR>(src, dst, a, r, strip, t0, t1, lane); break;
-      case 1: march<T, NV, K, 1, RING, AR, false, false, 0, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, ins); break;
-      case 2: march<T, NV, K, 2, RING, AR, false, false, 0, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, ins); break;
-      default: march<T, NV, K, 3, RING, AR, false, false, 0, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, ins); break;
-    }
-  }
-  queue_exit(a);
+  H2D_TB_WAVE(4)
+  MarchExtra<T> x;
+  x.ins = ins;
+  H2D_TB_ITEMS(H2D_BY_KIND(
+      if constexpr (EK == 0) march<T, NV, K, 0, RING, AR>(src, dst, a, r, strip, t0, t1, lane);
+      else march<T, NV, K, EK, RING, AR, false, false, 0, kFeatIns>(src, dst, a, r, strip, t0, t1, lane, nullptr, &x)))
 }
 
 // The general kernel with Robin walls (`g`: the four walls' pairs (a, b), an
@@ -1627,31 +1687,13 @@ __global__ __launch_bounds__(256) void tb_kernel_ins(const T* __restrict__ src, 
 template <typename T, int NV, int K, int RING, int AR>
 __global__ __launch_bounds__(256) void tb_kernel_rob(const T* __restrict__ src, T* __restrict__ dst, TbArgs a, T r,
                                                      int ins, RobCoef<T> g) {
-  using S = TbShape<T, NV, K>;
-  const int lane = threadIdx.x & 63;
-  const int64_t wid = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (wid >= a.nwaves) return;  // whole wave exits; no barriers in this kernel
-  int64_t it = wid;
-  int32_t lin = tb_span<kMaxRects>(a, it).lin;
-  while (it < a.nitems) {
-    int64_t strip, t0, t1;
-    if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {
-      it = next_item(a, it);
-      if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;
-      continue;
-    }
-    lin += (int32_t)(t1 - t0);
-    const int64_t c0 = strip * S::U - S::KA;
-    const int ek = (((t0 - K < a.fixed_lo) || (t1 + K > a.fixed_hi)) ? 1 : 0) |
-                   (((c0 < 0) || (c0 + S::W > a.ncols)) ? 2 : 0);
-    switch (ek) {
-      case 0: march<T, NV, K, 0, RING, AR>(src, dst, a, r, strip, t0, t1, lane); break;
-      case 1: march<T, NV, K, 1, RING, AR, false, false, 0, true, false, false, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, ins, nullptr, nullptr, nullptr, &g); break;
-      case 2: march<T, NV, K, 2, RING, AR, false, false, 0, true, false, false, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, ins, nullptr, nullptr, nullptr, &g); break;
-      default: march<T, NV, K, 3, RING, AR, false, false, 0, true, false, false, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, ins, nullptr, nullptr, nullptr, &g); break;
-    }
-  }
-  queue_exit(a);
+  H2D_TB_WAVE(4)
+  MarchExtra<T> x;
+  x.ins = ins;
+  x.rob = &g;
+  H2D_TB_ITEMS(H2D_BY_KIND(
+      if constexpr (EK == 0) march<T, NV, K, 0, RING, AR>(src, dst, a, r, strip, t0, t1, lane);
+      else march<T, NV, K, EK, RING, AR, false, false, 0, kFeatIns | kFeatRob>(src, dst, a, r, strip, t0, t1, lane, nullptr, &x)))
 }
 
 // The general kernel with a heat source (`q`: the source buffer, in the field's
@@ -1662,31 +1704,11 @@ __global__ __launch_bounds__(256) void tb_kernel_rob(const T* __restrict__ src, 
 template <typename T, int NV, int K, int RING, int AR>
 __global__ __launch_bounds__(64) void tb_kernel_src(const T* __restrict__ src, T* __restrict__ dst, TbArgs a, T r,
                                                     const T* __restrict__ q) {
-  using S = TbShape<T, NV, K>;
-  const int lane = threadIdx.x;
-  const int64_t wid = (int64_t)blockIdx.x;
-  if (wid >= a.nwaves) return;
-  int64_t it = wid;
-  int32_t lin = tb_span<kMaxRects>(a, it).lin;
-  while (it < a.nitems) {
-    int64_t strip, t0, t1;
-    if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {
-      it = next_item(a, it);
-      if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;
-      continue;
-    }
-    lin += (int32_t)(t1 - t0);
-    const int64_t c0 = strip * S::U - S::KA;
-    const int ek = (((t0 - K < a.fixed_lo) || (t1 + K > a.fixed_hi)) ? 1 : 0) |
-                   (((c0 < 0) || (c0 + S::W > a.ncols)) ? 2 : 0);
-    switch (ek) {
-      case 0: march<T, NV, K, 0, RING, AR, false, false, K, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q); break;
-      case 1: march<T, NV, K, 1, RING, AR, false, false, K, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q); break;
-      case 2: march<T, NV, K, 2, RING, AR, false, false, K, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q); break;
-      default: march<T, NV, K, 3, RING, AR, false, false, K, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q); break;
-    }
-  }
-  queue_exit(a);
+  H2D_TB_WAVE(1)
+  MarchExtra<T> x;
+  x.qsrc = q;
+  H2D_TB_ITEMS(H2D_BY_KIND(
+      march<T, NV, K, EK, RING, AR, false, false, K, kFeatSrc>(src, dst, a, r, strip, t0, t1, lane, nullptr, &x)))
 }
 
 // The heat-source kernel with a gain schedule: level s of the pass adds
@@ -1700,32 +1722,12 @@ template <typename T, int NV, int K, int RING, int AR>
 __global__ __launch_bounds__(64) void tb_kernel_gain(const T* __restrict__ src, T* __restrict__ dst, TbArgs a, T r,
                                                      const T* __restrict__ q, const T* __restrict__ g,
                                                      const int64_t* __restrict__ pos) {
-  using S = TbShape<T, NV, K>;
-  const int lane = threadIdx.x;
-  const int64_t wid = (int64_t)blockIdx.x;
-  if (wid >= a.nwaves) return;
-  const T* gp = g + *pos;
-  int64_t it = wid;
-  int32_t lin = tb_span<kMaxRects>(a, it).lin;
-  while (it < a.nitems) {
-    int64_t strip, t0, t1;
-    if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {
-      it = next_item(a, it);
-      if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;
-      continue;
-    }
-    lin += (int32_t)(t1 - t0);
-    const int64_t c0 = strip * S::U - S::KA;
-    const int ek = (((t0 - K < a.fixed_lo) || (t1 + K > a.fixed_hi)) ? 1 : 0) |
-                   (((c0 < 0) || (c0 + S::W > a.ncols)) ? 2 : 0);
-    switch (ek) {
-      case 0: march<T, NV, K, 0, RING, AR, false, false, K, false, true, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q, nullptr, gp); break;
-      case 1: march<T, NV, K, 1, RING, AR, false, false, K, false, true, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q, nullptr, gp); break;
-      case 2: march<T, NV, K, 2, RING, AR, false, false, K, false, true, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q, nullptr, gp); break;
-      default: march<T, NV, K, 3, RING, AR, false, false, K, false, true, false, false, true>(src, dst, a, r, strip, t0, t1, lane, nullptr, 0, q, nullptr, gp); break;
-    }
-  }
-  queue_exit(a);
+  H2D_TB_WAVE(1)
+  MarchExtra<T> x;
+  x.qsrc = q;
+  x.gain = g + *pos;
+  H2D_TB_ITEMS(H2D_BY_KIND(
+      march<T, NV, K, EK, RING, AR, false, false, K, kFeatSrc | kFeatGain>(src, dst, a, r, strip, t0, t1, lane, nullptr, &x)))
 }
 
 // The general kernel with a diffusivity map (`rmap`: the per-point diffusion
@@ -1739,22 +1741,10 @@ __global__ __launch_bounds__(64) void tb_kernel_gain(const T* __restrict__ src, 
 template <typename T, int NV, int K, int RING, int AR>
 __global__ __launch_bounds__(64) void tb_kernel_var(const T* __restrict__ src, T* __restrict__ dst, TbArgs a,
                                                     const T* __restrict__ rmap) {
-  const int lane = threadIdx.x;
-  const int64_t wid = (int64_t)blockIdx.x;
-  if (wid >= a.nwaves) return;
-  int64_t it = wid;
-  int32_t lin = tb_span<kMaxRects>(a, it).lin;
-  while (it < a.nitems) {
-    int64_t strip, t0, t1;
-    if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {
-      it = next_item(a, it);
-      if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;
-      continue;
-    }
-    lin += (int32_t)(t1 - t0);
-    march<T, NV, K, 0, RING, AR, false, false, K, false, false, true>(src, dst, a, T(0), strip, t0, t1, lane, nullptr, 0, rmap);
-  }
-  queue_exit(a);
+  H2D_TB_WAVE(1)
+  MarchExtra<T> x;
+  x.qsrc = rmap;
+  H2D_TB_ITEMS(march<T, NV, K, 0, RING, AR, false, false, K, kFeatVar>(src, dst, a, T(0), strip, t0, t1, lane, nullptr, &x))
 }
 
 // The general kernel of the conservative form (`rx`, `ry`: the per-face
@@ -1767,55 +1757,36 @@ __global__ __launch_bounds__(64) void tb_kernel_var(const T* __restrict__ src, T
 template <typename T, int NV, int K, int RING, int AR>
 __global__ __launch_bounds__(64) void tb_kernel_div(const T* __restrict__ src, T* __restrict__ dst, TbArgs a,
                                                     const T* __restrict__ rx, const T* __restrict__ ry) {
-  using S = TbShape<T, NV, K>;
-  const int lane = threadIdx.x;
-  const int64_t wid = (int64_t)blockIdx.x;
-  if (wid >= a.nwaves) return;
-  int64_t it = wid;
-  int32_t lin = tb_span<kMaxRects>(a, it).lin;
-  while (it < a.nitems) {
-    int64_t strip, t0, t1;
-    if (!tb_piece<kMaxRects>(a, it, lin, strip, t0, t1)) {
-      it = next_item(a, it);
-      if (it < a.nitems) lin = tb_span<kMaxRects>(a, it).lin;
-      continue;
-    }
-    lin += (int32_t)(t1 - t0);
-    const int64_t c0 = strip * S::U - S::KA;
-    const int ek = (((t0 - K < a.fixed_lo) || (t1 + K > a.fixed_hi)) ? 1 : 0) |
-                   (((c0 < 0) || (c0 + S::W > a.ncols)) ? 2 : 0);
-    switch (ek) {
-      case 0: march<T, NV, K, 0, RING, AR, false, false, K, false, false, false, true>(src, dst, a, T(1), strip, t0, t1, lane, nullptr, 0, rx, ry); break;
-      case 1: march<T, NV, K, 1, RING, AR, false, false, K, false, false, false, true>(src, dst, a, T(1), strip, t0, t1, lane, nullptr, 0, rx, ry); break;
-      case 2: march<T, NV, K, 2, RING, AR, false, false, K, false, false, false, true>(src, dst, a, T(1), strip, t0, t1, lane, nullptr, 0, rx, ry); break;
-      default: march<T, NV, K, 3, RING, AR, false, false, K, false, false, false, true>(src, dst, a, T(1), strip, t0, t1, lane, nullptr, 0, rx, ry); break;
-    }
-  }
-  queue_exit(a);
+  H2D_TB_WAVE(1)
+  MarchExtra<T> x;
+  x.qsrc = rx;
+  x.qsrc2 = ry;
+  H2D_TB_ITEMS(H2D_BY_KIND(
+      march<T, NV, K, EK, RING, AR, false, false, K, kFeatDiv>(src, dst, a, T(1), strip, t0, t1, lane, nullptr, &x)))
 }
 
-template <typename T, int NV, int K, int RING, bool MAIN, int AR, int VAR = kVarPlain>
-constexpr auto kernel_ptr() {
-  return &tb_kernel<T, NV, K, RING, MAIN, AR, VAR>;
-}
-
-// Resident 256-thread workgroups per CU for one kernel instance (occupancy API).
-template <typename T, int NV, int K, int RING, bool MAIN, int AR, int VAR = kVarPlain>
-int blocks_per_cu() {
+// Resident workgroups of THREADS threads per CU for one kernel instance
+// (occupancy API; cached per device). FALLBACK: the answer when the query fails.
+template <auto KERNEL, int THREADS, int FALLBACK>
+int resident_per_cu() {
   static std::mutex mu;
-  static std::map<int, int> cache;  // device -> blocks/CU
+  static std::map<int, int> cache;  // device -> workgroups/CU
   int dev = 0;
   (void)hipGetDevice(&dev);
   std::lock_guard<std::mutex> g(mu);
   auto it = cache.find(dev);
   if (it != cache.end()) return it->second;
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kernel_ptr<T, NV, K, RING, MAIN, AR, VAR>()),
-                                                   256, 0) != hipSuccess ||
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(KERNEL), THREADS, 0) != hipSuccess ||
       nb <= 0)
-    nb = 1;
+    nb = FALLBACK;
   cache[dev] = nb;
   return nb;
+}
+// Resident 256-thread workgroups per CU of one tb_kernel instance.
+template <typename T, int NV, int K, int RING, bool MAIN, int AR, int VAR = kVarPlain>
+int blocks_per_cu() {
+  return resident_per_cu<&tb_kernel<T, NV, K, RING, MAIN, AR, VAR>, 256, 1>();
 }
 
 // Per-(T, RING, MAIN, AR) entry points (16 B per lane), explicitly instantiated in
@@ -1829,38 +1800,53 @@ template <typename T, int AR>
 void dispatch_stats(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, hipStream_t s);
 template <typename T, int AR>
 int occupancy_blocks_stats(int k);
-// insulated-edge kernels: general kernel, ring 4 (tb_<dtype>_ins[_fma|_jac].hip)
-template <typename T, int AR>
-void dispatch_ins(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, int ins, hipStream_t s);
-template <typename T, int AR>
-int occupancy_blocks_ins(int k);
-// Robin-wall kernels: general kernel, ring 4, exact / fma (tb_<dtype>_rob[_fma].hip)
-template <typename T, int AR>
-void dispatch_rob(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, int ins, const RobCoef<T>& g,
-                  hipStream_t s);
-template <typename T, int AR>
-int occupancy_blocks_rob(int k);
-// heat-source kernels: general kernel, ring 4, depths 1..kMaxTBSrc (tb_<dtype>_src[_fma].hip)
-template <typename T, int AR>
-void dispatch_src(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, T r, const T* q, hipStream_t s);
-template <typename T, int AR>
-int occupancy_waves_src(int k);
-// heat-source kernels with a gain schedule: the same family (tb_<dtype>_gain.hip, both forms per unit)
-template <typename T, int AR>
-void dispatch_gain(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, T r, const T* q, const T* g,
-                   const int64_t* pos, hipStream_t s);
-template <typename T, int AR>
-int occupancy_waves_gain(int k);
-// diffusivity-map kernels: ring 4, depths 1..kMaxTBVar (tb_<dtype>_var[_fma].hip)
-template <typename T, int AR>
-void dispatch_var(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, const T* rmap, hipStream_t s);
-template <typename T, int AR>
-int occupancy_waves_var(int k);
-// conservative-form kernels: ring 4, depths 1..kMaxTBDiv (tb_<dtype>_div[_fma].hip)
-template <typename T, int AR>
-void dispatch_div(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, const T* rx, const T* ry, hipStream_t s);
-template <typename T, int AR>
-int occupancy_waves_div(int k);
+// The six feature families (general kernel, ring 4): one dispatch / occupancy
+// pair, specialised per (family, T, AR) in the family's instantiation units.
+//   FamIns  tb_<dtype>_ins[_fma|_jac].hip  insulated edges, depths 1..kMaxTB
+//   FamRob  tb_<dtype>_rob[_fma].hip       Robin walls, depths 1..kMaxTBRob
+//   FamSrc  tb_<dtype>_src[_fma].hip       heat source, depths 1..kMaxTBSrc
+//   FamGain tb_<dtype>_gain.hip            source with a gain schedule (both forms per unit)
+//   FamVar  tb_<dtype>_var[_fma].hip       diffusivity map, depths 1..kMaxTBVar
+//   FamDiv  tb_<dtype>_div[_fma].hip       conservative form, depths 1..kMaxTBDiv
+// What a feature launch hands its kernel after (src, dst, a): each family takes its own part.
+template <typename T>
+struct FeatArgs {
+  T r = T(0);
+  int ins = 0;                                // FamIns, FamRob: the walls (kInsRowLo ..)
+  RobCoef<T> rob{};                           // FamRob: the walls' pairs
+  const T *q = nullptr, *q2 = nullptr;        // FamSrc, FamGain: the source; FamVar: the map; FamDiv: RX, RY
+  const T* g = nullptr;                       // FamGain: the gain array
+  const int64_t* pos = nullptr;               //          and its position word
+};
+// A family: NAME, its kernel, threads per workgroup (256: four waves, the fallback
+// occupancy 1 workgroup per CU; 64: one wave, fallback 4), the kernel's name in
+// messages, and the kernel's arguments after (src, dst, a) from a FeatArgs x.
+#define H2D_FAMILY(NAME, KERNEL, THREADS, WHAT, ...)                                                           \
+  struct NAME {                                                                                                \
+    static constexpr int kThreads = THREADS, kWaves = THREADS / 64, kFallback = THREADS == 256 ? 1 : 4;        \
+    static constexpr const char* kNoDepth = "temporal depth not instantiated for the " WHAT " kernel";         \
+    template <typename T, int K, int AR>                                                                       \
+    static int resident() {                                                                                    \
+      return resident_per_cu<&KERNEL<T, 1, K, 4, AR>, THREADS, kFallback>();                                   \
+    }                                                                                                          \
+    template <typename T, int K, int AR>                                                                       \
+    static void launch(unsigned nwaves, const T* src, T* dst, const TbArgs& a, const FeatArgs<T>& x,           \
+                       hipStream_t s) {                                                                        \
+      hipLaunchKernelGGL((KERNEL<T, 1, K, 4, AR>), dim3((nwaves + kWaves - 1) / kWaves), dim3(THREADS), 0, s,  \
+                         src, dst, a, __VA_ARGS__);                                                            \
+    }                                                                                                          \
+  };
+H2D_FAMILY(FamIns, tb_kernel_ins, 256, "insulated-edge", x.r, x.ins)
+H2D_FAMILY(FamRob, tb_kernel_rob, 256, "Robin-wall", x.r, x.ins, x.rob)
+H2D_FAMILY(FamSrc, tb_kernel_src, 64, "heat-source", x.r, x.q)
+H2D_FAMILY(FamGain, tb_kernel_gain, 64, "gain-schedule", x.r, x.q, x.g, x.pos)
+H2D_FAMILY(FamVar, tb_kernel_var, 64, "diffusivity-map", x.q)
+H2D_FAMILY(FamDiv, tb_kernel_div, 64, "conservative-form", x.q, x.q2)
+// nwaves: the waves of the launch (FAM::kWaves per workgroup); occupancy: resident workgroups per CU
+template <class FAM, typename T, int AR>
+void dispatch_feat(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, const FeatArgs<T>& x, hipStream_t s);
+template <class FAM, typename T, int AR>
+int occupancy_feat(int k);
 #define H2D_TB_CASE(T, RING, MAIN, AR, KK)                                                                    \
   case KK:                                                                                                    \
     hipLaunchKernelGGL((tb_kernel<T, 1, KK, RING, MAIN, AR>), dim3(nblocks), dim3(256), 0, s, src, dst, a, r); \
@@ -1941,283 +1927,36 @@ int occupancy_waves_div(int k);
     return 1;                                                                                                 \
   }
 
-template <typename T, int K, int AR>
-int blocks_per_cu_ins() {
-  static std::mutex mu;
-  static std::map<int, int> cache;  // device -> blocks/CU
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> g(mu);
-  auto it = cache.find(dev);
-  if (it != cache.end()) return it->second;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tb_kernel_ins<T, 1, K, 4, AR>),
-                                                   256, 0) != hipSuccess ||
-      nb <= 0)
-    nb = 1;
-  cache[dev] = nb;
-  return nb;
-}
-#define H2D_INS_CASE(T, RING, MAIN, AR, KK)                                                                      \
-  case KK:                                                                                                       \
-    hipLaunchKernelGGL((tb_kernel_ins<T, 1, KK, 4, AR>), dim3(nblocks), dim3(256), 0, s, src, dst, a, r, ins); \
+// One instantiation unit of a feature family: dispatch / occupancy of (FAM, T, AR)
+// for K = 1..16 and the DEEP cases (H2D_TB_CASES_DEEP / _F32DEEP: 17..24, or H2D_NO_CASES).
+#define H2D_FEAT_CASE(T, FAM, MAIN, AR, KK)                           \
+  case KK:                                                            \
+    FAM::template launch<T, KK, AR>(nwaves, src, dst, a, x, s);       \
     return;
-#define H2D_INS_OCC_CASE(T, RING, MAIN, AR, KK) \
+#define H2D_FEAT_OCC_CASE(T, FAM, MAIN, AR, KK) \
   case KK:                                      \
-    return blocks_per_cu_ins<T, KK, AR>();
-#define H2D_INS_UNIT(T, AR, DEEP)                                                                             \
+    return FAM::template resident<T, KK, AR>();
+#define H2D_FEAT_UNIT(FAM, T, AR, DEEP)                                                                       \
   template <>                                                                                                 \
-  void dispatch_ins<T, AR>(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, int ins,      \
-                           hipStream_t s) {                                                                   \
+  void dispatch_feat<FAM, T, AR>(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a,               \
+                                 const FeatArgs<T>& x, hipStream_t s) {                                       \
     switch (k) {                                                                                              \
-      H2D_TB_CASES(H2D_INS_CASE, T, 4, false, AR)                                                             \
-      DEEP(H2D_INS_CASE, T, 4, false, AR)                                                                     \
+      H2D_TB_CASES(H2D_FEAT_CASE, T, FAM, false, AR)                                                          \
+      DEEP(H2D_FEAT_CASE, T, FAM, false, AR)                                                                  \
       default:                                                                                                \
         break;                                                                                                \
     }                                                                                                         \
-    HEAT2D_REQUIRE(false, "temporal depth not instantiated for the insulated-edge kernel");                   \
+    HEAT2D_REQUIRE(false, FAM::kNoDepth);                                                                     \
   }                                                                                                           \
   template <>                                                                                                 \
-  int occupancy_blocks_ins<T, AR>(int k) {                                                                    \
+  int occupancy_feat<FAM, T, AR>(int k) {                                                                     \
     switch (k) {                                                                                              \
-      H2D_TB_CASES(H2D_INS_OCC_CASE, T, 4, false, AR)                                                         \
-      DEEP(H2D_INS_OCC_CASE, T, 4, false, AR)                                                                 \
+      H2D_TB_CASES(H2D_FEAT_OCC_CASE, T, FAM, false, AR)                                                      \
+      DEEP(H2D_FEAT_OCC_CASE, T, FAM, false, AR)                                                              \
       default:                                                                                                \
         break;                                                                                                \
     }                                                                                                         \
-    return 1;                                                                                                 \
-  }
-
-template <typename T, int K, int AR>
-int blocks_per_cu_rob() {
-  static std::mutex mu;
-  static std::map<int, int> cache;  // device -> blocks/CU
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> g(mu);
-  auto it = cache.find(dev);
-  if (it != cache.end()) return it->second;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tb_kernel_rob<T, 1, K, 4, AR>),
-                                                   256, 0) != hipSuccess ||
-      nb <= 0)
-    nb = 1;
-  cache[dev] = nb;
-  return nb;
-}
-#define H2D_ROB_CASE(T, RING, MAIN, AR, KK)                                                                         \
-  case KK:                                                                                                          \
-    hipLaunchKernelGGL((tb_kernel_rob<T, 1, KK, 4, AR>), dim3(nblocks), dim3(256), 0, s, src, dst, a, r, ins, g); \
-    return;
-#define H2D_ROB_OCC_CASE(T, RING, MAIN, AR, KK) \
-  case KK:                                      \
-    return blocks_per_cu_rob<T, KK, AR>();
-#define H2D_ROB_UNIT(T, AR, DEEP)                                                                             \
-  template <>                                                                                                 \
-  void dispatch_rob<T, AR>(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, int ins,      \
-                           const RobCoef<T>& g, hipStream_t s) {                                              \
-    switch (k) {                                                                                              \
-      H2D_TB_CASES(H2D_ROB_CASE, T, 4, false, AR)                                                             \
-      DEEP(H2D_ROB_CASE, T, 4, false, AR)                                                                     \
-      default:                                                                                                \
-        break;                                                                                                \
-    }                                                                                                         \
-    HEAT2D_REQUIRE(false, "temporal depth not instantiated for the Robin-wall kernel");                       \
-  }                                                                                                           \
-  template <>                                                                                                 \
-  int occupancy_blocks_rob<T, AR>(int k) {                                                                    \
-    switch (k) {                                                                                              \
-      H2D_TB_CASES(H2D_ROB_OCC_CASE, T, 4, false, AR)                                                         \
-      DEEP(H2D_ROB_OCC_CASE, T, 4, false, AR)                                                                 \
-      default:                                                                                                \
-        break;                                                                                                \
-    }                                                                                                         \
-    return 1;                                                                                                 \
-  }
-
-// resident waves (one-wave workgroups) per CU of one tb_kernel_src instance
-template <typename T, int K, int AR>
-int waves_per_cu_src() {
-  static std::mutex mu;
-  static std::map<int, int> cache;  // device -> waves/CU
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> g(mu);
-  auto it = cache.find(dev);
-  if (it != cache.end()) return it->second;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tb_kernel_src<T, 1, K, 4, AR>), 64,
-                                                   0) != hipSuccess ||
-      nb <= 0)
-    nb = 4;
-  cache[dev] = nb;
-  return nb;
-}
-#define H2D_SRC_CASE(T, RING, MAIN, AR, KK)                                                                   \
-  case KK:                                                                                                    \
-    hipLaunchKernelGGL((tb_kernel_src<T, 1, KK, 4, AR>), dim3(nwaves), dim3(64), 0, s, src, dst, a, r, q);    \
-    return;
-#define H2D_SRC_OCC_CASE(T, RING, MAIN, AR, KK) \
-  case KK:                                      \
-    return waves_per_cu_src<T, KK, AR>();
-#define H2D_SRC_UNIT(T, AR)                                                                                   \
-  template <>                                                                                                 \
-  void dispatch_src<T, AR>(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, T r, const T* q,    \
-                           hipStream_t s) {                                                                   \
-    switch (k) {                                                                                              \
-      H2D_TB_CASES(H2D_SRC_CASE, T, 4, false, AR)                                                             \
-      default:                                                                                                \
-        break;                                                                                                \
-    }                                                                                                         \
-    HEAT2D_REQUIRE(false, "temporal depth not instantiated for the heat-source kernel");                      \
-  }                                                                                                           \
-  template <>                                                                                                 \
-  int occupancy_waves_src<T, AR>(int k) {                                                                     \
-    switch (k) {                                                                                              \
-      H2D_TB_CASES(H2D_SRC_OCC_CASE, T, 4, false, AR)                                                         \
-      default:                                                                                                \
-        break;                                                                                                \
-    }                                                                                                         \
-    return 4;                                                                                                 \
-  }
-
-// resident waves (one-wave workgroups) per CU of one tb_kernel_gain instance
-template <typename T, int K, int AR>
-int waves_per_cu_gain() {
-  static std::mutex mu;
-  static std::map<int, int> cache;  // device -> waves/CU
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> g(mu);
-  auto it = cache.find(dev);
-  if (it != cache.end()) return it->second;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tb_kernel_gain<T, 1, K, 4, AR>), 64,
-                                                   0) != hipSuccess ||
-      nb <= 0)
-    nb = 4;
-  cache[dev] = nb;
-  return nb;
-}
-#define H2D_GAIN_OCC_CASE(T, RING, MAIN, AR, KK) \
-  case KK:                                       \
-    return waves_per_cu_gain<T, KK, AR>();
-#define H2D_GAIN_CASE(T, RING, MAIN, AR, KK)                                                                  \
-  case KK:                                                                                                    \
-    hipLaunchKernelGGL((tb_kernel_gain<T, 1, KK, 4, AR>), dim3(nwaves), dim3(64), 0, s, src, dst, a, r, q, g, \
-                       pos);                                                                                  \
-    return;
-#define H2D_GAIN_UNIT(T, AR)                                                                                  \
-  template <>                                                                                                 \
-  void dispatch_gain<T, AR>(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, T r, const T* q,   \
-                            const T* g, const int64_t* pos, hipStream_t s) {                                  \
-    switch (k) {                                                                                              \
-      H2D_TB_CASES(H2D_GAIN_CASE, T, 4, false, AR)                                                            \
-      default:                                                                                                \
-        break;                                                                                                \
-    }                                                                                                         \
-    HEAT2D_REQUIRE(false, "temporal depth not instantiated for the gain-schedule kernel");                    \
-  }                                                                                                           \
-  template <>                                                                                                 \
-  int occupancy_waves_gain<T, AR>(int k) {                                                                    \
-    switch (k) {                                                                                              \
-      H2D_TB_CASES(H2D_GAIN_OCC_CASE, T, 4, false, AR)                                                        \
-      default:                                                                                                \
-        break;                                                                                                \
-    }                                                                                                         \
-    return 4;                                                                                                 \
-  }
-
-// resident waves (one-wave workgroups) per CU of one tb_kernel_var instance
-template <typename T, int K, int AR>
-int waves_per_cu_var() {
-  static std::mutex mu;
-  static std::map<int, int> cache;  // device -> waves/CU
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> g(mu);
-  auto it = cache.find(dev);
-  if (it != cache.end()) return it->second;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tb_kernel_var<T, 1, K, 4, AR>), 64,
-                                                   0) != hipSuccess ||
-      nb <= 0)
-    nb = 4;
-  cache[dev] = nb;
-  return nb;
-}
-#define H2D_VAR_CASE(T, RING, MAIN, AR, KK)                                                                   \
-  case KK:                                                                                                    \
-    hipLaunchKernelGGL((tb_kernel_var<T, 1, KK, 4, AR>), dim3(nwaves), dim3(64), 0, s, src, dst, a, rmap);    \
-    return;
-#define H2D_VAR_OCC_CASE(T, RING, MAIN, AR, KK) \
-  case KK:                                      \
-    return waves_per_cu_var<T, KK, AR>();
-#define H2D_VAR_UNIT(T, AR)                                                                                   \
-  template <>                                                                                                 \
-  void dispatch_var<T, AR>(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, const T* rmap,      \
-                           hipStream_t s) {                                                                   \
-    switch (k) {                                                                                              \
-      H2D_TB_CASES(H2D_VAR_CASE, T, 4, false, AR)                                                             \
-      default:                                                                                                \
-        break;                                                                                                \
-    }                                                                                                         \
-    HEAT2D_REQUIRE(false, "temporal depth not instantiated for the diffusivity-map kernel");                  \
-  }                                                                                                           \
-  template <>                                                                                                 \
-  int occupancy_waves_var<T, AR>(int k) {                                                                     \
-    switch (k) {                                                                                              \
-      H2D_TB_CASES(H2D_VAR_OCC_CASE, T, 4, false, AR)                                                         \
-      default:                                                                                                \
-        break;                                                                                                \
-    }                                                                                                         \
-    return 4;                                                                                                 \
-  }
-
-// resident waves (one-wave workgroups) per CU of one tb_kernel_div instance
-template <typename T, int K, int AR>
-int waves_per_cu_div() {
-  static std::mutex mu;
-  static std::map<int, int> cache;  // device -> waves/CU
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::lock_guard<std::mutex> g(mu);
-  auto it = cache.find(dev);
-  if (it != cache.end()) return it->second;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&tb_kernel_div<T, 1, K, 4, AR>), 64,
-                                                   0) != hipSuccess ||
-      nb <= 0)
-    nb = 4;
-  cache[dev] = nb;
-  return nb;
-}
-#define H2D_DIV_CASE(T, RING, MAIN, AR, KK)                                                                   \
-  case KK:                                                                                                    \
-    hipLaunchKernelGGL((tb_kernel_div<T, 1, KK, 4, AR>), dim3(nwaves), dim3(64), 0, s, src, dst, a, rx, ry);  \
-    return;
-#define H2D_DIV_OCC_CASE(T, RING, MAIN, AR, KK) \
-  case KK:                                      \
-    return waves_per_cu_div<T, KK, AR>();
-#define H2D_DIV_UNIT(T, AR)                                                                                   \
-  template <>                                                                                                 \
-  void dispatch_div<T, AR>(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, const T* rx,        \
-                           const T* ry, hipStream_t s) {                                                      \
-    switch (k) {                                                                                              \
-      H2D_TB_CASES(H2D_DIV_CASE, T, 4, false, AR)                                                             \
-      default:                                                                                                \
-        break;                                                                                                \
-    }                                                                                                         \
-    HEAT2D_REQUIRE(false, "temporal depth not instantiated for the conservative-form kernel");                \
-  }                                                                                                           \
-  template <>                                                                                                 \
-  int occupancy_waves_div<T, AR>(int k) {                                                                     \
-    switch (k) {                                                                                              \
-      H2D_TB_CASES(H2D_DIV_OCC_CASE, T, 4, false, AR)                                                         \
-      default:                                                                                                \
-        break;                                                                                                \
-    }                                                                                                         \
-    return 4;                                                                                                 \
+    return FAM::kFallback;                                                                                    \
   }
 
 }  // namespace tbimpl

@@ -437,9 +437,9 @@ bool Solver::pipe_ok(int k) const {
 void Solver::launch_tb(const void* src, void* dst, int64_t rb, int64_t re, int k) {
   if (re <= rb) return;
   if (hip_)
-    kern::launch_tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, s_compute_, cfg_.tile_rows, compute_cus_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, s_compute_, cfg_.tile_rows, compute_cus_, terms());
   else
-    cpu::tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    cpu::tb(dtype(), src, dst, L_, rb, re, k, cfg_.r, terms());
 }
 
 void Solver::exchange_on(void* field, int64_t k, hipStream_t s) {
@@ -572,7 +572,7 @@ void Solver::cycle_finish() {
     if (pe) H2D_HIP(hipEventRecord(pe->ev[5], s_comm_));
     if (pend_frame_ >= 0) {  // the edge rank's frame-side band (launch_overlap), after the exchange
       kern::launch_edge_rect(dtype(), buf_[cur_], dst, L_, split_plan_banded(pend_k_, pend_frame_b_), pend_frame_, cfg_.r,
-                             s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+                             s_comm_, terms());
       // the next cycle's compute-stream work waits for it (and so for the
       // exchange ahead of it); ev_bnd_, posted to the transport, is left alone
       H2D_HIP(hipEventRecord(ev_frame_, s_comm_));
@@ -838,8 +838,8 @@ void Solver::trial_cycle(const kern::SplitPlan& c) {
   last_k_ = 0;  // the other buffer no longer holds T_{n-1}: stats(residual) reports NaN
   if (c.valid == 3) {  // edge-first: both parts in order on the compute stream
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
-    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
-    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_compute_, terms());
+    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, terms(), d_queue_);
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
     return;
@@ -847,15 +847,15 @@ void Solver::trial_cycle(const kern::SplitPlan& c) {
   H2D_HIP(hipStreamWaitEvent(s_compute_, ev_bnd_, 0));
   H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));
   if (c.flags & kern::kPlanLead) {  // lead: the band launch issued first
-    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
-    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, terms());
+    kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, terms(), d_queue_);
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
     return;
   }
-  kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+  kern::launch_split(dtype(), src, dst, L_, c, true, cfg_.r, s_compute_, terms(), d_queue_);
   H2D_HIP(hipEventRecord(ev_int_, s_compute_));
-  kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+  kern::launch_split(dtype(), src, dst, L_, c, false, cfg_.r, s_comm_, terms());
   H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
 }
 
@@ -1260,9 +1260,9 @@ void Solver::launch_overlap(int k, int64_t B) {
     H2D_HIP(hipStreamWaitEvent(s_comm_, ev_int_, 0));     // main part c-1
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_comm_));
     launch_cycle_aux(k, s_comm_);
-    kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_edge_rect(dtype(), src, dst, L_, sp, 1 - frame_rect, cfg_.r, s_comm_, terms());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, terms(), d_queue_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_comm_));
@@ -1279,12 +1279,12 @@ void Solver::launch_overlap(int k, int64_t B) {
     H2D_HIP(hipStreamWaitEvent(s_compute_, ev_comm_, 0));
     if (pe) H2D_HIP(hipEventRecord(pe->ev[2], s_compute_));
     launch_cycle_aux(k, s_compute_);
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_compute_, terms());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_compute_));
     H2D_HIP(hipEventRecord(ev_bnd_, s_compute_));
     if (tr_->exchanges()) tr_->post(dst, L_, ev_bnd_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, terms(), d_queue_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
     pend_ = Pending::EdgeFirst;
@@ -1296,23 +1296,23 @@ void Solver::launch_overlap(int k, int64_t B) {
   launch_cycle_aux(k, s_comm_);  // (ahead of the band launch in every order below)
   if (lead) {
     // lead: the band launch first (comm stream), then the interior beside it
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, terms());
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, terms(), d_queue_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
   } else if (sp.valid) {
     if (pe) H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, cfg_.arith, d_queue_, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_split(dtype(), src, dst, L_, sp, true, cfg_.r, s_compute_, terms(), d_queue_);
     if (pe) H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     H2D_HIP(hipEventRecord(ev_int_, s_compute_));
-    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, cfg_.arith, nullptr, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_split(dtype(), src, dst, L_, sp, false, cfg_.r, s_comm_, terms());
   } else {  // slab too thin / narrow to split: all of it beside the exchange
     if (pe) {
       H2D_HIP(hipEventRecord(pe->ev[0], s_compute_));
       H2D_HIP(hipEventRecord(pe->ev[1], s_compute_));
     }
-    kern::launch_tb(dtype(), src, dst, L_, 0, L_.nrows, k, cfg_.r, s_comm_, 0, 0, cfg_.arith, bc_, source(), rmap(), face_rx(), face_ry(), gain(), robin());
+    kern::launch_tb(dtype(), src, dst, L_, 0, L_.nrows, k, cfg_.r, s_comm_, 0, 0, terms());
   }
   if (pe) H2D_HIP(hipEventRecord(pe->ev[3], s_comm_));
   H2D_HIP(hipEventRecord(ev_bnd_, s_comm_));
