@@ -21,7 +21,7 @@ from .utils.config import InputDat, Problem, make_problem, parse_input_text, rea
 def __getattr__(name):
     # lazy: importing the models pulls in the native library / torch
     if name in ("HeatSolver", "LoopbackGroup", "rmap_from_nu", "faces_from_k", "robin_from_h", "robin_from_flux",
-                "robin_wall_temperature"):
+                "robin_wall_temperature", "weights_from"):
         from .models import heat2d as _m
         return getattr(_m, name)
     if name in ("plan_max_grid", "footprint"):  # the memory-fit planner (utils/memplan.py)

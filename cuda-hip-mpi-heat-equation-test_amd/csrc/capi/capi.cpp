@@ -236,6 +236,32 @@ int heat2d_cpu_tb_rob(int dtype, const void* src, void* dst, const heat2d_layout
 
 int heat2d_max_tb_rob(void) { return kMaxTBRob; }
 
+int heat2d_tb_w5(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                 void* stream, int64_t tile_rows, int arith, int bc, const double* weights) {
+  return guarded([&] {
+    HEAT2D_REQUIRE(weights != nullptr, "heat2d_tb_w5 needs the five weights");
+    kern::TbTerms t;
+    t.arith = arith;
+    t.bc = bc;
+    t.weights = weights;
+    kern::launch_tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, as_stream(stream), tile_rows, 0, t);
+  });
+}
+
+int heat2d_cpu_tb_w5(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                     int arith, int bc, const double* weights) {
+  return guarded([&] {
+    HEAT2D_REQUIRE(weights != nullptr, "heat2d_cpu_tb_w5 needs the five weights");
+    kern::TbTerms t;
+    t.arith = arith;
+    t.bc = bc;
+    t.weights = weights;
+    cpu::tb((DType)dtype, src, dst, to_layout(L), rb, re, k, 0.0, t);
+  });
+}
+
+int heat2d_max_tb_w5(void) { return kMaxTBW5; }
+
 int heat2d_tb_src(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                   double r, void* stream, int64_t tile_rows, int arith, const void* source) {
   return guarded([&] {
@@ -682,6 +708,44 @@ int heat2d_probe_cone_rob(int dtype, const void* src, const heat2d_layout* L, in
     kern::probe_bounds(a, to_layout(L), bc, robin);
     if (on_device) kern::launch_probe_cone((DType)dtype, a, arith, as_stream(stream));
     else cpu::probe_cone((DType)dtype, a, arith);
+  });
+}
+
+int heat2d_probe_cone_w5(int dtype, const void* src, const heat2d_layout* L, int k, int arith, int bc,
+                         const double* weights, const int64_t* pts, int64_t P, void* out, void* stream, int on_device) {
+  return guarded([&] {
+    HEAT2D_REQUIRE(weights != nullptr, "heat2d_probe_cone_w5 needs the five weights");
+    for (int i = 0; i < 5; ++i) HEAT2D_REQUIRE(std::isfinite(weights[i]), "weights must be finite");
+    kern::ProbeArgs a{};
+    a.src = src;
+    a.pts = pts;
+    a.hist = out;
+    a.capacity = k;
+    a.P = P;
+    a.k = k;
+    kern::probe_bounds(a, to_layout(L), bc);
+    a.w5 = 1;
+    for (int i = 0; i < 5; ++i) a.wt[i] = weights[i];
+    if (on_device) kern::launch_probe_cone((DType)dtype, a, arith, as_stream(stream));
+    else cpu::probe_cone((DType)dtype, a, arith);
+  });
+}
+
+int heat2d_solver_set_weights(void* s, const double* weights) {
+  return guarded([&] { static_cast<Solver*>(s)->set_weights(weights); });
+}
+
+int heat2d_group_set_weights(void* g, const double* weights) {
+  return guarded([&] { static_cast<LoopbackGroup*>(g)->set_weights(weights); });
+}
+
+int heat2d_solver_weights(void* s, double* out5, int32_t* set, int32_t* max_tb) {
+  return guarded([&] {
+    const Solver* so = static_cast<Solver*>(s);
+    const double* w = so->weights();
+    for (int i = 0; i < 5; ++i) out5[i] = w ? w[i] : 0.0;
+    *set = w ? 1 : 0;
+    *max_tb = kMaxTBW5;
   });
 }
 

@@ -87,6 +87,10 @@ struct Args {
   // or taken from a restart's checkpoint
   bool robin_set[4] = {};
   double robin[8] = {1.0, -0.0, 1.0, -0.0, 1.0, -0.0, 1.0, -0.0};
+  // --weights wS,wE,wN,wW,wC: the constant-coefficient five-point operator in place of r
+  // (Solver::set_weights), or taken from a restart's checkpoint
+  bool weights_set = false;
+  double weights[5] = {};
   // --source FILE.npy: heat source, the frame-inclusive (n+2) x (n+2) per-step increment dt * f
   // (SolverConfig::source; converted to the run's dtype, a wrong shape fails)
   std::string source;
@@ -120,6 +124,7 @@ void usage() {
       "              [--transport auto|rccl|peer] [--share-gpu] [--autotune auto|on|off] [--edge-shift N]\n"
       "              [--bc-x dirichlet|periodic|insulated|robin] [--bc-y dirichlet|periodic|insulated|robin]\n"
       "              [--robin-x-lo A,B] [--robin-x-hi A,B] [--robin-y-lo A,B] [--robin-y-hi A,B]\n"
+      "              [--weights wS,wE,wN,wW,wC]\n"
       "              [--source FILE.npy] [--source-gain FILE] [--rmap FILE.npy] [--faces FILE.npy]\n"
       "              [--probes FILE [--probes-out FILE.npy]]\n");
 }
@@ -202,6 +207,22 @@ Args parse_args(int argc, char** argv) {
       a.robin_set[side] = true;
       a.robin[2 * side] = av;
       a.robin[2 * side + 1] = bv;
+    }
+    else if (s == "--weights" || s.compare(0, 10, "--weights=") == 0) {  // --weights wS,wE,wN,wW,wC (or --weights=...)
+      const std::string v = s == "--weights" ? need("--weights") : s.substr(10);
+      const char* p = v.c_str();
+      bool ok = true;
+      for (int k = 0; k < 5 && ok; ++k) {
+        char* e = nullptr;
+        a.weights[k] = std::strtod(p, &e);
+        ok = e && e != p && *e == (k < 4 ? ',' : '\0');
+        p = e ? e + 1 : p;
+      }
+      if (!ok) {
+        std::fprintf(stderr, "--weights expects wS,wE,wN,wW,wC (five numbers), got %s\n", v.c_str());
+        std::exit(2);
+      }
+      a.weights_set = true;
     }
     else if (s == "--edge-shift") {
       a.edge_shift = std::atoi(need("--edge-shift").c_str());
@@ -377,6 +398,11 @@ void save_checkpoint(Shared& sh, Solver& s, Transport& tr, int rank, int64_t ste
         m.robin[2 * k] = s.config().robin[2 * k];
         m.robin[2 * k + 1] = s.config().robin[2 * k + 1];
       }
+    // the five weights as the solver converted them (exactly: hex floats); the key only with weights
+    if (const double* w = s.weights()) {
+      m.weights_set = true;
+      for (int k = 0; k < 5; ++k) m.weights[k] = w[k];
+    }
     m.source_sha256 = sh.source_sha256;  // (empty: no source, written as null)
     m.source_gain_sha256 = sh.gain_sha256;  // (empty: no schedule, the key is not written)
     m.rmap_sha256 = sh.rmap_sha256;      // (empty: no map, the key is not written)
@@ -551,6 +577,28 @@ void run_rank(Shared& sh, int rank) {
                                      " != " + m0.rmap_sha256 + ")");
       }
     }
+    // the five weights: the flag, or a restart's checkpointed values (a flag that says otherwise fails)
+    bool weights_on = a.weights_set;
+    double weights[5];
+    for (int k = 0; k < 5; ++k) weights[k] = cfg.dtype == 0 ? (double)(float)a.weights[k] : a.weights[k];
+    if (!a.restart.empty()) {
+      const ckpt::Meta mw = ckpt::read_meta(a.restart);
+      if (a.weights_set) {
+        bool same = mw.weights_set;
+        for (int k = 0; k < 5 && same; ++k) same = weights[k] == mw.weights[k];
+        HEAT2D_REQUIRE(same, mw.weights_set ? "--weights conflicts with the checkpoint's weights"
+                                            : "--weights conflicts with the checkpoint: it was written without weights");
+      }
+      weights_on = mw.weights_set;
+      for (int k = 0; k < 5; ++k) weights[k] = mw.weights[k];
+    }
+    if (weights_on) {  // a negative weight draws the warning (what weights do not go with: Solver::set_weights, below)
+      const char* const names[5] = {"wS", "wE", "wN", "wW", "wC"};
+      for (int k = 0; k < 5; ++k)
+        if (weights[k] < 0 && root && !a.quiet)
+          std::fprintf(stderr, "warning: negative weight %s = %.6g: the maximum principle is lost, FTCS may be unstable\n",
+                       names[k], weights[k]);
+    }
     if (!a.restart.empty()) {
       // ... and the face coefficients the checkpointed run had (not saved either), and no others
       const ckpt::Meta mf = ckpt::read_meta(a.restart);
@@ -592,7 +640,9 @@ void run_rank(Shared& sh, int rank) {
       // the whole run — the IC in [m, 2m] (the reference's: 1 and 2) keeps
       // every sum - 4c exact; a restart's data is not known to be
       // (with a source auto stays with the solver: fma or exact, never jacobi)
-      if (sh.prob.r == 0.25 && ic_sterbenz_safe(sh.prob.ic) && a.restart.empty() && cfg.engine == 0 && !cfg.source && !cfg.rmap && !cfg.faces &&
+      if (weights_on) {  // (no reference program defines the term: auto is the cheap form; Solver::set_weights resolves it)
+        arith_used = "fma (auto)";
+      } else if (sh.prob.r == 0.25 && ic_sterbenz_safe(sh.prob.ic) && a.restart.empty() && cfg.engine == 0 && !cfg.source && !cfg.rmap && !cfg.faces &&
           !robin_any) {  // (with Robin walls auto stays with the solver too: fma or exact, never jacobi)
         cfg.arith = 2;
         arith_used = "jacobi (auto)";
@@ -606,6 +656,7 @@ void run_rank(Shared& sh, int rank) {
     }
     if (root) sh.arith_used = arith_used;
     Solver s(cfg, tr);
+    if (weights_on) s.set_weights(weights);  // (refuses, before the first step, whatever weights do not go with)
     if (cfg.source) s.set_source(sh.source.data(), sh.prob.n_owned + 2);
     if (cfg.rmap) s.set_rmap(sh.rmap.data(), sh.prob.n_owned + 2);
     if (cfg.faces) {

@@ -124,6 +124,33 @@ void row_div_fma_sw(const T* up, const T* mid, const T* dn, T* out, int64_t n, c
     out[j] = c + p;
   }
 }
+// ... the five-weight operator, w = (wS, wE, wN, wW, wC): every product and sum rounded, in the
+// march's order S, E, N, W and last C; arith 1: the first product, then four fmas
+template <typename T>
+void row_w5_exact(const T* up, const T* mid, const T* dn, T* out, int64_t n, const T* w) {
+  for (int64_t j = 0; j < n; ++j)
+    out[j] = (((w[0] * dn[j] + w[1] * mid[j + 1]) + w[2] * up[j]) + w[3] * mid[j - 1]) + w[4] * mid[j];
+}
+template <typename T>
+__attribute__((target("fma"))) void row_w5_fma_hw(const T* up, const T* mid, const T* dn, T* out, int64_t n, const T* w) {
+  for (int64_t j = 0; j < n; ++j) {
+    T p = w[0] * dn[j];
+    p = std::fma(w[1], mid[j + 1], p);
+    p = std::fma(w[2], up[j], p);
+    p = std::fma(w[3], mid[j - 1], p);
+    out[j] = std::fma(w[4], mid[j], p);
+  }
+}
+template <typename T>
+void row_w5_fma_sw(const T* up, const T* mid, const T* dn, T* out, int64_t n, const T* w) {
+  for (int64_t j = 0; j < n; ++j) {
+    T p = w[0] * dn[j];
+    p = std::fma(w[1], mid[j + 1], p);
+    p = std::fma(w[2], up[j], p);
+    p = std::fma(w[3], mid[j - 1], p);
+    out[j] = std::fma(w[4], mid[j], p);
+  }
+}
 // arith 2 (r == 1/4): the centre weight 1 - 4r is zero, r * sum (r*x exact)
 template <typename T>
 void row_jacobi(const T* up, const T* mid, const T* dn, T* out, int64_t n, T r) {
@@ -193,6 +220,8 @@ void rob_row_impl(T* dst, const T* src, int64_t n, T a, T b, int arith) {
 // gn (with q: the gains of the pass, gn[s - 1] for level s): level s adds
 // gn[s - 1] * q — the product rounded, then the add; arith 1: one fma — the
 // device march's tb_impl.hpp March GAIN.
+// w5 (the five weights, Dirichlet or periodic axes): an owned point's update is the weighted
+// sum of its five operands (the device march's tb_impl.hpp March W5); pinned points are copied.
 // rm (a diffusivity map in the field's layout, Dirichlet axes only): the
 // multiplier of an owned point's update is its element of rm instead of r (the
 // device march's tb_impl.hpp March VAR); pinned points are copied.
@@ -202,7 +231,7 @@ void rob_row_impl(T* dst, const T* src, int64_t n, T a, T b, int arith) {
 template <typename T>
 void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re, int k, T r, int arith, int bc,
              const T* q = nullptr, const T* rm = nullptr, const T* fx = nullptr, const T* fy = nullptr,
-             const T* gn = nullptr, const double* rob = nullptr) {
+             const T* gn = nullptr, const double* rob = nullptr, const double* w5 = nullptr) {
   const SlabLayout L = kern::bc_layout(L0, bc & kern::kBcPeriodicX);  // (the columns: free_cols below)
   const bool free_cols = (bc & kern::kBcPeriodicY) != 0;
   const bool robin = (bc & kern::kBcRobin) != 0;
@@ -229,6 +258,8 @@ void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re,
   const int64_t c = L.cpad;
   T* a = A.data();
   T* b = B.data();
+  const T wt[5] = {w5 ? (T)w5[0] : T(0), w5 ? (T)w5[1] : T(0), w5 ? (T)w5[2] : T(0), w5 ? (T)w5[3] : T(0),
+                   w5 ? (T)w5[4] : T(0)};
   auto* row_update = arith == 2   ? &row_jacobi<T>
                      : arith == 1 ? (host_has_fma() ? &row_fma_hw<T> : &row_fma_sw<T>)
                                   : &row_exact<T>;
@@ -267,6 +298,11 @@ void tb_impl(const T* src, T* dst, const SlabLayout& L0, int64_t rb, int64_t re,
         T* out = b + li * P + c - g;
         if (row < fixed_lo || row >= fixed_hi) {
           std::memcpy(out, mid, sizeof(T) * (size_t)(L.ncols + 2 * g));
+          continue;
+        }
+        if (w5) {
+          if (arith == 1) (host_has_fma() ? row_w5_fma_hw<T> : row_w5_fma_sw<T>)(up, mid, dn, out, L.ncols + 2 * g, wt);
+          else row_w5_exact<T>(up, mid, dn, out, L.ncols + 2 * g, wt);
           continue;
         }
         if (fx) {
@@ -398,7 +434,7 @@ void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_b
   const int bc = terms.bc;
   const void *source = terms.source, *rmap = terms.rmap, *rx = terms.rx, *ry = terms.ry;
   const kern::GainRef gain = terms.gain;
-  const double* robin = terms.robin;
+  const double *robin = terms.robin, *weights = terms.weights;
   HEAT2D_REQUIRE(k >= 1 && k <= L.halo, "k out of range");
   HEAT2D_REQUIRE(arith >= 0 && arith <= 3, "arith must be 0, 1, 2 or 3");
   HEAT2D_REQUIRE(arith != 2 || r == 0.25, "arith 2 (jacobi) needs r == 1/4 exactly");
@@ -418,17 +454,25 @@ void tb(DType dt, const void* src, void* dst, const SlabLayout& L, int64_t row_b
                  "face coefficients need arith 0 (exact) or 1 (fma), Dirichlet boundaries on both axes, no heat source and "
                  "no diffusivity map");
   HEAT2D_REQUIRE(!gain.g || (source && gain.pos), "a gain schedule needs a heat source and its position word");
+  if (weights) {
+    HEAT2D_REQUIRE(arith == 0 || arith == 1, "weights need arith 0 (exact) or 1 (fma)");
+    HEAT2D_REQUIRE(!source && !rmap && !rx && !gain.g, "weights go with no heat source, diffusivity map, face coefficients or gain schedule");
+    HEAT2D_REQUIRE(!(bc & (kern::kBcWallX | kern::kBcWallY)), "weights need Dirichlet or periodic axes: no insulated or Robin walls");
+    for (int i = 0; i < 5; ++i) HEAT2D_REQUIRE(std::isfinite(weights[i]), "weights must be finite");
+  }
   if (arith == 3) arith = 1;
   if (row_end <= row_begin) return;
   const int64_t gpos = gain.g ? *gain.pos : 0;
   if (dt == DType::F32)
     tb_impl<float>(static_cast<const float*>(src), static_cast<float*>(dst), L, row_begin, row_end, k, (float)r, arith, bc,
                    static_cast<const float*>(source), static_cast<const float*>(rmap), static_cast<const float*>(rx),
-                   static_cast<const float*>(ry), gain.g ? static_cast<const float*>(gain.g) + gpos : nullptr, robin);
+                   static_cast<const float*>(ry), gain.g ? static_cast<const float*>(gain.g) + gpos : nullptr, robin,
+                   weights);
   else
     tb_impl<double>(static_cast<const double*>(src), static_cast<double*>(dst), L, row_begin, row_end, k, r, arith, bc,
                     static_cast<const double*>(source), static_cast<const double*>(rmap), static_cast<const double*>(rx),
-                    static_cast<const double*>(ry), gain.g ? static_cast<const double*>(gain.g) + gpos : nullptr, robin);
+                    static_cast<const double*>(ry), gain.g ? static_cast<const double*>(gain.g) + gpos : nullptr, robin,
+                    weights);
 }
 
 void init(DType dt, void* field, const SlabLayout& L, const kern::IcParams& ic, const double* xc,
@@ -545,6 +589,30 @@ void probe_cone_run(const kern::ProbeArgs& a) {
     }
   }
 }
+// ... of the five-weight operator (kernels/probe_cone.hip probe_cone_w5)
+template <typename T, int AR>
+void probe_cone_w5_run(const kern::ProbeArgs& a) {
+  constexpr int S = kern::kProbeSide;
+  std::vector<T> planes((size_t)2 * S * S);
+  T* plane[2] = {planes.data(), planes.data() + (size_t)S * S};
+  const T* src = static_cast<const T*>(a.src);
+  T* hist = static_cast<T*>(a.hist);
+  const int k = a.k, side = 2 * k + 1;
+  const int64_t base = (a.base ? *a.base : 0) + a.base0;
+  for (int64_t p = 0; p < a.P; ++p) {
+    const int64_t ci = a.pts[2 * p], cj = a.pts[2 * p + 1];
+    for (int idx = 0; idx < side * side; ++idx) {
+      const int u = idx / side, v = idx % side;
+      const int64_t row = ci - k + u, col = cj - k + v;
+      if (kern::probe_loads(a, row, col)) plane[0][u * S + v] = src[a.L.offset(row, col)];
+    }
+    for (int s = 1; s <= k; ++s) {
+      const int w = 2 * (k - s) + 1;
+      for (int idx = 0; idx < w * w; ++idx) kern::probe_point_w5<T, AR>(a, ci, cj, s, idx, plane[(s - 1) & 1], plane[s & 1]);
+      if (base + s - 1 < a.capacity) hist[(base + s - 1) * a.P + p] = plane[s & 1][k * S + k];
+    }
+  }
+}
 template <typename T, int MODE>
 void probe_cone_mode(const kern::ProbeArgs& a, int arith) {
   if (arith == 0) probe_cone_run<T, MODE, 0>(a);
@@ -554,7 +622,13 @@ void probe_cone_mode(const kern::ProbeArgs& a, int arith) {
 }
 template <typename T>
 void probe_cone_typed(const kern::ProbeArgs& a, int arith) {
-  if (a.robin) {
+  if (a.w5) {
+    HEAT2D_REQUIRE(!a.source && !a.rmap && !a.rx && !a.gain && !a.robin && a.wall_r0 == INT64_MIN && a.wall_c0 == INT64_MIN &&
+                       arith <= 1,
+                   "probe_cone: weights take the plain mode, Dirichlet or periodic axes and arith exact or fma");
+    if (arith == 0) probe_cone_w5_run<T, 0>(a);
+    else probe_cone_w5_run<T, 1>(a);
+  } else if (a.robin) {
     HEAT2D_REQUIRE(!a.source && !a.rmap && !a.rx && !a.gain && (arith == 0 || arith == 1),
                    "probe_cone: Robin walls take the plain mode and arith exact or fma");
     if (arith == 0) probe_cone_run<T, kern::kProbePlain, 0, false, true>(a);

@@ -197,6 +197,25 @@ int heat2d_tb_rob(int dtype, const void* src, void* dst, const heat2d_layout* L,
 int heat2d_cpu_tb_rob(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                       double r, int arith, int bc, const double* robin);
 int heat2d_max_tb_rob(void);
+/* heat2d_tb_bc / heat2d_cpu_tb_bc with the constant-coefficient five-point operator in place of the scalar r:
+ * weights = (wS, wE, wN, wW, wC), finite, already in the field's dtype; every fused level is
+ * T' = ((((wS*S + wE*E) + wN*N) + wW*W) + wC*C), S = T[i+1,j], E = T[i,j+1], N = T[i-1,j], W = T[i,j-1]
+ * (arith 1: wS*S, then one fma per further operand). bc: 0 | 1 (periodic x) | 2 (periodic y); arith 0 / 1;
+ * depths 1..heat2d_max_tb_w5() on the device. */
+int heat2d_tb_w5(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                 void* stream, int64_t tile_rows, int arith, int bc, const double* weights);
+int heat2d_cpu_tb_w5(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
+                     int arith, int bc, const double* weights);
+int heat2d_max_tb_w5(void);
+/* heat2d_probe_cone in the plain mode with the five weights (bc and weights as heat2d_tb_w5; arith 0 / 1) */
+int heat2d_probe_cone_w5(int dtype, const void* src, const heat2d_layout* L, int k, int arith, int bc,
+                         const double* weights, const int64_t* pts, int64_t P, void* out, void* stream, int on_device);
+/* Solver::set_weights / LoopbackGroup::set_weights: 5 doubles (converted to the run's dtype), or NULL to return
+ * to the scalar-r kernels. Drops captured graphs. */
+int heat2d_solver_set_weights(void* s, const double* weights);
+int heat2d_group_set_weights(void* g, const double* weights);
+/* out5 = the weights in the run's dtype (zeros without), *set = 1 with weights, *max_tb = kMaxTBW5 */
+int heat2d_solver_weights(void* s, double* out5, int32_t* set, int32_t* max_tb);
 int heat2d_tb_src(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,
                   double r, void* stream, int64_t tile_rows, int arith, const void* source);
 int heat2d_cpu_tb_src(int dtype, const void* src, void* dst, const heat2d_layout* L, int64_t rb, int64_t re, int k,

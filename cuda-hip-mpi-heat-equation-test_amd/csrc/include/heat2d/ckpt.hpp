@@ -25,6 +25,10 @@ struct Meta {
   // k (x_lo, x_hi, y_lo, y_hi) is recorded; robin[2k], robin[2k + 1] its (a, b)
   int robin_sides = 0;
   double robin[8] = {1.0, -0.0, 1.0, -0.0, 1.0, -0.0, 1.0, -0.0};
+  // the five weights (wS, wE, wN, wW, wC) in the run's dtype, recorded exactly (meta.json "weights": a list of
+  // five hex floats, as utils/checkpoint.py writes it; the key only with weights)
+  bool weights_set = false;
+  double weights[5] = {};
   // the run's heat source: SHA-256 (hex) of the global frame-inclusive array's bytes in the run's
   // dtype, as utils/checkpoint.py records it; empty: none (null, or absent in older saves)
   std::string source_sha256;

@@ -66,6 +66,9 @@ constexpr int kMaxTBDiv = 16;
 // Deepest pass with Robin walls (tb_kernel_rob: depths 1..kMaxTBRob, both dtypes,
 // exact and fma, none with scratch — every depth the insulated kernels have).
 constexpr int kMaxTBRob = 24;
+// Deepest pass of the five-weight operator (tb_kernel_w5: depths 1..kMaxTBW5, both
+// dtypes, exact and fma, none with scratch; a solver with weights clamps to it).
+constexpr int kMaxTBW5 = 24;
 // Most probe points of one solver (Solver::set_probes: one probe_cone workgroup
 // per point and cycle).
 constexpr int kMaxProbes = 4096;

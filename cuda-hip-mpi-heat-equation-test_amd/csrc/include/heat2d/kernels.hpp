@@ -193,6 +193,16 @@ struct TbTerms {
   // them. Every launch that would run tb_kernel_ins runs tb_kernel_rob: arith
   // 0 / 1, depths 1..kMaxTBRob, no source / rmap / faces.
   const double* robin = nullptr;
+  // The constant-coefficient five-point operator: 5 values (wS, wE, wN, wW, wC) already
+  // converted to the field's dtype, T' = wS*S + wE*E + wN*N + wW*W + wC*C at every fused
+  // level with S = T[i+1,j], E = T[i,j+1], N = T[i-1,j], W = T[i,j-1], C = T[i,j] — every
+  // product and sum rounded, ((((wS*S + wE*E) + wN*N) + wW*W) + wC*C); arith 1:
+  // p = wS*S, then p = fma(w, operand, p) for E, N, W and C — `r` is then not used. Read
+  // on the host when the launch is made and passed to tb_kernel_w5 by value, so a captured
+  // launch keeps them. Every rect of the launch runs tb_kernel_w5 (tb_impl.hpp): Dirichlet
+  // or periodic axes, arith 0 / 1, depths 1..kMaxTBW5, no source / rmap / faces / gain, no
+  // fused statistics, no wave-pair plans. nullptr: the scalar-r kernels.
+  const double* weights = nullptr;
 };
 
 // dst(rows [row_begin,row_end)) = k FTCS steps of src. `src`/`dst` are

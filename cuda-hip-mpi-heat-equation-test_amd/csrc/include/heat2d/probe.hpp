@@ -58,6 +58,10 @@ struct ProbeArgs {
   // a Robin one holds (1, -0.0)
   int32_t robin;
   double rob[8];
+  // the five-weight operator (w5 != 0; plain mode, arith exact / fma, Dirichlet or periodic
+  // axes): wt = (wS, wE, wN, wW, wC) in the field's dtype, `r` is not used
+  int32_t w5;
+  double wt[5];
 };
 
 // The frame and wall lines of a slab under boundary bits `bc`.
@@ -167,6 +171,33 @@ __host__ __device__ inline void probe_point(const ProbeArgs& a, int64_t ci, int6
     if (GAIN) coef[2] = static_cast<const T*>(a.gain)[(a.gain_pos ? *a.gain_pos : 0) + a.gain_pos0 + s - 1];
   }
   out[at] = probe_update<T, MODE, AR, GAIN>(c, so, ea, no, we, coef);
+}
+
+// The five-weight operator's update of one point (ProbeArgs::wt), the march's W5 rule: operands
+// in the order S, E, N, W and last C, every product and sum rounded; AR 1: the first product,
+// then one fma per further operand.
+template <typename T, int AR>
+__host__ __device__ inline T probe_update_w5(T c, T s, T e, T n, T w, const double* wt) {
+  const T ws = (T)wt[0], we = (T)wt[1], wn = (T)wt[2], ww = (T)wt[3], wc = (T)wt[4];
+  if (AR == 1) return probe_fma(wc, c, probe_fma(ww, w, probe_fma(wn, n, probe_fma(we, e, ws * s))));
+  return (((ws * s + we * e) + wn * n) + ww * w) + wc * c;
+}
+// probe_point for the five-weight operator: frame lines keep their value, the ghost rows /
+// columns of a periodic axis are read as they lie in the plane (as the plain cone).
+template <typename T, int AR>
+__host__ __device__ inline void probe_point_w5(const ProbeArgs& a, int64_t ci, int64_t cj, int s, int idx, const T* in,
+                                               T* out) {
+  const int w = 2 * (a.k - s) + 1;
+  const int u = s + idx / w, v = s + idx % w;  // plane coordinates
+  const int64_t row = ci - a.k + u, col = cj - a.k + v;
+  if (row < a.frame_r0 || row > a.frame_r1 || col < a.frame_c0 || col > a.frame_c1) return;  // off the grid
+  const int at = u * kProbeSide + v;
+  const T c = in[at];
+  if (row == a.frame_r0 || row == a.frame_r1 || col == a.frame_c0 || col == a.frame_c1) {
+    out[at] = c;  // a Dirichlet frame line
+    return;
+  }
+  out[at] = probe_update_w5<T, AR>(c, in[at + kProbeSide], in[at + 1], in[at - kProbeSide], in[at - 1], a.wt);
 }
 
 // Whether patch point (row, col) is loaded: on the grid and inside the allocation.

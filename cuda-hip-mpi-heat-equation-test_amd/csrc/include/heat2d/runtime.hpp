@@ -497,6 +497,19 @@ class Solver {
   // Between step() calls; drops the captured graphs.
   void set_faces(const void* rx, const void* ry, int64_t ld);
   bool has_faces() const { return faces_on_; }
+  // The constant-coefficient five-point operator in place of the scalar r
+  // (kern::TbTerms::weights): w5 = (wS, wE, wN, wW, wC), finite; converted to the
+  // run's dtype here. Every stencil launch then runs tb_kernel_w5 (the CPU
+  // backend: cpu::tb's twin) and the probes probe_cone_w5; step_stats() takes the
+  // unfused path. Dirichlet or periodic axes, arith exact / fma (auto: fma), the
+  // temporal-blocked engine, no copy-swap, a solver built without source, rmap and
+  // faces; the depths the solver chooses are clamped to kMaxTBW5 while weights are set. nullptr returns to the scalar-r kernels, bit for bit.
+  // Between step() calls; drops the captured graphs, and a change between with
+  // and without weights drops the plans and measured schedules too (another
+  // kernel family: its own plan-cache keys).
+  void set_weights(const double* w5);
+  bool has_weights() const { return w5_on_; }
+  const double* weights() const { return w5_on_ ? w5_ : nullptr; }  // in the run's dtype
   // Probe points: the temperature at `count` owned points after EVERY step, the
   // levels inside a fused pass included. `points` holds count pairs (i, j) of
   // GLOBAL frame-inclusive indices, 1 <= i <= nrows_global, 1 <= j <= ncols
@@ -658,8 +671,14 @@ class Solver {
     t.ry = face_ry();
     t.gain = gain();
     t.robin = robin();
+    t.weights = weights();
     return t;
   }
+  bool w5_on_ = false;  // set_weights has filled w5_
+  double w5_[5] = {};
+  int arith_cfg_ = 0;   // cfg_.arith as the solver was built (set_weights(nullptr) returns to it)
+  bool arith_auto_ = false;  // ... and whether it was given as auto (-1)
+  int tb_cfg_ = 0, k_pref_cfg_ = 0;  // cfg_.tb / k_pref_ as built: with weights both are clamped to kMaxTBW5
   void drop_graphs();         // captured graphs hold the kernels of the run with / without a source or map
   // probe points (set_probes): this rank's points as (local row, column) pairs,
   // the history and the device-resident row base (HIP) or their host twins
@@ -761,6 +780,7 @@ class LoopbackGroup {
   void set_source_gain(const void* host, int64_t len, int64_t start);  // on every member (the whole schedule)
   // Solver::set_probes on every member (the global list: each keeps the points of its rows)
   void set_probes(const int64_t* points, int64_t count, int64_t capacity);
+  void set_weights(const double* w5);  // Solver::set_weights on every member
   int nranks() const { return (int)members_.size(); }
   Solver& member(int i) { return *members_[i]; }
 

@@ -98,6 +98,33 @@ __global__ __launch_bounds__(256) void probe_cone_rob(ProbeArgs a) {
   }
 }
 
+// The cone of the five-weight operator (ProbeArgs::wt): the same planes and levels,
+// every point the weighted sum of its five operands (probe_point_w5).
+template <typename T, int AR>
+__global__ __launch_bounds__(256) void probe_cone_w5(ProbeArgs a) {
+  __shared__ T plane[2][kProbeSide * kProbeSide];
+  const int64_t p = blockIdx.x;
+  const int64_t ci = a.pts[2 * p], cj = a.pts[2 * p + 1];
+  const int k = a.k, side = 2 * k + 1;
+  const T* src = static_cast<const T*>(a.src);
+  for (int idx = threadIdx.x; idx < side * side; idx += 256) {
+    const int u = idx / side, v = idx % side;
+    const int64_t row = ci - k + u, col = cj - k + v;
+    if (probe_loads(a, row, col)) plane[0][u * kProbeSide + v] = src[a.L.offset(row, col)];
+  }
+  __syncthreads();
+  const int64_t base = (a.base ? *a.base : 0) + a.base0;
+  T* hist = static_cast<T*>(a.hist);
+  for (int s = 1; s <= k; ++s) {
+    const int w = 2 * (k - s) + 1;
+    const T* in = plane[(s - 1) & 1];
+    T* out = plane[s & 1];
+    for (int idx = threadIdx.x; idx < w * w; idx += 256) probe_point_w5<T, AR>(a, ci, cj, s, idx, in, out);
+    __syncthreads();
+    if (threadIdx.x == 0 && base + s - 1 < a.capacity) hist[(base + s - 1) * a.P + p] = out[k * kProbeSide + k];
+  }
+}
+
 __global__ __launch_bounds__(64) void gain_step(const int64_t* from, int64_t* to, int k) {
   if (threadIdx.x == 0) *to = *from + k;
 }
@@ -117,7 +144,13 @@ void launch_mode(const ProbeArgs& a, int arith, hipStream_t stream) {
 
 template <typename T>
 void launch_typed(const ProbeArgs& a, int arith, hipStream_t stream) {
-  if (a.robin) {
+  if (a.w5) {
+    const dim3 grid((unsigned)a.P), block(256);
+    if (a.source || a.rmap || a.rx || a.gain || a.robin || a.wall_r0 != INT64_MIN || a.wall_c0 != INT64_MIN || arith > 1)
+      fail(__FILE__, __LINE__, "probe_cone: weights take the plain mode, Dirichlet or periodic axes and arith exact or fma");
+    if (arith == 0) hipLaunchKernelGGL((probe_cone_w5<T, 0>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((probe_cone_w5<T, 1>), grid, block, 0, stream, a);
+  } else if (a.robin) {
     const dim3 grid((unsigned)a.P), block(256);
     if (a.source || a.rmap || a.rx || a.gain || arith > 1)
       fail(__FILE__, __LINE__, "probe_cone: Robin walls take the plain mode and arith exact or fma");

@@ -313,8 +313,8 @@ RobCoef<T> rob_coef(int bc, const double* robin) {
 
 // The kernel family a launch runs (select_family). Plain: tb_kernel (general or
 // interior, any ring); Stats: its fused-statistics variant; Pipe: the wave-pair
-// kernel; the rest: the six feature families of tb_impl.hpp.
-enum class Family { Plain, Stats, Pipe, Ins, Rob, Src, Gain, Var, Div };
+// kernel; the rest: the seven feature families of tb_impl.hpp.
+enum class Family { Plain, Stats, Pipe, Ins, Rob, Src, Gain, Var, Div, W5 };
 // What the host needs to know of a feature family.
 struct FamilyInfo {
   int max_k;             // deepest pass,
@@ -353,6 +353,8 @@ void launch_family(const FamilyInfo& f, DType dt, int k, const TbTerms& t, const
     x.q2 = t.ry ? static_cast<const T*>(t.ry) + o : nullptr;
     x.g = static_cast<const T*>(t.gain.g);
     x.pos = t.gain.pos;
+    if (t.weights)
+      for (int i = 0; i < 5; ++i) x.w5.w[i] = (T)t.weights[i];
     with_ar_upto<MAXAR>(t.arith, f.no_form, [&](auto ar) {
       dispatch_feat<FAM, T, decltype(ar)::value>(k, (unsigned)a.nwaves, static_cast<const T*>(src) + o,
                                                  static_cast<T*>(dst) + o, a, x, stream);
@@ -382,7 +384,11 @@ const FamilyInfo* family_info(Family f) {
   static constexpr FamilyInfo div = family<FamDiv, 1>(
       kMaxTBDiv, "temporal depth exceeds the conservative-form kernels' deepest pass (kMaxTBDiv)",
       "face coefficients need arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 assume one r", true);
+  static constexpr FamilyInfo w5 = family<FamW5, 1>(
+      kMaxTBW5, "temporal depth exceeds the five-weight kernels' deepest pass (kMaxTBW5)",
+      "weights need arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 assume one r", true);
   switch (f) {
+    case Family::W5: return &w5;
     case Family::Ins: return &ins;
     case Family::Rob: return &rob;
     case Family::Src: return &src;
@@ -400,6 +406,9 @@ const FamilyInfo* family_info(Family f) {
 //   faces (rx, ry) / rmap / source [+ gain]: Div / Var / Src / Gain, every rect of
 //     the launch, interior ones too; one of the three at most, Dirichlet on both
 //     axes, arith 0 / 1, no statistics, no wave-pair kernel, depths to the family's.
+//   weights: W5, every rect of the launch, interior ones too; none of the three above and
+//     no gain, Dirichlet or periodic axes (the family runs on bc_layout's view like every
+//     launch), arith 0 / 1, no statistics, no wave-pair kernel, depths to kMaxTBW5.
 //   walls (insulated or Robin axes) under a general launch: Ins, or Rob with a
 //     Robin axis; an interior launch keeps tb_kernel (launch_rects carves the
 //     frame-column strips out of it).
@@ -415,6 +424,20 @@ Family select_family(DType dt, int k, const TbTerms& t, bool main, bool partials
                  "an axis has one boundary kind: Robin, periodic or insulated");
   Family fam = Family::Plain;
   const char *dirichlet = nullptr, *alone = nullptr;  // the family's messages for a bc / for statistics or pipe
+  if (t.weights) {
+    HEAT2D_REQUIRE(!t.source, "weights with a heat source: no kernel carries them together");
+    HEAT2D_REQUIRE(!t.rmap, "weights with a diffusivity map: the map scales one r, no kernel carries them together");
+    HEAT2D_REQUIRE(!t.rx && !t.ry, "weights with face coefficients: no kernel carries them together");
+    HEAT2D_REQUIRE(!t.gain.g, "weights with a gain schedule: a gain scales a heat source");
+    HEAT2D_REQUIRE(!(bc & (kBcWallX | kBcWallY)), "weights need Dirichlet or periodic axes: no insulated or Robin walls");
+    HEAT2D_REQUIRE(arith == 0 || arith == 1,
+                   "weights need arith 0 (exact) or 1 (fma): the scaled levels of 2 / 3 assume one r");
+    HEAT2D_REQUIRE(!partials, "weights have no fused-statistics kernel");
+    HEAT2D_REQUIRE(!pipe, "weights have no wave-pair kernel");
+    HEAT2D_REQUIRE(k <= kMaxTBW5, "temporal depth exceeds the five-weight kernels' deepest pass (kMaxTBW5)");
+    for (int i = 0; i < 5; ++i) HEAT2D_REQUIRE(std::isfinite(t.weights[i]), "weights must be finite");
+    return Family::W5;
+  }
   if (t.rx || t.ry) {
     HEAT2D_REQUIRE(t.rx && t.ry, "face coefficients need both buffers (rx and ry)");
     HEAT2D_REQUIRE(!t.source && !t.rmap, "face coefficients with a heat source or a diffusivity map: no kernel carries them together");
@@ -535,7 +558,8 @@ int64_t launch_rects_1(DType dt, const void* src, void* dst, const SlabLayout& L
   const FamilyInfo* fi = family_info(fam);
   const bool pipe = fam == Family::Pipe, every_rect = fi && fi->every_rect;
   if (every_rect) {
-    nwaves = std::min<int64_t>(nwaves, (int64_t)cu_count() * fi->occupancy(*fi, dt, k, arith));
+    // (occupancy: resident workgroups per CU, of fi->waves waves each)
+    nwaves = std::min<int64_t>(nwaves, (int64_t)cu_count() * fi->occupancy(*fi, dt, k, arith) * fi->waves);
     main = false;
   }
   HEAT2D_REQUIRE(nrect >= 1 && nrect <= (main ? kMainRects : kMaxRects), "bad rect count");

@@ -483,16 +483,45 @@ template <typename T, int K>
 struct GainState<T, K, true> {
   T gs[K];  // gs[s - 1]: the gain of level s
 };
+// W5 (tb_kernel_w5, the constant-coefficient five-point operator: a moving
+// medium, unequal diffusion numbers on the two axes, a linear loss): every
+// level is T' = wS*S + wE*E + wN*N + wW*W + wC*C with five wave-uniform weights
+// (the kernel's extra argument; `r` is not used), summed in the march's operand
+// order, every product and sum rounded,
+//   AR 0: ((((wS*S + wE*E) + wN*N) + wW*W) + wC*C)
+//   AR 1: p = wS*S; p = fma(wE, E, p); p = fma(wN, N, p); p = fma(wW, W, p); T' = fma(wC, C, p)
+// — the S and E terms where the plain march forms S + E (partial(), when the
+// centre row arrives), N and W and last the centre term in update(). No ring,
+// no load beside the plain march's. Pinned points keep C by a select (EK 1 / 3:
+// the wave-uniform frame-row test, EK 2 / 3: one bit per element, `pin`): a
+// product by a zero weight would not keep a -0.0 or a non-finite pad entry, and
+// the select costs one mask register where per-lane weights would cost 5 V.
+// (The state lives in a base that is empty unless W5, as the states above.)
+template <typename T>
+struct W5Coef {
+  T w[5];  // wS, wE, wN, wW, wC
+};
+constexpr int kW5S = 0, kW5E = 1, kW5N = 2, kW5W = 3, kW5C = 4;
+template <typename T, bool W5>
+struct W5State {};
+template <typename T>
+struct W5State<T, true> {
+  W5Coef<T> wt;
+  uint32_t pin;  // EK & 2: bit e = element e (memory order) lies in a Dirichlet / pad column
+};
 // The features of a march, one bit each (FEAT, the last template argument of
-// March, MarchF32 and march<>): the sections INS .. GAIN above.
-constexpr int kFeatIns = 1, kFeatSrc = 2, kFeatVar = 4, kFeatDiv = 8, kFeatGain = 16, kFeatRob = 32;
+// March, MarchF32 and march<>): the sections INS .. W5 above.
+constexpr int kFeatIns = 1, kFeatSrc = 2, kFeatVar = 4, kFeatDiv = 8, kFeatGain = 16, kFeatRob = 32, kFeatW5 = 64;
 constexpr bool feat_has(int feat, int bit) { return (feat & bit) != 0; }
 template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, int CL = K, int FEAT = 0>
 struct March : WallState<feat_has(FEAT, kFeatIns)>, SrcState<K, RING, feat_has(FEAT, kFeatSrc | kFeatVar)>,
                DivState<K, RING, feat_has(FEAT, kFeatDiv)>, GainState<T, K, feat_has(FEAT, kFeatGain)>,
-               RobState<T, feat_has(FEAT, kFeatRob)> {
+               RobState<T, feat_has(FEAT, kFeatRob)>, W5State<T, feat_has(FEAT, kFeatW5)> {
   static constexpr bool INS = feat_has(FEAT, kFeatIns), SRC = feat_has(FEAT, kFeatSrc), VAR = feat_has(FEAT, kFeatVar),
-                        DIV = feat_has(FEAT, kFeatDiv), GAIN = feat_has(FEAT, kFeatGain), ROB = feat_has(FEAT, kFeatRob);
+                        DIV = feat_has(FEAT, kFeatDiv), GAIN = feat_has(FEAT, kFeatGain), ROB = feat_has(FEAT, kFeatRob),
+                        W5 = feat_has(FEAT, kFeatW5);
+  static_assert(!W5 || (FEAT == kFeatW5 && (AR == 0 || AR == 1) && !ST),
+                "five weights: no other feature, unscaled arithmetic, no fused statistics");
   static_assert(!ROB || (INS && (AR == 0 || AR == 1) && !SRC && !VAR && !DIV),
                 "Robin walls: the insulated march's substitution sites, unscaled arithmetic, no source, map or faces");
   using S = TbShape<T, NV, K>;
@@ -604,6 +633,14 @@ struct March : WallState<feat_has(FEAT, kFeatIns)>, SrcState<K, RING, feat_has(F
         if constexpr (AR == 1) part[e] = fma_t((*rx)[e], de, p);
         else part[e] = p + (*rx)[e] * de;
       }
+    } else if constexpr (W5) {
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        const T east = e < V - 1 ? C[e + 1] : eastL;
+        const T p = this->wt.w[kW5S] * Sx[e];
+        if constexpr (AR == 1) part[e] = fma_t(this->wt.w[kW5E], east, p);
+        else part[e] = p + this->wt.w[kW5E] * east;
+      }
     } else if constexpr (ROB) {
       // (the ghost of the row wall only on the wall row: a wave-uniform branch)
       const bool swall = (EK & 1) && row == this->wall_hi;  // wave-uniform
@@ -643,6 +680,22 @@ struct March : WallState<feat_has(FEAT, kFeatIns)>, SrcState<K, RING, feat_has(F
     const T west0 = from_lower(C[V - 1]);
     const bool frame_row = (EK & 1) && ((uint32_t)(row - fixed_lo) >= (uint32_t)(fixed_hi - fixed_lo));  // wave-uniform
     const T rs = frame_row ? T(0) : r;                                      // EK 1: scalar select
+    if constexpr (W5) {  // ((part + wN*N) + wW*W) + wC*C; a pinned point keeps C (select)
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        const T west = e > 0 ? C[e - 1] : west0;
+        T q;
+        if constexpr (AR == 1)
+          q = fma_t(this->wt.w[kW5C], C[e], fma_t(this->wt.w[kW5W], west, fma_t(this->wt.w[kW5N], N[e], part[e])));
+        else
+          q = ((part[e] + this->wt.w[kW5N] * N[e]) + this->wt.w[kW5W] * west) + this->wt.w[kW5C] * C[e];
+        if constexpr (EK == 0) out[e] = q;
+        else if constexpr (EK == 1) out[e] = frame_row ? C[e] : q;
+        else if constexpr (EK == 2) out[e] = ((this->pin >> e) & 1u) ? C[e] : q;
+        else out[e] = (frame_row || ((this->pin >> e) & 1u)) ? C[e] : q;
+      }
+      return;
+    }
     if constexpr (DIV) {
       // rv: the row's east faces RX[row] (the west face of element 0 is the west lane's last
       // element), ryn: the north faces RY[row - 1]; r is 1, so re is 1 or 0
@@ -915,10 +968,13 @@ struct March : WallState<feat_has(FEAT, kFeatIns)>, SrcState<K, RING, feat_has(F
 // VAR: a map row sits there in the same order and is the Row `re` of the level.
 template <int K, int EK, int RING, int AR, bool ST = false, int CL = K, int FEAT = 0>
 struct MarchF32 : WallState<feat_has(FEAT, kFeatIns)>, SrcState<K, RING, feat_has(FEAT, kFeatSrc | kFeatVar)>,
-                  GainState<float, K, feat_has(FEAT, kFeatGain)>, RobState<float, feat_has(FEAT, kFeatRob)> {
+                  GainState<float, K, feat_has(FEAT, kFeatGain)>, RobState<float, feat_has(FEAT, kFeatRob)>,
+                  W5State<float, feat_has(FEAT, kFeatW5)> {
   static_assert(!feat_has(FEAT, kFeatDiv), "face coefficients run the element-wise march");
   static constexpr bool INS = feat_has(FEAT, kFeatIns), SRC = feat_has(FEAT, kFeatSrc), VAR = feat_has(FEAT, kFeatVar),
-                        GAIN = feat_has(FEAT, kFeatGain), ROB = feat_has(FEAT, kFeatRob);
+                        GAIN = feat_has(FEAT, kFeatGain), ROB = feat_has(FEAT, kFeatRob), W5 = feat_has(FEAT, kFeatW5);
+  static_assert(!W5 || (FEAT == kFeatW5 && (AR == 0 || AR == 1) && !ST),
+                "five weights: no other feature, unscaled arithmetic, no fused statistics");
   static_assert(!ROB || (INS && (AR == 0 || AR == 1) && !SRC && !VAR),
                 "Robin walls: the insulated march's substitution sites, unscaled arithmetic, no source or map");
   using F2 = float __attribute__((ext_vector_type(2)));
@@ -993,8 +1049,40 @@ struct MarchF32 : WallState<feat_has(FEAT, kFeatIns)>, SrcState<K, RING, feat_ha
   __device__ __forceinline__ float ghost1(int side, float c) const {
     return rob_ghost<AR>(this->g.a[side], c, this->g.b[side]);
   }
+  // W5: five packed operations per register pair — wS*S, then E here (east of a = (c0, c2) is b, east
+  // of b = (c1, c3) is (c2, c0 of lane + 1)); N, W and the centre term in w5_update (see W5State)
+  __device__ __forceinline__ F2 w2(int i) const { return F2{this->wt.w[i], this->wt.w[i]}; }
+  __device__ __forceinline__ Row w5_update(const Row& part, const Row& C, const Row& N, int32_t row) const {
+    const F2 Wa{from_lower(C.b.y), C.b.x};  // west of (c0, c2); west of (c1, c3) is a
+    Row q;
+    if constexpr (AR == 1) {
+      q.a = __builtin_elementwise_fma(w2(kW5C), C.a, __builtin_elementwise_fma(w2(kW5W), Wa, __builtin_elementwise_fma(w2(kW5N), N.a, part.a)));
+      q.b = __builtin_elementwise_fma(w2(kW5C), C.b, __builtin_elementwise_fma(w2(kW5W), C.a, __builtin_elementwise_fma(w2(kW5N), N.b, part.b)));
+    } else {
+      q.a = ((part.a + w2(kW5N) * N.a) + w2(kW5W) * Wa) + w2(kW5C) * C.a;
+      q.b = ((part.b + w2(kW5N) * N.b) + w2(kW5W) * C.a) + w2(kW5C) * C.b;
+    }
+    if constexpr ((EK & 2) != 0) {  // (pin: bit e = column c_e, memory order)
+      q.a.x = (this->pin & 1u) ? C.a.x : q.a.x;
+      q.b.x = (this->pin & 2u) ? C.b.x : q.b.x;
+      q.a.y = (this->pin & 4u) ? C.a.y : q.a.y;
+      q.b.y = (this->pin & 8u) ? C.b.y : q.b.y;
+    }
+    if constexpr ((EK & 1) != 0) {
+      const bool frame_row = (uint32_t)(row - fixed_lo) >= (uint32_t)(fixed_hi - fixed_lo);  // wave-uniform
+      if (frame_row) q = C;
+    }
+    return q;
+  }
   __device__ __forceinline__ Row partial(const Row& S, const Row& C, int32_t row) const {
-    if constexpr (ROB) {
+    if constexpr (W5) {
+      const F2 Eb{C.a.y, from_upper(C.a.x)};
+      const F2 pa = w2(kW5S) * S.a, pb = w2(kW5S) * S.b;
+      if constexpr (AR == 1)
+        return Row{__builtin_elementwise_fma(w2(kW5E), C.b, pa), __builtin_elementwise_fma(w2(kW5E), Eb, pb)};
+      else
+        return Row{pa + w2(kW5E) * C.b, pb + w2(kW5E) * Eb};
+    } else if constexpr (ROB) {
       const bool swall = (EK & 1) && row == this->wall_hi;  // wave-uniform
       Row E{C.b, F2{C.a.y, from_upper(C.a.x)}};             // east of (c0, c2), (c1, c3)
       if constexpr ((EK & 2) != 0) {  // (wall_e: bit e = column c_e, memory order)
@@ -1073,6 +1161,7 @@ struct MarchF32 : WallState<feat_has(FEAT, kFeatIns)>, SrcState<K, RING, feat_ha
   }
   __device__ __forceinline__ Row update(const Row& part, const Row& C, const Row& N, int32_t row,
                                         const Row* rv = nullptr) const {
+    if constexpr (W5) return w5_update(part, C, N, row);
     if constexpr (AR == 3 && EK == 0) {  // scaled: fma(b, C, sum) on packed pairs
       const Row sum = sum4(part, C, N, row);
       const F2 b2 = {fb, fb};
@@ -1107,6 +1196,10 @@ struct MarchF32 : WallState<feat_has(FEAT, kFeatIns)>, SrcState<K, RING, feat_ha
   // the even/odd pairs and need a transpose before the 16-B store.
   __device__ __forceinline__ VT update_last(const Row& part, const Row& C, const Row& N, int32_t row,
                                             const Row* rv = nullptr) const {
+    if constexpr (W5) {  // (the packed form, then memory order)
+      const Row q = w5_update(part, C, N, row);
+      return VT{q.a.x, q.b.x, q.a.y, q.b.y};
+    }
     if constexpr (AR == 3 && EK == 0) {  // scaled level K, unscaled by r^K at the store
       const Row sum = sum4(part, C, N, row);
       return VT{__builtin_fmaf(fb, C.a.x, sum.a.x) * fu, __builtin_fmaf(fb, C.b.x, sum.b.x) * fu,
@@ -1298,6 +1391,7 @@ struct MarchExtra {
   const T* qsrc2 = nullptr;       // kFeatDiv: RY
   const T* gain = nullptr;        // kFeatGain: the gain of the pass's level 1
   const RobCoef<T>* rob = nullptr;  // kFeatRob: the walls' pairs
+  const W5Coef<T>* w5 = nullptr;    // kFeatW5: the five weights
 };
 template <typename T, int NV, int K, int EK, int RING, int AR, bool ST = false, bool PS = false, int CLX = 0,
           int FEAT = 0>
@@ -1305,7 +1399,8 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
                                       int64_t t1, int lane, StatAcc* acc = nullptr,
                                       const MarchExtra<T>* x = nullptr) {
   constexpr bool INS = feat_has(FEAT, kFeatIns), SRC = feat_has(FEAT, kFeatSrc), VAR = feat_has(FEAT, kFeatVar),
-                 DIV = feat_has(FEAT, kFeatDiv), GAIN = feat_has(FEAT, kFeatGain), ROB = feat_has(FEAT, kFeatRob);
+                 DIV = feat_has(FEAT, kFeatDiv), GAIN = feat_has(FEAT, kFeatGain), ROB = feat_has(FEAT, kFeatRob),
+                 W5 = feat_has(FEAT, kFeatW5);
   using S = TbShape<T, NV, K>;
   constexpr int V = S::V;
   constexpr int ES = (int)sizeof(T);
@@ -1371,6 +1466,15 @@ __device__ __forceinline__ void march(const T* src, T* dst, const TbArgs& a, T r
     w.wall_e = me;
   }
   if constexpr (ROB) w.g = *x->rob;  // the walls' pairs, wave-uniform (the kernel's argument)
+  if constexpr (W5) {                // the weights, wave-uniform (the kernel's argument), and the pinned columns
+    w.wt = *x->w5;
+    uint32_t mp = 0;
+    if constexpr ((EK & 2) != 0) {
+#pragma unroll
+      for (int e = 0; e < V; ++e) mp |= (mycol + e < 0 || mycol + e >= a.ncols) ? (1u << e) : 0u;
+    }
+    w.pin = mp;
+  }
   if constexpr (SRC || VAR) {  // the source buffer / the map (qsrc) has the field's layout
     w.qrow = reinterpret_cast<const char*>(x->qsrc + a.col_lo);
     w.qdelta = w.qrow - w.srow;
@@ -1765,6 +1869,22 @@ __global__ __launch_bounds__(64) void tb_kernel_div(const T* __restrict__ src, T
       march<T, NV, K, EK, RING, AR, false, false, K, kFeatDiv>(src, dst, a, T(1), strip, t0, t1, lane, nullptr, &x)))
 }
 
+// The general kernel of the five-weight operator (`w`: wS, wE, wN, wW, wC in the
+// field's dtype, by value: an argument of this kernel only, so a captured launch
+// keeps them — TbArgs and every other kernel stay as they are; the scalar r is
+// not an argument). The same items and kinds as the general kernel; every item
+// runs the one-chain march with the weighted sum at every level (March W5). No
+// LDS; four waves per workgroup, as the general kernel.
+template <typename T, int NV, int K, int RING, int AR>
+__global__ __launch_bounds__(256) void tb_kernel_w5(const T* __restrict__ src, T* __restrict__ dst, TbArgs a,
+                                                    W5Coef<T> w) {
+  H2D_TB_WAVE(4)
+  MarchExtra<T> x;
+  x.w5 = &w;
+  H2D_TB_ITEMS(H2D_BY_KIND(
+      march<T, NV, K, EK, RING, AR, false, false, K, kFeatW5>(src, dst, a, T(0), strip, t0, t1, lane, nullptr, &x)))
+}
+
 // Resident workgroups of THREADS threads per CU for one kernel instance
 // (occupancy API; cached per device). FALLBACK: the answer when the query fails.
 template <auto KERNEL, int THREADS, int FALLBACK>
@@ -1800,7 +1920,7 @@ template <typename T, int AR>
 void dispatch_stats(int k, unsigned nblocks, const T* src, T* dst, const TbArgs& a, T r, hipStream_t s);
 template <typename T, int AR>
 int occupancy_blocks_stats(int k);
-// The six feature families (general kernel, ring 4): one dispatch / occupancy
+// The seven feature families (general kernel, ring 4): one dispatch / occupancy
 // pair, specialised per (family, T, AR) in the family's instantiation units.
 //   FamIns  tb_<dtype>_ins[_fma|_jac].hip  insulated edges, depths 1..kMaxTB
 //   FamRob  tb_<dtype>_rob[_fma].hip       Robin walls, depths 1..kMaxTBRob
@@ -1808,6 +1928,7 @@ int occupancy_blocks_stats(int k);
 //   FamGain tb_<dtype>_gain.hip            source with a gain schedule (both forms per unit)
 //   FamVar  tb_<dtype>_var[_fma].hip       diffusivity map, depths 1..kMaxTBVar
 //   FamDiv  tb_<dtype>_div[_fma].hip       conservative form, depths 1..kMaxTBDiv
+//   FamW5   tb_<dtype>_w5[_fma].hip        five weights, depths 1..kMaxTBW5
 // What a feature launch hands its kernel after (src, dst, a): each family takes its own part.
 template <typename T>
 struct FeatArgs {
@@ -1817,6 +1938,7 @@ struct FeatArgs {
   const T *q = nullptr, *q2 = nullptr;        // FamSrc, FamGain: the source; FamVar: the map; FamDiv: RX, RY
   const T* g = nullptr;                       // FamGain: the gain array
   const int64_t* pos = nullptr;               //          and its position word
+  W5Coef<T> w5{};                             // FamW5: the five weights
 };
 // A family: NAME, its kernel, threads per workgroup (256: four waves, the fallback
 // occupancy 1 workgroup per CU; 64: one wave, fallback 4), the kernel's name in
@@ -1842,6 +1964,7 @@ H2D_FAMILY(FamSrc, tb_kernel_src, 64, "heat-source", x.r, x.q)
 H2D_FAMILY(FamGain, tb_kernel_gain, 64, "gain-schedule", x.r, x.q, x.g, x.pos)
 H2D_FAMILY(FamVar, tb_kernel_var, 64, "diffusivity-map", x.q)
 H2D_FAMILY(FamDiv, tb_kernel_div, 64, "conservative-form", x.q, x.q2)
+H2D_FAMILY(FamW5, tb_kernel_w5, 256, "five-weight", x.w5)
 // nwaves: the waves of the launch (FAM::kWaves per workgroup); occupancy: resident workgroups per CU
 template <class FAM, typename T, int AR>
 void dispatch_feat(int k, unsigned nwaves, const T* src, T* dst, const TbArgs& a, const FeatArgs<T>& x, hipStream_t s);

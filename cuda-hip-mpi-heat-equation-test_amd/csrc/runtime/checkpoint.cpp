@@ -269,10 +269,41 @@ void read_robin(const std::string& js, Meta& m) {
     m.robin_sides |= 1 << k;
   }
 }
+// " \"weights\": [\"0x1.cp-4\", ...],\n" ("" without weights)
+std::string weights_json(const Meta& m) {
+  if (!m.weights_set) return "";
+  std::string o = " \"weights\": [";
+  for (int i = 0; i < 5; ++i) {
+    char b[64];
+    std::snprintf(b, sizeof(b), "%s\"%a\"", i ? ", " : "", m.weights[i]);
+    o += b;
+  }
+  return o + "],\n";
+}
+// the "weights" list of a meta.json (either writer's layout): five quoted hex floats
+void read_weights(const std::string& js, Meta& m) {
+  size_t p = js.find("\"weights\"");
+  if (p == std::string::npos) return;
+  size_t q = js.find('[', p);
+  HEAT2D_REQUIRE(q != std::string::npos, "malformed meta.json: \"weights\" is no list");
+  const size_t end = js.find(']', q);
+  HEAT2D_REQUIRE(end != std::string::npos, "malformed meta.json: \"weights\" is not closed");
+  for (int i = 0; i < 5; ++i) {
+    const size_t a = js.find('"', q + 1);
+    const size_t b = a == std::string::npos ? a : js.find('"', a + 1);
+    HEAT2D_REQUIRE(b != std::string::npos && b < end, "malformed meta.json: \"weights\" holds fewer than five strings");
+    const std::string t = js.substr(a + 1, b - a - 1);
+    char* e = nullptr;
+    m.weights[i] = std::strtod(t.c_str(), &e);
+    HEAT2D_REQUIRE(e && e != t.c_str() && *e == '\0', "malformed meta.json: a weight is no number (" + t + ")");
+    q = b;
+  }
+  m.weights_set = true;
+}
 }  // namespace
 
 void write_meta(const std::string& dir, const std::string& name, const Meta& m) {
-  char buf[1792];
+  char buf[2048];
   std::snprintf(buf, sizeof(buf),
                 "{\n \"format\": \"%s\",\n \"step\": %lld,\n \"nranks\": %d,\n \"dtype\": \"%s\",\n"
                 " \"n_owned\": %lld,\n \"n_input\": %lld,\n \"convention\": \"%s\",\n \"sigma\": %.17g,\n"
@@ -290,7 +321,9 @@ void write_meta(const std::string& dir, const std::string& name, const Meta& m) 
                  // (and the key of the source's gain schedule only with one)
                  (m.source_gain_sha256.empty() ? "" : " \"source_gain_sha256\": \"" + m.source_gain_sha256 + "\",\n") +
                  // (and the key of the Robin walls' pairs only with a Robin axis)
-                 robin_json(m)).c_str());
+                 robin_json(m) +
+                 // (and the key of the five weights only with them)
+                 weights_json(m)).c_str());
   write_atomic(join(join(dir, name), "meta.json"), buf);  // + fsync of the step directory (rank files' entries)
   write_atomic(join(dir, "latest"), name + "\n");  // the commit point
   // prune: keep the two newest complete saves, ordered by (step, generation)
@@ -367,6 +400,7 @@ Meta read_meta(const std::string& dir) {
     if (m.faces_sha256 == "null") m.faces_sha256.clear();
   }
   read_robin(js, m);
+  read_weights(js, m);
   auto bc_ok = [](const std::string& v) { return v == "dirichlet" || v == "periodic" || v == "insulated" || v == "robin"; };
   HEAT2D_REQUIRE(bc_ok(m.bc_x) && bc_ok(m.bc_y),
                  dir + ": meta.json: bc_x / bc_y must be dirichlet, periodic, insulated or robin");

@@ -190,6 +190,7 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
     }
     K = std::min<int>(K, kMaxTBRob);  // the Robin kernels' deepest pass
   }
+  arith_auto_ = cfg_.arith < 0;
   if (cfg_.arith < 0) {
     // auto: the contracted form when it is bitwise identical to the reference
     // rounding — r an exact power of two (sigma = 0.25 in every shipped
@@ -201,6 +202,7 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
                  "arith must be 0 (reference rounding), 1 (fma), 2 (jacobi, r = 1/4), 3 (fast) or -1 (auto)");
   HEAT2D_REQUIRE(cfg_.arith != 2 || cfg_.r == 0.25, "arith 2 (jacobi) needs r == 1/4 exactly (sigma = 0.25)");
   HEAT2D_REQUIRE(cfg_.arith != 3 || cfg_.r > 0, "arith 3 (fast) needs r > 0");
+  arith_cfg_ = cfg_.arith;
   bc_ = config_bc(cfg_);
   if (bc_) {
     const bool ins = (bc_ & (kern::kBcInsulatedX | kern::kBcInsulatedY)) != 0;
@@ -247,6 +249,8 @@ Solver::Solver(const SolverConfig& cfg, std::shared_ptr<Transport> tr, hipStream
   cfg_.tb = K;
   band_ = K;
   k_pref_ = tb_given ? K : std::min(K, tb_pref);
+  tb_cfg_ = K;
+  k_pref_cfg_ = k_pref_;
   HEAT2D_REQUIRE((cfg_.halo > 0 ? cfg_.halo : kDefaultHalo) >= K, "halo must be >= temporal depth");
   L_ = solver_layout(cfg_, rank, P);
   Lk_ = kern::bc_layout(L_, bc_);
@@ -431,7 +435,7 @@ bool Solver::pipe_ok(int k) const {
   // (nor with a heat source: the source kernel is the one-wave general one)
   // (nor with a diffusivity map, for the same reason)
   return kern::pipe_available(dtype(), k, cfg_.arith) && !(bc_ & kern::kBcWallY) && !cfg_.source && !cfg_.rmap &&
-         !cfg_.faces;  // (nor with face coefficients)
+         !cfg_.faces && !w5_on_;  // (nor with face coefficients or weights)
 }
 
 void Solver::launch_tb(const void* src, void* dst, int64_t rb, int64_t re, int k) {
@@ -922,7 +926,9 @@ std::string Solver::cache_ctx() const {
   // (plans tuned with the source kernels are another family; keys without a source stay as they were)
   // (and so are plans tuned with the diffusivity-map kernels)
   // (and with the conservative-form kernels)
-  return std::string(b) + (cfg_.source ? "|src1" : "") + (cfg_.rmap ? "|rmap1" : "") + (cfg_.faces ? "|faces1" : "");
+  // (and with the five-weight kernels)
+  return std::string(b) + (cfg_.source ? "|src1" : "") + (cfg_.rmap ? "|rmap1" : "") + (cfg_.faces ? "|faces1" : "") +
+         (w5_on_ ? "|w5" : "");
 }
 
 // The cached autotuned plan of depth k for this slab, re-validated by one
@@ -2018,7 +2024,7 @@ void Solver::step_stats(int64_t n, double out[6]) {
   // (periodic y: the fused-statistics march would count its ghost columns;
   // insulated axes: the fused-statistics kernel has no insulated edges)
   // (a heat source: the fused-statistics kernel has no source term)
-  if (!hip_ || jit_ || cfg_.copy_swap || cfg_.bc_y || cfg_.bc_x == kBcInsulated || cfg_.bc_x == kBcRobinKind || cfg_.source || cfg_.rmap || cfg_.faces) {
+  if (!hip_ || jit_ || cfg_.copy_swap || cfg_.bc_y || cfg_.bc_x == kBcInsulated || cfg_.bc_x == kBcRobinKind || cfg_.source || cfg_.rmap || cfg_.faces || w5_on_) {
     step(n - 1);
     step(1);
     stats(out, true);
@@ -2209,6 +2215,42 @@ void Solver::set_source(const void* host, int64_t ld) {
   if (hip_) H2D_HIP(hipMemcpy(src_buf_, stage.data(), stage.size(), hipMemcpyHostToDevice));
   else std::memcpy(src_buf_, stage.data(), stage.size());
   src_on_ = true;
+}
+
+void Solver::set_weights(const double* w5) {
+  if (w5) {
+    HEAT2D_REQUIRE(!jit_ && cfg_.engine == 0, "weights need the temporal-blocked engine (engine \"jit\" takes one r)");
+    HEAT2D_REQUIRE(!cfg_.copy_swap, "weights have no copy-swap mode");
+    HEAT2D_REQUIRE(!cfg_.source && !cfg_.rmap && !cfg_.faces,
+                   "weights with a heat source, a diffusivity map or face coefficients: no kernel carries them together");
+    HEAT2D_REQUIRE(!(bc_ & (kern::kBcWallX | kern::kBcWallY)),
+                   "weights need Dirichlet or periodic axes (no insulated or Robin five-weight kernels)");
+    HEAT2D_REQUIRE(arith_auto_ || arith_cfg_ == 0 || arith_cfg_ == 1,
+                   "weights have no arith jacobi / fast: their scaled levels assume one r (use exact, fma or auto)");
+    for (int i = 0; i < 5; ++i) {
+      const double v = cfg_.dtype == 0 ? (double)(float)w5[i] : w5[i];  // the run's dtype
+      HEAT2D_REQUIRE(std::isfinite(v), "weights must be finite in the run's dtype");
+    }
+  }
+  drop_graphs();  // (synchronises; the captured launches hold the old weights by value)
+  const bool was = w5_on_;
+  w5_on_ = w5 != nullptr;
+  for (int i = 0; i < 5; ++i) w5_[i] = w5 ? (cfg_.dtype == 0 ? (double)(float)w5[i] : w5[i]) : 0.0;
+  // auto: fma with weights (no reference program defines the term), the solver's own choice without
+  cfg_.arith = (w5_on_ && arith_auto_) ? 1 : arith_cfg_;
+  // the five-weight kernels' deepest pass: the clamp the other families take when the solver is built
+  cfg_.tb = w5_on_ ? std::min<int>(tb_cfg_, kMaxTBW5) : tb_cfg_;
+  k_pref_ = w5_on_ ? std::min<int>(k_pref_cfg_, kMaxTBW5) : k_pref_cfg_;
+  if (was != w5_on_) {  // another kernel family: its plans, timings and schedules are not this one's
+    for (int k = 0; k <= kMaxTB; ++k) {
+      split_[k] = kern::SplitPlan{};
+      tuned_ms_[k] = depth_ms_[k] = pre_ms_[k] = 0.f;
+      plan_origin_[k] = -1;
+    }
+    banded_.clear();
+    sched_.clear();
+    sched_replay_.clear();
+  }
 }
 
 void Solver::free_gain() {
@@ -2474,6 +2516,10 @@ void Solver::launch_cycle_aux(int k, hipStream_t stream) {
   a.r = cfg_.r;
   a.k = k;
   kern::probe_bounds(a, L_, bc_, robin());
+  if (w5_on_) {
+    a.w5 = 1;
+    for (int i = 0; i < 5; ++i) a.wt[i] = w5_[i];
+  }
   if (hip_) {
     a.pts = d_probe_pts_;
     a.base = d_probe_base_;
@@ -2591,6 +2637,10 @@ void LoopbackGroup::set_faces(const void* rx, const void* ry, int64_t ld) {
 
 void LoopbackGroup::set_source_gain(const void* host, int64_t len, int64_t start) {
   for (auto& m : members_) m->set_source_gain(host, len, start);
+}
+
+void LoopbackGroup::set_weights(const double* w5) {
+  for (auto& m : members_) m->set_weights(w5);
 }
 
 void LoopbackGroup::set_probes(const int64_t* points, int64_t count, int64_t capacity) {

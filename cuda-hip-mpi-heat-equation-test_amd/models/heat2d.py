@@ -235,6 +235,69 @@ def robin_wall_temperature(t_wall: float) -> tuple:
     return -1.0, float(2.0 * np.float64(t_wall))
 
 
+def weights_from(problem: Problem, nu_x=None, nu_y=None, vx: float = 0.0, vy: float = 0.0, decay: float = 0.0,
+                 scheme: str = "upwind") -> tuple:
+    """The five weights (wS, wE, wN, wW, wC) of ``weights=`` for
+    u_t + v . grad(u) = nu_x u_xx + nu_y u_yy - decay * u on the problem's grid,
+    in float64. x is the row axis (toward increasing i), y the column axis;
+    nu_x / nu_y default to problem.nu. With rx = nu_x dt/dx², ry = nu_y dt/dx²,
+    cx = vx dt/dx, cy = vy dt/dx:
+        central: wS = rx - cx/2, wN = rx + cx/2, wE = ry - cy/2, wW = ry + cy/2
+        upwind:  wS = rx + max(-cx, 0), wN = rx + max(cx, 0), wE = ry + max(-cy, 0), wW = ry + max(cy, 0)
+    and in both wC = 1 - (wS + wE + wN + wW) - decay*dt. A negative weight loses
+    the maximum principle (the solvers warn)."""
+    if scheme not in ("upwind", "central"):
+        raise ValueError(f"scheme must be 'upwind' or 'central', got {scheme!r}")
+    f = np.float64
+    dt, dx = f(problem.dt), f(problem.delta)
+    rx = f(problem.nu if nu_x is None else nu_x) * dt / (dx * dx)
+    ry = f(problem.nu if nu_y is None else nu_y) * dt / (dx * dx)
+    cx, cy = f(vx) * dt / dx, f(vy) * dt / dx
+    if scheme == "central":
+        wS, wN, wE, wW = rx - cx / 2, rx + cx / 2, ry - cy / 2, ry + cy / 2
+    else:
+        wS, wN = rx + max(-cx, f(0)), rx + max(cx, f(0))
+        wE, wW = ry + max(-cy, f(0)), ry + max(cy, f(0))
+    wC = f(1) - (wS + wE + wN + wW) - f(decay) * dt
+    return float(wS), float(wE), float(wN), float(wW), float(wC)
+
+
+_WEIGHT_NAMES = ("wS", "wE", "wN", "wW", "wC")
+
+
+def _check_weights(weights, np_dtype, *, arith, engine="tb", copy_swap=False, bc_x, bc_y, source=None, rmap=None,
+                   faces=None, source_gain=None):
+    """What a solver refuses with ``weights=`` (RuntimeError), the converted 5 doubles, and the
+    warning for a negative weight (today's r > 1/4 warning, generalised)."""
+    arr, w = N.weights_array(weights, np_dtype)
+    if arith in ("jacobi", "fast"):
+        raise RuntimeError(f"weights have no arith {arith!r}: the scaled levels assume one r (use exact, fma or auto)")
+    if engine == "jit":
+        raise RuntimeError("weights need the temporal-blocked engine (engine 'jit' takes one r)")
+    if copy_swap:
+        raise RuntimeError("weights have no copy-swap mode")
+    for name, bc in (("bc_x", bc_x), ("bc_y", bc_y)):
+        if bc in ("insulated", "robin"):
+            raise RuntimeError(f"weights need 'dirichlet' or 'periodic' axes: {name}={bc!r} has no five-weight kernels")
+    for name, v in (("source", source), ("rmap", rmap), ("faces", faces), ("source_gain", source_gain)):
+        if v is not None:
+            raise RuntimeError(f"weights together with {name}=: no kernel carries them together")
+    neg = {n: v for n, v in zip(_WEIGHT_NAMES, w) if v < 0}
+    if neg:
+        import warnings
+        warnings.warn("negative weight " + ", ".join(f"{n} = {v:.6g}" for n, v in neg.items()) +
+                      ": the update is no convex combination, the maximum principle is lost", RuntimeWarning, stacklevel=3)
+    return arr, w
+
+
+def _weights_info(h) -> dict:
+    """info()["weights"]: whether the native solver runs with weights, the values it runs (converted to the
+    run's dtype; None without) and the depth clamp of the five-weight kernels."""
+    v, s, m = (C.c_double * 5)(), C.c_int32(), C.c_int32()
+    N.call("heat2d_solver_weights", h, v, C.byref(s), C.byref(m))
+    return {"set": bool(s.value), "values": tuple(float(x) for x in v) if s.value else None, "max_tb": int(m.value)}
+
+
 def _robin_info(h, bc_x: str, bc_y: str) -> dict:
     """info()["robin"]: the pairs the native solver runs (converted to the
     run's dtype) for the sides of its Robin axes, and the depth clamp of the
@@ -337,6 +400,20 @@ class HeatSolver:
             of two, else exact — never jacobi), engine "tb", no copy_swap, no
             source / rmap / faces; info()["robin"] holds the converted pairs
             and the depth clamp.
+        weights: (wS, wE, wN, wW, wC), the constant-coefficient five-point
+            operator T' = wS*S + wE*E + wN*N + wW*W + wC*C at every fused level
+            (S = T[i+1,j], E = T[i,j+1], N = T[i-1,j], W = T[i,j-1], C = T[i,j];
+            :func:`weights_from` computes them for a moving medium, unequal
+            diffusivities on the two axes and a linear loss). Every product and
+            sum is rounded, ((((wS*S + wE*E) + wN*N) + wW*W) + wC*C); "fma": the
+            first product, then one fma per further operand: bitwise equal to
+            models.reference.ftcs(weights=) at any depth, plan and rank count.
+            problem.r is not used. Five finite entries, converted to the run's
+            dtype; a negative one warns (the maximum principle is lost).
+            "dirichlet" / "periodic" axes, arith "exact" / "fma" ("auto": fma),
+            engine "tb", no copy_swap, no source / rmap / faces / source_gain
+            (RuntimeError). :meth:`set_weights` replaces or drops them between
+            steps; info()["weights"] holds the converted values and the depth clamp.
         source: a heat source, u_t = nu lap(u) + f: the GLOBAL frame-inclusive
             array (rows + 2) x (n + 2) of the per-step increment S = dt * f (the
             solver does no scaling; converted to the field's dtype; its frame
@@ -411,7 +488,7 @@ class HeatSolver:
                  comm_cus: int = 0, autotune: int = -1, engine: str = "tb", arith: str = "auto",
                  slab_row0: Optional[int] = None, edge_shift: int = 0, bc_x: str = "dirichlet",
                  bc_y: str = "dirichlet", source=None, rmap=None, faces=None, probes=None,
-                 probe_steps: Optional[int] = None, source_gain=None, robin=None):
+                 probe_steps: Optional[int] = None, source_gain=None, robin=None, weights=None):
         self.problem = problem
         self.edge_shift = 0 if bc_x == "periodic" else int(edge_shift)  # (periodic x: no edge slabs)
         self.bc_x, self.bc_y = bc_x, bc_y
@@ -457,6 +534,10 @@ class HeatSolver:
             raise ValueError(f"arith must be one of {sorted(N.ARITH)}")
         cfg.arith = N.ARITH[arith]
         self.arith = arith
+        self.weights = None  # the converted five weights (set_weights)
+        if weights is not None:  # (refused before anything is built)
+            _check_weights(weights, self.np_dtype, arith=arith, engine=engine, copy_swap=copy_swap, bc_x=bc_x, bc_y=bc_y,
+                           source=source, rmap=rmap, faces=faces, source_gain=source_gain)
         cfg.source = int(source is not None)
         self.source_sha256 = None
         self.source_gain_sha256 = None
@@ -482,10 +563,29 @@ class HeatSolver:
             self.set_rmap(rmap)
         if faces is not None:
             self.set_faces(faces)
+        if weights is not None:
+            self.set_weights(weights)
         if probes is not None:
             self.set_probes(probes, probe_steps)
         if init:
             self.init()
+
+    def set_weights(self, weights) -> None:
+        """Replace the five weights (wS, wE, wN, wW, wC) of the constant-coefficient
+        operator T' = wS*S + wE*E + wN*N + wW*W + wC*C (``weights_from``; operands
+        S = T[i+1,j], E = T[i,j+1], N = T[i-1,j], W = T[i,j-1], C = T[i,j]) or
+        drop them (None: the scalar-r kernels again, bit for bit), between step()
+        calls. problem.r is not used with weights; arith "auto" runs "fma".
+        "dirichlet" / "periodic" axes, arith exact / fma / auto, engine "tb", no
+        copy_swap, no source / rmap / faces (RuntimeError); five finite entries
+        (ValueError); a negative weight warns. Captured graphs are dropped."""
+        if weights is None:
+            N.call("heat2d_solver_set_weights", self._h, None)
+            self.weights = None
+            return
+        arr, w = _check_weights(weights, self.np_dtype, arith=self.arith, bc_x=self.bc_x, bc_y=self.bc_y)
+        N.call("heat2d_solver_set_weights", self._h, arr)
+        self.weights = w
 
     def set_probes(self, points, steps: Optional[int] = None) -> None:
         """Replace the probe points (see the class docstring) or clear them
@@ -624,6 +724,7 @@ class HeatSolver:
                 "source_gain": _gain_info(self._h),  # {"set", "length", "position"}
                 "rmap": _rmap_info(self._h),
                 "faces": _faces_info(self._h),
+                "weights": _weights_info(self._h),  # {"set", "values": the converted five or None, "max_tb"}
                 "probes": self._probes(),  # {"count": this rank's, "capacity", "recorded"}
                 "rank": self.rank, "size": self.size, "layout": self.layout.as_dict()}
 
@@ -863,9 +964,14 @@ class LoopbackGroup:
                  tb: int = 0, tile_rows: int = 0, device: Optional[int] = None, arith: str = "auto",
                  overlap: bool = True, autotune: int = -1, comm_cus: int = 0, edge_shift: int = 0,
                  bc_x: str = "dirichlet", bc_y: str = "dirichlet", source=None, rmap=None, faces=None,
-                 probes=None, probe_steps: Optional[int] = None, source_gain=None, robin=None):
+                 probes=None, probe_steps: Optional[int] = None, source_gain=None, robin=None, weights=None):
         self.problem = problem
         self.bc_x, self.bc_y = bc_x, bc_y
+        self.arith = arith
+        self.weights = None
+        if weights is not None:  # the five-weight operator (HeatSolver weights=); refused before anything is built
+            _check_weights(weights, NP_DTYPES[DTYPES[dtype]], arith=arith, bc_x=bc_x, bc_y=bc_y, source=source, rmap=rmap,
+                           faces=faces, source_gain=source_gain)
         self.backend = resolve_backend(backend)
         self.dtype = DTYPES[dtype]
         if self.backend == "hip" and device is None:
@@ -903,6 +1009,8 @@ class LoopbackGroup:
             self.set_rmap(rmap)
         if faces is not None:
             self.set_faces(faces)
+        if weights is not None:
+            self.set_weights(weights)
         self._nprobes = 0
         if probes is not None:
             self.set_probes(probes, probe_steps)
@@ -958,6 +1066,20 @@ class LoopbackGroup:
         m = self.problem.n_owned
         rx, ry = _faces_arrays(faces, m, m, NP_DTYPES[self.dtype])
         N.call("heat2d_group_set_faces", self._h, rx.ctypes.data_as(C.c_void_p), ry.ctypes.data_as(C.c_void_p), m + 2)
+
+    def set_weights(self, weights) -> None:
+        """The five weights on every member, or None to drop them (HeatSolver.set_weights)."""
+        if weights is None:
+            N.call("heat2d_group_set_weights", self._h, None)
+            self.weights = None
+            return
+        arr, w = _check_weights(weights, NP_DTYPES[self.dtype], arith=self.arith, bc_x=self.bc_x, bc_y=self.bc_y)
+        N.call("heat2d_group_set_weights", self._h, arr)
+        self.weights = w
+
+    def weights_info(self, i: int = 0) -> dict:
+        """info()["weights"] of member i."""
+        return _weights_info(self._member(i))
 
     def set_probes(self, points, steps: Optional[int] = None) -> None:
         """Probe points on every member (HeatSolver.set_probes; the global list:

@@ -272,9 +272,52 @@ def _ftcs_step_faces(T: np.ndarray, arith: str, faces) -> np.ndarray:
     return out
 
 
+def weights_tuple(weights, dtype) -> tuple:
+    """``weights`` = (wS, wE, wN, wW, wC) checked and converted to ``dtype``: five
+    entries, each finite in the run's dtype. ValueError otherwise."""
+    try:
+        w = [x for x in weights]
+    except TypeError:
+        raise ValueError("weights must be a 5-tuple (wS, wE, wN, wW, wC)") from None
+    if len(w) != 5:
+        raise ValueError(f"weights must be a 5-tuple (wS, wE, wN, wW, wC), got {len(w)} entries")
+    t = np.dtype(dtype).type
+    with np.errstate(over="ignore"):
+        w = tuple(t(x) for x in w)
+    if not all(np.isfinite(x) for x in w):
+        raise ValueError(f"weights must be finite in the run's dtype, got {w}")
+    return w
+
+
+def _ftcs_step_weights(T: np.ndarray, arith: str, weights, bc_x: str, bc_y: str) -> np.ndarray:
+    """One step of the constant-coefficient five-point operator
+    T' = wS*S + wE*E + wN*N + wW*W + wC*C (a moving medium, unequal diffusion
+    numbers on the two axes, a linear loss: ``heat2d.weights_from``), operands in
+    the march's order, every product and sum rounded,
+        exact: T' = ((((wS*S + wE*E) + wN*N) + wW*W) + wC*C)
+        fma:   p = wS*S; p = fma(wE,E,p); p = fma(wN,N,p); p = fma(wW,W,p); T' = fma(wC,C,p)
+    (:func:`fma`: one rounding each). Axes "dirichlet" (frame pinned) or
+    "periodic" (:func:`wrap_frame` before the step); ``r`` is not used."""
+    if arith not in ("exact", "fma"):
+        raise ValueError("weights need arith 'exact' or 'fma' (jacobi / fast assume one r)")
+    for name, bc in (("bc_x", bc_x), ("bc_y", bc_y)):
+        if bc not in ("dirichlet", "periodic"):
+            raise ValueError(f"weights need 'dirichlet' or 'periodic' axes, got {name}={bc!r}")
+    wS, wE, wN, wW, wC = weights_tuple(weights, T.dtype)
+    T = wrap_frame(T, bc_x, bc_y)
+    c, s, e, n, w = T[1:-1, 1:-1], T[2:, 1:-1], T[1:-1, 2:], T[:-2, 1:-1], T[1:-1, :-2]
+    out = T.copy()
+    if arith == "fma":
+        b = lambda x: np.broadcast_to(x, c.shape)  # noqa: E731
+        out[1:-1, 1:-1] = fma(b(wC), c, fma(b(wW), w, fma(b(wN), n, fma(b(wE), e, wS * s))))
+    else:
+        out[1:-1, 1:-1] = (((wS * s + wE * e) + wN * n) + wW * w) + wC * c
+    return out
+
+
 def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
               source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None, gain=None,
-              robin=None) -> np.ndarray:
+              robin=None, weights=None) -> np.ndarray:
     """One FTCS step of a frame-inclusive field. On a Dirichlet axis the frame
     is kept fixed; on a periodic or insulated one it is refreshed from the
     owned points before the step (:func:`wrap_frame`) — the update and its
@@ -300,7 +343,14 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
     "fma"): before the step the frame entry next to an owned point C on a Robin
     side is set to the ghost value a * C + b ("fma": fma(a, C, b)), then the
     unchanged update runs — with a Robin axis "fma" is the contracted update
-    with a single rounding, fma(r, fma(-4, C, sum), C), as with a source."""
+    with a single rounding, fma(r, fma(-4, C, sum), C), as with a source.
+    weights ((wS, wE, wN, wW, wC); "dirichlet" or "periodic" axes, arith "exact" or
+    "fma", none of source / rmap / faces / gain / robin): the five-weight operator
+    (:func:`_ftcs_step_weights`); ``r`` is then not used. None: today's function."""
+    if weights is not None:
+        if source is not None or rmap is not None or faces is not None or gain is not None or robin is not None:
+            raise ValueError("weights together with source=, rmap=, faces=, a gain or robin= are not offered")
+        return _ftcs_step_weights(T, arith, weights, bc_x, bc_y)
     has_robin = bc_x == "robin" or bc_y == "robin"
     if has_robin and arith not in ("exact", "fma"):
         raise ValueError("a Robin wall needs arith 'exact' or 'fma' (the scaled levels of jacobi / fast would need b scaled per level)")
@@ -348,7 +398,7 @@ def ftcs_step(T: np.ndarray, r, arith: str = "exact", bc_x: str = "dirichlet", b
 def ftcs(problem: Problem, nsteps: int | None = None, dtype=np.float64, T0: np.ndarray | None = None,
          arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
          source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None,
-         source_gain=None, gain_start: int = 0, robin=None) -> np.ndarray:
+         source_gain=None, gain_start: int = 0, robin=None, weights=None) -> np.ndarray:
     """Run FTCS; returns the frame-inclusive field (frame entries on periodic
     / insulated axes: wrap / edge images of the returned owned points; on Robin
     axes their ghost values).
@@ -361,6 +411,12 @@ def ftcs(problem: Problem, nsteps: int | None = None, dtype=np.float64, T0: np.n
     (:func:`ftcs_step` gain=)."""
     T = initial_field(problem, dtype) if T0 is None else T0.astype(dtype)
     n = problem.ntime if nsteps is None else nsteps
+    if weights is not None:  # the five-weight operator (:func:`ftcs_step`); problem.r is not used
+        if source is not None or rmap is not None or faces is not None or source_gain is not None or robin is not None:
+            raise ValueError("weights together with source=, rmap=, faces=, source_gain= or robin= are not offered")
+        for _ in range(n):
+            T = ftcs_step(T, problem.r, arith, bc_x, bc_y, weights=weights)
+        return wrap_frame(T, bc_x, bc_y)
     if source_gain is not None:
         G = _gain_array(source_gain, T.dtype, source, gain_start, n)
         for q in range(n):
@@ -402,7 +458,7 @@ def _gain_array(source_gain, dtype, source, start: int, nsteps: int) -> np.ndarr
 def probe_history(problem: Problem, nsteps: int, probes, dtype=np.float64, T0: np.ndarray | None = None,
                   arith: str = "exact", bc_x: str = "dirichlet", bc_y: str = "dirichlet",
                   source: np.ndarray | None = None, rmap: np.ndarray | None = None, faces=None,
-                  source_gain=None, gain_start: int = 0, robin=None) -> np.ndarray:
+                  source_gain=None, gain_start: int = 0, robin=None, weights=None) -> np.ndarray:
     """The golden of the solver's probe points: the (nsteps, P) array whose row
     q holds the values :func:`ftcs_step` leaves at ``probes`` after step q + 1.
     ``probes``: P owned points (i, j) in frame-inclusive indices, 1 <= i, j <= n,
@@ -418,10 +474,12 @@ def probe_history(problem: Problem, nsteps: int, probes, dtype=np.float64, T0: n
     if len(p) and (p.min() < 1 or p[:, 0].max() > n or p[:, 1].max() > m):
         raise ValueError(f"probes must be owned points (1..{n}, 1..{m})")
     H = np.empty((nsteps, len(p)), dtype=T.dtype)
+    if weights is not None and source_gain is not None:
+        raise ValueError("weights together with source_gain= are not offered")
     G = None if source_gain is None else _gain_array(source_gain, T.dtype, source, gain_start, nsteps)
     for q in range(nsteps):
         T = ftcs_step(T, problem.r, arith, bc_x, bc_y, source, rmap, faces,
-                      gain=None if G is None else G[gain_start + q], robin=robin)
+                      gain=None if G is None else G[gain_start + q], robin=robin, weights=weights)
         H[q] = T[p[:, 0], p[:, 1]]
     return H
 

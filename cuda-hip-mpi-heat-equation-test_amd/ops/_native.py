@@ -71,6 +71,15 @@ def robin_array(robin, bc_x: str, bc_y: str, np_dtype):
     return arr, {k: (float(a), float(b)) for k, (a, b) in pairs.items()}
 
 
+def weights_array(weights, np_dtype):
+    """The 5 doubles the native side takes for ``weights=``: (wS, wE, wN, wW, wC)
+    checked (five finite entries) and converted to the run's dtype
+    (models.reference.weights_tuple). Returns (array, tuple of the converted values)."""
+    from ..models.reference import weights_tuple
+    w = tuple(float(x) for x in weights_tuple(weights, np_dtype))
+    return (C.c_double * 5)(*w), w
+
+
 def bc_code(name: str, what: str = "bc") -> int:
     if name not in BC:
         raise ValueError(f"{what} must be one of {sorted(BC)}, got {name!r}")
@@ -187,6 +196,15 @@ _SIGS = {
     "heat2d_probe_cone_rob": (C.c_int, [C.c_int, _P, _LP, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_double), _P,
                                         _I64, _P, _P, C.c_int]),
     "heat2d_solver_robin": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "heat2d_tb_w5": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, _P, _I64, C.c_int, C.c_int,
+                               C.POINTER(C.c_double)]),
+    "heat2d_cpu_tb_w5": (C.c_int, [C.c_int, _P, _P, _LP, _I64, _I64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "heat2d_max_tb_w5": (C.c_int, []),
+    "heat2d_probe_cone_w5": (C.c_int, [C.c_int, _P, _LP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _I64, _P, _P,
+                                       C.c_int]),
+    "heat2d_solver_set_weights": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "heat2d_group_set_weights": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "heat2d_solver_weights": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "heat2d_wrap_cols": (C.c_int, [C.c_int, _P, _LP, _I64, _I64, _P, C.c_int]),
     "heat2d_wrap_rows": (C.c_int, [C.c_int, _P, _LP, _I64, _P, C.c_int]),
     "heat2d_init_field": (C.c_int, [C.c_int, _P, _LP, C.POINTER(IcParams), _P, _P, _P]),
@@ -422,6 +440,11 @@ def plan_cache_path() -> str:
     buf = C.create_string_buffer(4096)
     call("heat2d_plan_cache_path", buf, 4096)
     return buf.value.decode()
+
+
+def max_tb_w5() -> int:
+    """Deepest pass of the five-weight kernels (common.hpp kMaxTBW5)."""
+    return int(lib().heat2d_max_tb_w5())
 
 
 def max_tb() -> int:

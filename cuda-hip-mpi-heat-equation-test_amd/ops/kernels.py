@@ -84,11 +84,24 @@ def init_field(field: torch.Tensor, layout: N.Layout, ic, xcoord: np.ndarray,
                C.byref(p), xh.ctypes.data_as(C.c_void_p), yh.ctypes.data_as(C.c_void_p))
 
 
+def _weights_args(weights, src, arith, bc_x, bc_y, others, what):
+    """The raw ops' checks of ``weights=``: (5 doubles in src's dtype, arith code, bc bits)."""
+    if any(o is not None for o in others):
+        raise ValueError(f"{what}: weights together with source, rmap, faces, gain or robin: no kernel carries them")
+    for name, bc in (("bc_x", bc_x), ("bc_y", bc_y)):
+        if bc not in ("dirichlet", "periodic"):
+            raise ValueError(f"{what}: weights need 'dirichlet' or 'periodic' axes, got {name}={bc!r}")
+    if arith not in ("exact", "fma", "auto"):
+        raise ValueError(f"{what}: weights need arith 'exact', 'fma' or 'auto' (jacobi / fast assume one r)")
+    arr, _ = N.weights_array(weights, np.float32 if src.dtype == torch.float32 else np.float64)
+    return arr, N.ARITH["exact"] if arith == "exact" else N.ARITH["fma"], N.bc_bits(bc_x, bc_y)
+
+
 def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: float,
             rows: Optional[tuple[int, int]] = None, tile_rows: int = 0, arith: str = "exact",
             bc_x: str = "dirichlet", bc_y: str = "dirichlet", source: Optional[torch.Tensor] = None,
             rmap: Optional[torch.Tensor] = None, faces: Optional[tuple] = None,
-            gain: Optional[torch.Tensor] = None, gain_pos: int = 0, robin=None) -> None:
+            gain: Optional[torch.Tensor] = None, gain_pos: int = 0, robin=None, weights=None) -> None:
     """dst[rows] = k FTCS steps of src (temporal-blocked kernel). The k ghost rows
     around ``rows`` must be valid in ``src``; Dirichlet rows/cols are kept.
     ``arith``: "exact" (reference rounding), "fma" (contracted update) or
@@ -130,7 +143,30 @@ def tb_step(src: torch.Tensor, dst: torch.Tensor, layout: N.Layout, k: int, r: f
     level (arith "fma": fma(a, C, b)); the frame of the rows written gets the
     ghost values in ``dst``. Arith "exact" / "fma" / "auto", no ``source`` /
     ``rmap`` / ``faces``; on the device k is at most ``N.max_tb_rob()``
-    (csrc/kernels/tb_impl.hpp ``tb_kernel_rob``)."""
+    (csrc/kernels/tb_impl.hpp ``tb_kernel_rob``).
+    ``weights`` = (wS, wE, wN, wW, wC): the constant-coefficient five-point
+    operator T' = wS*S + wE*E + wN*N + wW*W + wC*C at every fused level (operands
+    S = T[i+1,j], E = T[i,j+1], N = T[i-1,j], W = T[i,j-1], C = T[i,j]; every
+    product and sum rounded, arith "fma" / "auto": the first product, then four
+    fmas); ``r`` is not used. "dirichlet" or "periodic" axes, none of ``source``
+    / ``rmap`` / ``faces`` / ``gain`` / ``robin``; on the device k is at most
+    ``N.max_tb_w5()`` (csrc/kernels/tb_impl.hpp ``tb_kernel_w5``)."""
+    if weights is not None:
+        w_arr, ar, bc = _weights_args(weights, src, arith, bc_x, bc_y, (source, rmap, faces, gain, robin), "tb_step")
+        _check_field(src, layout)
+        _check_field(dst, layout)
+        if src.dtype != dst.dtype or src.device != dst.device:
+            raise ValueError("src/dst dtype/device mismatch")
+        if src.data_ptr() == dst.data_ptr():
+            raise ValueError("tb_step is out-of-place (ping-pong fields)")
+        rb, re = (0, layout.nrows) if rows is None else rows
+        if src.is_cuda:
+            N.call("heat2d_tb_w5", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                   C.byref(layout), rb, re, k, _stream(src), tile_rows, ar, bc, w_arr)
+        else:
+            N.call("heat2d_cpu_tb_w5", dtype_code(src), C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                   C.byref(layout), rb, re, k, ar, bc, w_arr)
+        return
     if gain is not None:
         if source is None:
             raise RuntimeError("gain= scales a heat source: pass source=")
@@ -267,7 +303,7 @@ def probe_points(points, nrows_global: int, ncols: int) -> np.ndarray:
 def probe_cone(src: torch.Tensor, layout: N.Layout, k: int, r: float, points, arith: str = "exact",
                bc_x: str = "dirichlet", bc_y: str = "dirichlet", source: Optional[torch.Tensor] = None,
                rmap: Optional[torch.Tensor] = None, faces: Optional[tuple] = None,
-               gain: Optional[torch.Tensor] = None, robin=None) -> torch.Tensor:
+               gain: Optional[torch.Tensor] = None, robin=None, weights=None) -> torch.Tensor:
     """The probe-cone kernel alone (csrc/kernels/probe_cone.hip; CPU tensors:
     its twin): the values at ``points`` after each of the next k steps of
     ``src``, a (k, P) tensor of src's dtype and device — row s - 1 holds level
@@ -278,7 +314,27 @@ def probe_cone(src: torch.Tensor, layout: N.Layout, k: int, r: float, points, ar
     k gains of the levels, level s scaled by ``gain[s - 1]`` (``probe_cone_gain``).
     ``robin`` (with a "robin" axis, as :func:`tb_step`): the plain cone with the
     ghost value at the walls (``probe_cone_rob``), arith "exact" / "fma".
+    ``weights`` (as :func:`tb_step`): the cone of the five-weight operator
+    (``probe_cone_w5``), arith "exact" / "fma" / "auto"; ``r`` is not used.
     Nothing is written but the result."""
+    if weights is not None:
+        w_arr, ar, bc = _weights_args(weights, src, arith, bc_x, bc_y, (source, rmap, faces, gain, robin), "probe_cone")
+        _check_field(src, layout)
+        pts = probe_points(points, int(layout.nrows_global), int(layout.ncols))
+        loc = pts - np.array([1 + layout.row0, 1], dtype=np.int64)
+        if ((loc[:, 0] < 0) | (loc[:, 0] >= layout.nrows)).any():
+            raise ValueError("probe_cone: a point's row is not an owned row of this slab")
+        if not 1 <= k <= min(N.max_tb(), int(layout.halo)):
+            raise ValueError(f"probe_cone: k must be in [1, {min(N.max_tb(), int(layout.halo))}]")
+        out = torch.empty((k, len(pts)), dtype=src.dtype, device=src.device)
+        if len(pts) == 0:
+            return out
+        dpts = torch.from_numpy(np.ascontiguousarray(loc)).to(src.device)
+        N.call("heat2d_probe_cone_w5", dtype_code(src), C.c_void_p(src.data_ptr()), C.byref(layout), int(k), ar, bc, w_arr,
+               C.c_void_p(dpts.data_ptr()), len(pts), C.c_void_p(out.data_ptr()), _stream(src), int(src.is_cuda))
+        if src.is_cuda:
+            torch.cuda.current_stream(src.device).synchronize()  # keep dpts alive until done
+        return out
     if gain is not None:
         if source is None:
             raise RuntimeError("gain= scales a heat source: pass source=")

@@ -68,6 +68,14 @@ def build_parser():
                              "stability warning. "
                              "Checkpoints record the converted pairs exactly; a restart takes them from there and a "
                              "contradicting flag fails")
+    ap.add_argument("--weights", default=None, metavar="wS,wE,wN,wW,wC", type=_weights5,
+                    help="the constant-coefficient five-point operator T' = wS*S + wE*E + wN*N + wW*W + wC*C in place of "
+                         "r (S = T[i+1,j], E = T[i,j+1], N = T[i-1,j], W = T[i,j-1], C = T[i,j]; heat2d.weights_from "
+                         "computes them for a moving medium, unequal diffusivities and a linear loss): five finite "
+                         "numbers, converted to the run's dtype (a negative first one: --weights=...). Dirichlet or "
+                         "periodic axes, engine tb, arith exact / fma (auto is fma), not with --source, --rmap, --faces "
+                         "or --copy-swap. A negative weight draws a warning. Checkpoints record the converted values "
+                         "exactly; a restart takes them from there and a contradicting flag fails")
     ap.add_argument("--source", default=None, metavar="FILE.npy",
                     help="heat source u_t = nu lap(u) + f: the frame-inclusive (n+2) x (n+2) array of the per-step "
                          "increment dt * f (converted to the run's dtype; a wrong shape fails), added at every step "
@@ -117,6 +125,17 @@ def build_parser():
     ap.add_argument("--share-gpu", action="store_true",
                     help="every rank on GPU 0 (--transport peer or auto): the multi-process path on one GPU")
     return ap
+
+
+def _weights5(text: str):
+    """'wS,wE,wN,wW,wC' -> the 5-tuple: the argument of --weights."""
+    try:
+        w = tuple(float(v) for v in text.split(","))
+    except ValueError:
+        w = ()
+    if len(w) != 5:
+        raise argparse.ArgumentTypeError(f"expected wS,wE,wN,wW,wC (five numbers), got {text!r}")
+    return w
 
 
 def _robin_pair(text: str):
@@ -361,6 +380,28 @@ def run(argv=None) -> int:
         if arith in ("jacobi", "fast"):
             raise SystemExit(f"heat2d: --arith {arith} has no Robin walls (their scaled levels would need b scaled per "
                              "level): use exact, fma or auto")
+    # the five weights: the flag, or a restart checkpoint's (a contradicting flag fails)
+    weights = a.weights
+    if a.restart:
+        kept = checkpoint.weights_from_meta(saved)
+        if weights is not None and tuple(float(np_dtype(x)) for x in weights) != kept:
+            raise SystemExit(f"heat2d: --weights {','.join(map(repr, weights))} conflicts with the checkpoint's weights = {kept}")
+        weights = kept
+    if weights is not None:
+        # the solver's own rules (what weights do not go with) and its warning for a negative weight, here
+        # so that both speak before anything is built
+        import warnings
+        from heat2d.models.heat2d import _check_weights
+        try:
+            with warnings.catch_warnings(record=True) as caught:
+                warnings.simplefilter("always")
+                weights = _check_weights(weights, np_dtype, arith=a.arith, engine=engine, copy_swap=a.copy_swap, source=source,
+                                         rmap=rmap, faces=faces, source_gain=source_gain, **bc)[1]
+        except (RuntimeError, ValueError) as e:
+            raise SystemExit(f"heat2d: --weights: {e}")
+        for w in caught if root else ():
+            print(f"warning: {w.message}", file=sys.stderr)
+        arith = "fma" if a.arith == "auto" else a.arith  # (no reference program defines the term: auto is the cheap form)
     if bc["bc_x"] == "periodic" and world > 1 and backend == "hip" and a.transport in ("rccl", "peer"):
         raise SystemExit(f"heat2d: --transport {a.transport} does not pair the first rank with the last: periodic x "
                          "on more than one rank needs --transport host (or auto)")
@@ -381,16 +422,22 @@ def run(argv=None) -> int:
     if a.edge_shift not in ("auto", "measure"):
         edge_shift = int(a.edge_shift)
     elif world >= 3 and (backend == "hip" or a.edge_shift == "measure") and engine == "tb" and \
-            bc["bc_x"] != "periodic" and source is None and rmap is None and faces is None:  # (periodic x: no edge slabs; the probe slabs carry no source / map)
+            bc["bc_x"] != "periodic" and source is None and rmap is None and faces is None and weights is None:  # (periodic x: no edge slabs; the probe slabs carry no source / map / weights)
         edge_shift = _measure_edge_shift(prob, a, rank, world, local, backend, kinds[0], engine, arith,
                                          min(nsteps, 48), root and not a.quiet)
 
     def make_solver(tr):
+        import warnings
+        with warnings.catch_warnings():  # (a negative weight: warned about above, once)
+            warnings.simplefilter("ignore", RuntimeWarning)
+            return _make(tr)
+
+    def _make(tr):
         return HeatSolver(prob, dtype=a.dtype, backend=backend, tb=a.tb, overlap=not a.no_overlap,
                           copy_swap=a.copy_swap, managed=a.managed or var.managed, graph=a.graph, transport=tr,
                           device=local if backend == "hip" else None, engine=engine, arith=arith,
                           edge_shift=edge_shift, source=source, rmap=rmap, faces=faces, source_gain=source_gain,
-                          robin=robin or None, **bc)
+                          robin=robin or None, weights=weights, **bc)
 
     tr, s, kind, fallback = _make_solver(kinds, make_transport, make_solver, world)
     if fallback and root and not a.quiet:

@@ -135,6 +135,9 @@ def save(solver, directory: str, step: Optional[int] = None, extra: Optional[dic
         # (HeatSolver.robin); the key only with a Robin axis
         if getattr(solver, "robin", None):
             meta["robin"] = robin_to_meta(solver.robin)
+        # ... and the five weights (wS, wE, wN, wW, wC), the same way (HeatSolver.weights); the key only with weights
+        if getattr(solver, "weights", None) is not None:
+            meta["weights"] = weights_to_meta(solver.weights)
         meta.update(extra or {})
         _write_atomic(os.path.join(sd, "meta.json"), json.dumps(meta, indent=1))
         _write_atomic(os.path.join(directory, "latest"), os.path.basename(sd) + "\n")  # the commit point
@@ -152,6 +155,17 @@ def robin_to_meta(pairs: dict) -> dict:
 def robin_from_meta(meta: dict) -> dict:
     """The Robin pairs a checkpoint recorded, {side: (a, b)} ({} without a Robin axis)."""
     return {k: (float.fromhex(a), float.fromhex(b)) for k, (a, b) in meta.get("robin", {}).items()}
+
+
+def weights_to_meta(weights) -> list:
+    """[w.hex() x 5] of the converted weights (wS, wE, wN, wW, wC): what meta.json records."""
+    return [float(w).hex() for w in weights]
+
+
+def weights_from_meta(meta: dict):
+    """The five weights a checkpoint recorded, or None (written without weights)."""
+    w = meta.get("weights")
+    return None if w is None else tuple(float.fromhex(v) for v in w)
 
 
 def resolve(directory: str) -> str:
@@ -187,6 +201,13 @@ def load(solver, directory: str) -> dict:
     have, saved = {k: tuple(v) for k, v in (getattr(solver, "robin", None) or {}).items()}, robin_from_meta(meta)
     if have != saved:
         raise ValueError(f"the restart's Robin pairs differ from the checkpoint's ({have} != {saved})")
+    have, saved = getattr(solver, "weights", None), weights_from_meta(meta)  # (by value, as the Robin pairs)
+    if (None if have is None else tuple(have)) != saved:
+        if saved is None:
+            raise ValueError("the checkpoint was written without weights, this run has them")
+        if have is None:
+            raise ValueError(f"the checkpoint was written with weights {saved}: give the restart the same weights")
+        raise ValueError(f"the restart's weights differ from the checkpoint's ({tuple(have)} != {saved})")
     have, saved = getattr(solver, "source_sha256", None), meta.get("source_sha256")  # (older saves: none)
     if saved != have:
         if saved is None:
